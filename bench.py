@@ -149,6 +149,17 @@ def check_against_trapdoor(zkp, limb_sums, result):
     return bool(int(ginf) == int(einf) and np.array_equal(np.asarray(got, dtype=np.uint64), exp))
 
 
+def dump_outputs(dirname, result):
+    """--dump-outputs: what the caller of the timed path (zkp_hip.dist.msm_g1_sharded) received in the last timed step, exactly, as
+    float64 for an output-for-output comparison of two builds.  msm_xy.npy (12, 2): the affine sum's 12 Montgomery uint64 limbs (x then
+    y), each split into its low and high 32-bit halves; msm_inf.npy (1,): the infinity flag."""
+    os.makedirs(dirname, exist_ok=True)
+    xy = np.asarray(result[0], dtype=np.uint64).reshape(12)
+    halves = np.stack([xy & np.uint64(0xFFFFFFFF), xy >> np.uint64(32)], axis=1).astype(np.float64)
+    np.save(os.path.join(dirname, "msm_xy.npy"), halves)
+    np.save(os.path.join(dirname, "msm_inf.npy"), np.array([int(result[1])], dtype=np.float64))
+
+
 def allreduce_limb_sums(torch, dist, sums, device):
     t = torch.tensor(sums, dtype=torch.int64, device=device)  # entries < 2^58 per rank: world * 2^58 < 2^63 up to 32 ranks
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -593,7 +604,12 @@ def main():
     ap.add_argument("--extras-deadline-s", type=float, default=float(os.environ.get("ZKP_BENCH_EXTRAS_DEADLINE_S", "420")),
                     help="N > 1: seconds after the headline is known at which rank 0 prints the line with the extras it has and "
                          "exits (a peer that died inside a collective must not take the headline with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the MSM result of the last timed step as DIR/<name>.npy (float64, exact; "
+                         "rank 0); the synthetic inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.in_process_leg:
         print(json.dumps(in_process_leg(args)), flush=True)
         return
@@ -689,6 +705,8 @@ def main():
     if world > 1:
         sums = allreduce_limb_sums(torch, dist, sums, coll_device)
     bit_exact_full = check_against_trapdoor(zkp, sums, result)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * n * args.steps / elapsed

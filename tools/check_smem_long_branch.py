@@ -12,15 +12,18 @@ SIInsertWaitcnts runs before branch relaxation, so nothing waits.  This script d
 every long-branch sequence, walks the straight-line code before it (up to the last s_waitcnt that drains lgkmcnt, at most 64 instructions)
 for a scalar-memory instruction whose destination overlaps the pair the jump uses.  Exit code 1 and one line per hit.
     python tools/check_smem_long_branch.py [lib.so]"""
+import os
 import re
 import struct
 import subprocess
 import sys
+import tempfile
 
 SMEM = ("s_load_", "s_buffer_load_", "s_memtime", "s_memrealtime", "s_scratch_load_", "s_atc_probe")
 
 
-def code_object(path):
+def code_object(path, tmpdir):
+    """the gfx950 code object of the fat binary at path, written into tmpdir (private to this run); returns its path"""
     data = open(path, "rb").read()
     i = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
     n = struct.unpack_from("<Q", data, i + 24)[0]
@@ -31,8 +34,9 @@ def code_object(path):
         triple = data[off:off + tl].decode()
         off += tl
         if "gfx950" in triple:
-            open("/tmp/zkp_co_lb.o", "wb").write(data[i + o:i + o + sz])
-            return "/tmp/zkp_co_lb.o"
+            out = os.path.join(tmpdir, "zkp_co_lb.o")
+            open(out, "wb").write(data[i + o:i + o + sz])
+            return out
     raise SystemExit("no gfx950 code object in " + path)
 
 
@@ -83,7 +87,8 @@ def scan(dis):
 
 def main():
     path = sys.argv[1] if len(sys.argv) > 1 else "zkp-implementation_amd/libzkp_hip.so"
-    dis = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", "--mcpu=gfx950", code_object(path)], capture_output=True, text=True).stdout
+    with tempfile.TemporaryDirectory() as tmpdir:
+        dis = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", "--mcpu=gfx950", code_object(path, tmpdir)], capture_output=True, text=True).stdout
     hits, kernels, lb = scan(dis)
     for h in hits:
         print("HAZARD", h)

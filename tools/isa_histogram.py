@@ -8,10 +8,12 @@ The NTT passes have (almost) no data-dependent control flow -- every lane execut
 body is the dynamic mix up to the trip counts of the load / store loops; the dynamic totals per element come from the SQ counters
 (tools/prof_r05_ntt_counters.sh)."""
 import collections
+import os
 import re
 import struct
 import subprocess
 import sys
+import tempfile
 
 CLASSES = [
     ("mad64 (v_mad_u64_u32)", lambda o: o.startswith("v_mad_u64_u32") or o.startswith("v_mad_i64_i32")),
@@ -30,7 +32,8 @@ CLASSES = [
 ]
 
 
-def code_object(path):
+def code_object(path, tmpdir):
+    """the gfx950 code object of the fat binary at path, written into tmpdir (private to this run); returns its path"""
     data = open(path, "rb").read()
     i = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
     n = struct.unpack_from("<Q", data, i + 24)[0]
@@ -41,8 +44,9 @@ def code_object(path):
         triple = data[off:off + tl].decode()
         off += tl
         if "gfx950" in triple:
-            open("/tmp/zkp_co_hist.o", "wb").write(data[i + o:i + o + sz])
-            return "/tmp/zkp_co_hist.o"
+            out = os.path.join(tmpdir, "zkp_co_hist.o")
+            open(out, "wb").write(data[i + o:i + o + sz])
+            return out
     raise SystemExit("no gfx950 code object in " + path)
 
 
@@ -51,7 +55,8 @@ def main():
     md = "--md" in sys.argv
     path = args[0] if args and args[0].endswith(".so") else "zkp-implementation_amd/libzkp_hip.so"
     filters = [a for a in args if not a.endswith(".so")]
-    dis = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", "--mcpu=gfx950", code_object(path)], capture_output=True, text=True).stdout
+    with tempfile.TemporaryDirectory() as tmpdir:
+        dis = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", "--mcpu=gfx950", code_object(path, tmpdir)], capture_output=True, text=True).stdout
     for blk in re.split(r"\n(?=[0-9a-f]{16} <)", dis):
         m = re.match(r"[0-9a-f]{16} <(\S+)>:", blk)
         if not m or (filters and not any(f in m.group(1) for f in filters)):

@@ -5,6 +5,7 @@ import re
 import struct
 import subprocess
 import sys
+import tempfile
 
 path = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else "zkp-implementation_amd/libzkp_hip.so"
 filters = [a for a in sys.argv[1:] if not a.endswith(".so")]
@@ -18,8 +19,11 @@ for _ in range(n):
     triple = data[off:off + tl].decode()
     off += tl
     if "gfx950" in triple:
-        open("/tmp/zkp_co.o", "wb").write(data[i + o:i + o + sz])
-txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", "/tmp/zkp_co.o"], capture_output=True, text=True).stdout
+        co = data[i + o:i + o + sz]
+with tempfile.NamedTemporaryFile(suffix=".o") as f:  # private to this run: a fixed name under /tmp may belong to another user
+    f.write(co)
+    f.flush()
+    txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
 for blk in txt.split("- .agpr_count:")[1:]:
     name = re.search(r"\.name:\s+(\S+)", blk)
     if not name or (filters and not any(f in name.group(1) for f in filters)):
