@@ -3,6 +3,8 @@
 //   HostPool: run() from several caller threads (serialised inside), with and without a preceding warm(), warm() without a run() after it
 //   Uploader: submit() / wait() pairs whose job spins on a flag the submitter sets later (the shape of msm_partial_batch's use), a job that
 //             throws, one uploader per slot from concurrent caller threads
+//   RangeUpload: the guard of an uploader job -- released normally, released with an error, and a submitter that leaves its scope by
+//             return or by throw before it releases the job: the guard must cancel and join it
 #include <cstdio>
 #include <cstdlib>
 #include "host_threads.hpp"
@@ -79,6 +81,40 @@ int main() {
             });
         for (auto& c : callers) c.join();
         bad += errs.load();
+    }
+    // ---- RangeUpload
+    for (int round = 0; round < 200; round++) {
+        std::atomic<int> issued_calls{0};
+        const int mode = round % 4;  // 0 released, 1 released with an error, 2 leave by return, 3 leave by throw
+        auto submitter = [&]() -> int {
+            RangeUpload ru;
+            ru.submit(uploader(2), std::vector<uint64_t>{3, 5, 7}, 2, [] { return ZKP_HOST_THREADS_OK; },
+                      [&](size_t k, uint64_t off, uint64_t len) {
+                          issued_calls.fetch_add(1, std::memory_order_relaxed);
+                          const uint64_t want_off[3] = {2, 5, 10}, want_len[3] = {3, 5, 7};
+                          if (off != want_off[k] || len != want_len[k]) return ZKP_HOST_THREADS_E_DEVICE;
+                          return mode == 1 && k == 1 ? ZKP_HOST_THREADS_E_DEVICE : ZKP_HOST_THREADS_OK;
+                      });
+            if (mode == 2) return -1;
+            if (mode == 3) throw round;
+            ru.release(true);
+            if (mode == 0 && !ru.wait_issued(3)) return 1;
+            if (mode == 1 && ru.wait_issued(3)) return 1;
+            return ru.join() == (mode == 0 ? ZKP_HOST_THREADS_OK : ZKP_HOST_THREADS_E_DEVICE) ? 0 : 1;
+        };
+        int r;
+        try {
+            r = submitter();
+        } catch (int) {
+            r = -1;
+        }
+        if (mode >= 2 ? (r != -1 || issued_calls.load() != 0) : r != 0) bad++;
+        if (mode == 0 && issued_calls.load() != 3) bad++;
+    }
+    {   // the uploader is free again after a cancelled job
+        std::atomic<int> done{0};
+        uploader(2).submit([&]() -> int { done.store(1, std::memory_order_release); return ZKP_HOST_THREADS_OK; });
+        if (uploader(2).wait() != ZKP_HOST_THREADS_OK || done.load(std::memory_order_acquire) != 1) bad++;
     }
     std::printf("host threads stress: %d failures\n", bad);
     return bad ? 1 : 0;

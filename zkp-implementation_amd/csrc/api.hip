@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/zkp_hip.h"
@@ -218,6 +220,9 @@ struct DevBuf {  // grow-only device allocation
         cap = 0;
     }
 };
+template <class T> struct TypedBuf : DevBuf {  // the same, holding T elements
+    T* get() const { return static_cast<T*>(p); }
+};
 
 // ----------------------------------------------------------------------------------------------------
 // host <-> device field views
@@ -315,7 +320,10 @@ struct Ctx {
     DevBuf ntt_scratch;
     std::map<std::pair<unsigned, int>, void*> axis0_tw[2];  // [field] (log_len, inverse) -> omega_len^e, e < len (run_ntt_axis0)
     // MSM
-    DevBuf scalars, digits, sorted, entries, counts, start, perm, over, pieces, buckets, parts, pyr1, odd0, odd1, result;
+    DevBuf scalars, over;
+    TypedBuf<uint32_t> digits, sorted, counts, start, perm, result;
+    TypedBuf<uint2> entries;
+    TypedBuf<uint4> pieces, buckets, parts, pyr1, odd0, odd1;
     void* host_result = nullptr;  // pinned
     size_t host_result_cap = 0;
     void* fri_small = nullptr;    // pinned: the few dozen words zkp_fri_prove reads back after the folding phase
@@ -924,528 +932,7 @@ struct zkp_bases {
 
 namespace {
 
-// Window width.  Scalars have 255 bits and the signed-digit recoding needs one spare bit, so only widths dividing 256
-// give a top window that is as densely populated as the others (any other width leaves a few-bit top window whose
-// handful of buckets collect n / 8 points each: measured 4-9x slower at 2^14..2^18, profiles/r01_window_sweep.txt).
-unsigned pick_window_bits(size_t n) {
-    int c = n >= 2048 ? 16 : 8;
-    if (const char* e = getenv("ZKP_MSM_C")) {
-        int v = atoi(e);
-        if (v >= 8 && v <= 16) c = v;  // below 8 bits a scalar has more than 32 windows (MsmGeom::off holds 36 offsets)
-    }
-    return (unsigned)c;
-}
-
-// out[m] = sum_i scalars[m][i] * bases[i] as extended-Jacobian points (host), for `count` scalar vectors of the same
-// length over the same bases.  The vectors are stacked as extra windows of ONE pass through the kernels, so that a
-// batch of small MSMs (the 3 + 1 + 3 + 2 commitments of a PLONK proof) fills the GPU and pays the latency-bound
-// bucket reduction once.  With expanded bases (zkp_g1_bases_precompute) all windows of a scalar share one bucket set.
-// Host scalars fed range by range: the upload of range k+1 (second stream) overlaps the kernels of range k (shared-bucket
-// mode only: later ranges add into the same buckets).  Used by the host-pointer entry zkp_msm_g1.
-struct MsmFeed {
-    const uint64_t* h_scalars;  // n x 4 limbs on the host
-    hipStream_t copy_stream;    // non-blocking
-    hipEvent_t ev;
-    uint64_t range_log;         // log2 of the scalars per range
-    uint64_t first_len;         // != 0: the first range is this short (its upload is the exposed one), the rest follows in one piece
-                                // per 2^range_log scalars
-    uint64_t second_len = 0;    // != 0 (with first_len): a second range of this length before the rest
-};
-// bucket lanes (lane-per-bucket kernel: three waves on each of the 1024 SIMDs) / bucket quads below which a bucket's run is split
-// (round 5: lanes for TWO generations of workgroups, not one.  With exactly one resident generation the launch lasts as long as its
-// longest lanes -- the largest buckets, 1.8x the average run at 32 entries per bucket -- while the SIMDs that drew short runs idle; a
-// second generation lets the dispatcher even that out.  PLONK 2^16: the batches of three go from two to four parts per bucket, accumulate +
-// fold 1.82 -> 1.76 ms per proof, the proof 3.83 -> 3.75 ms on one box, tools/job_r05m.sh)
-static constexpr uint64_t SPLIT_FILL_LANES = 6 * 1024 * 64, SPLIT_FILL_QUADS = 2 * 1024 * 64 / 4 * 2;
-static constexpr uint64_t FOLD_LANE_MIN_ADDS = 1ull << 15;  // adds in one fold launch from which one lane per add is used (profiles/r05_m_fold_lane.md)
-static constexpr uint32_t MSM_MAX_SPLIT_LOG = 2;  // eight parts measured no better than four (2^16 single 0.535 against 0.529 ms, batches worse)
-#ifdef ZKP_MSM_CHECK  // diagnosis builds: wait for every kernel of the walk and say which one was reached
-#define MSM_TRACE(stream, what) do { hipError_t e_ = hipStreamSynchronize(stream); fprintf(stderr, "ZKP_MSM_CHECK range %llu: %s done (%d)\n", (unsigned long long)ridx, what, (int)e_); } while (0)
-#else
-#define MSM_TRACE(stream, what) do { } while (0)
-#endif
-int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t count, size_t n, hipStream_t st, HXyzz* out,
-                      const MsmFeed* feed = nullptr) {
-    if (n > bases->n) return fail(ZKP_E_SIZE, "more scalars than bases (kzg/src/scheme.rs:86)");
-    if (count == 0) return ZKP_OK;
-    if (n == 0) {
-        for (size_t m = 0; m < count; m++) out[m] = HXyzz::infinity();
-        return ZKP_OK;
-    }
-    if (n >= (1ull << 31)) return fail(ZKP_E_ARG, "n >= 2^31");
-    if (count > (size_t)MSM_MAX_BATCH) return fail(ZKP_E_ARG, "batch of more than 64 MSMs");
-    // expanded bases: always the shared bucket set.  Even a 2^8-term vector over 20-bit windows (2^19 mostly empty buckets)
-    // beats the per-window path, whose host tail alone (256 doublings) costs 0.4 ms: 0.35 vs 0.85 ms at 2^10 terms.
-    const bool shared = bases->pre_c != 0;
-    MsmGeom g;
-    g.c = shared ? bases->pre_c : pick_window_bits(n);
-    const uint32_t nwin1 = shared ? bases->pre_planes : 256 / g.c + (256 % g.c ? 1 : 0);
-    g.nslice = nwin1;
-    static_assert(sizeof(MsmGeom::off) / sizeof(uint16_t) == 36, "MsmGeom::off");
-    if (nwin1 + 1 > 36) return fail(ZKP_E_ARG, "more than 35 windows per scalar");
-    for (uint32_t s = 0; s <= nwin1 && s < 36; s++) g.off[s] = shared ? bases->pre_off[s] : (uint16_t)(s * g.c);
-    g.shared = shared ? 1u : 0u;
-    // Shared mode walks the scalars in ranges of at most 2^23: the expanded bases of a range are 13 x 2^23 x 128 B = 14 GB,
-    // and random 128-byte reads over a larger footprint fall off a translation cliff (accumulate: 6.3 G adds/s up to 2^23,
-    // 4.5 G/s at 2^24 in one range, profiles/r01_f_shared_buckets.md).  Later ranges add into the same buckets.
-    uint64_t range = n;            // the longest range: what the workspaces and the sort geometry are sized for
-    std::vector<uint64_t> lens;    // the scalar ranges in order (host-fed scalars: one or two short ranges first, see msm_host_scalars)
-    if (shared) {
-        // ... measured again in round 2 with 12 planes (22-bit windows): ranges of 2^24 (25.8 GB of planes) are still fine -- 2^24 32.73 ->
-        // 32.31 ms in one range, 2^26 128.4 -> 126.6 ms -- and 2^25 (51.5 GB) is over the cliff (2^25 in one range 80.0 against 63.8 ms):
-        // profiles/r02_j_sort_under_accumulate.md
-        const uint64_t max_range = bases->pre_planes <= 12 ? 1ull << 24 : 1ull << 23;
-        uint64_t cap = feed ? std::min<uint64_t>(max_range, 1ull << feed->range_log) : max_range;
-        if (const char* e = getenv("ZKP_MSM_RANGE_LOG")) {
-            int v = atoi(e);
-            if (v >= 10 && v <= 30) cap = 1ull << v;
-        }
-        const uint64_t npass = (n + cap - 1) / cap;
-        range = (n + npass - 1) / npass;
-        uint64_t want_first = feed ? feed->first_len : 0;
-        if (!feed && count == 1)
-            if (const char* e = getenv("ZKP_MSM_FIRST_PCT")) {  // tuning aid (resident scalars): a short first range whose sort is the exposed one
-                const int v = atoi(e);
-                if (v >= 1 && v <= 90) want_first = std::max<uint64_t>(1024, ((uint64_t)n * v / 100) & ~(uint64_t)1023);
-            }
-        uint64_t done = 0;  // short ranges first (they obey the range limit like the others), then the rest in equal ranges of at most `cap`
-        for (uint64_t want : {want_first, feed && want_first ? feed->second_len : (uint64_t)0})
-            if (want && done + want < n) {
-                lens.push_back(std::min<uint64_t>(want, cap));
-                done += lens.back();
-            }
-        const uint64_t rest = n - done, rpass = (rest + cap - 1) / cap, rr = (rest + rpass - 1) / rpass;
-        for (; done < n; done += lens.back()) lens.push_back(std::min<uint64_t>(rr, n - done));
-        range = *std::max_element(lens.begin(), lens.end());
-    } else {
-        lens.push_back(n);
-    }
-    g.resume = 0;
-    g.more = 0;
-    g.interleave = 0;  // set below once the geometry is known
-    g.ns = range;
-    g.plane_stride = bases->n;
-    g.nwin = shared ? (uint32_t)count : nwin1 * (uint32_t)count;  // sort windows = bucket sets
-    g.n = shared ? (uint64_t)nwin1 * range : n;                        // entries per sort window
-    if (g.n >= (1ull << 31)) return fail(ZKP_E_ARG, "windows x scalars >= 2^31 with expanded bases");
-    g.nb = 1u << (g.c - 1);
-    g.interleave = (g.nwin > 1 && g.n <= (1ull << 22)) ? 1u : 0u;  // measured: +5 % at 2^22, 0 at 2^23, -5 % at 2^24
-    const uint64_t entries = g.n;
-    uint32_t want = std::max<uint32_t>(1, (512 + g.nwin - 1) / g.nwin);
-    uint64_t maxchunks = (entries + 4095) / 4096;
-    g.nchunk = (uint32_t)std::min<uint64_t>(want, maxchunks);
-    if (const char* e = getenv("ZKP_MSM_NCHUNK")) {
-        int v = atoi(e);
-        if (v >= 1 && v <= 4096) g.nchunk = (uint32_t)std::min<uint64_t>((uint64_t)v, entries);
-    }
-    g.chunk = (entries + g.nchunk - 1) / g.nchunk;
-    // a bucket is oversized above 4x the average run; its pieces are no longer than an average run (they execute next to
-    // the ordinary lanes, so a longer piece would become the critical path)
-    g.run_limit = (uint32_t)std::max<uint64_t>(128, 4 * (entries / g.nb));
-    g.piece = (uint32_t)std::max<uint64_t>(32, entries / g.nb);
-    SortGeom sg;
-    // 2^19 buckets: 1024 partitions x 512 bins (first-pass runs of 4 entries per partition and tile instead of 2; measured
-    // sort 0.245 -> 0.225 ms at 2^20, 3.41 -> 3.31 ms at 2^24; 512 x 1024 is slower again)
-    // wider windows (21..24 bits over an expanded SRS: 12 or 11 slices instead of 13): 1024 bins per partition
-    sg.lo_bits = std::min<uint32_t>(g.c >= 21 ? 10 : g.c >= 20 ? 9 : 8, g.c - 1);
-    if (const char* e = getenv("ZKP_SORT_LO_BITS")) {  // tuning aid
-        const int v = atoi(e);
-        if (v >= 6 && v <= 10 && (uint32_t)v < g.c) sg.lo_bits = (uint32_t)v;
-    }
-    sg.nhi = g.nb >> sg.lo_bits;
-    if (sg.nhi > SORT_MAX_PART) return fail(ZKP_E_ARG, "window width above 24 bits is not supported by the sort");
-    const size_t W = g.nwin, nb = g.nb, c = g.c;
-    // Several scalar ranges: the digits + sort of range r+1 run on a second stream while range r is being accumulated (the sort is
-    // memory-bound, the accumulate issue-bound); what the accumulate reads (sorted indices, bucket starts, size order, piece
-    // descriptors) is double-buffered for it.
-    const bool overlap = shared && range < n && !getenv("ZKP_MSM_NO_OVERLAP");
-    const size_t nbuf = overlap ? 2 : 1;
-    ZCHK(ctx().digits.ensure(4 * W * entries));
-    ZCHK(ctx().sorted.ensure(nbuf * 4 * W * entries));
-    ZCHK(ctx().counts.ensure(4 * W * ((size_t)g.nchunk * sg.nhi + 2 * sg.nhi + 1 + 512)));
-    ZCHK(ctx().entries.ensure(8 * W * entries));
-    ZCHK(ctx().start.ensure(nbuf * 4 * W * (nb + 2)));
-    ZCHK(ctx().perm.ensure(nbuf * 4 * W * nb));
-    // oversized-bucket bookkeeping (msm_order): at most n / LIMIT oversized buckets and n / PIECE + that many pieces
-    const uint32_t over_cap = (uint32_t)std::min<uint64_t>(entries / 128 + 1, (uint64_t)nb);  // also bounds the saturated bin
-    const uint32_t desc_cap = (uint32_t)(entries / g.piece + entries / g.run_limit + 2);
-    const size_t over_bytes = ((4 * W * (2 + (size_t)over_cap + over_cap + 1) + 16 * W * (size_t)desc_cap) + 255) & ~(size_t)255;
-    ZCHK(ctx().over.ensure(nbuf * over_bytes));
-    ZCHK(ctx().pieces.ensure(256 * W * (size_t)desc_cap));
-    ZCHK(ctx().buckets.ensure(256 * W * nb));
-    // Few buckets for the machine (a small MSM over narrow windows, single pass): 2 or 4 lanes / quads share a bucket's run
-    // (msm.hpp, split_run) so that narrow windows -- a short bucket reduction -- still fill the SIMDs.
-    g.split_log = 0;
-    {
-        const bool quad_kernel = (uint64_t)g.n * g.nwin <= (1ull << 20);  // (the choice made at the launch below)
-        const uint64_t units = (uint64_t)nb * W, want_units = quad_kernel ? SPLIT_FILL_QUADS : SPLIT_FILL_LANES;
-        if (range >= n)
-            while (g.split_log < MSM_MAX_SPLIT_LOG && (units << g.split_log) < want_units) g.split_log++;
-        if (const char* e = getenv("ZKP_MSM_SPLIT_LOG")) {  // tuning aid
-            const int v = atoi(e);
-            if (v >= 0 && v <= (int)MSM_MAX_SPLIT_LOG && range >= n) g.split_log = (uint32_t)v;
-        }
-    }
-    if (g.split_log) ZCHK(ctx().parts.ensure(256 * W * nb * ((1u << g.split_log) - 1)));
-    ZCHK(ctx().pyr1.ensure(256 * W * nb));
-    ZCHK(ctx().odd0.ensure(256 * W * nb));
-    ZCHK(ctx().odd1.ensure(256 * W * nb));
-    // The c result points of every bucket set are written by the last kernel straight into pinned host memory (device-accessible:
-    // 5 KB over PCIe), followed by one flag word per bucket set; a device-to-host copy would be one more (blit) kernel launch per
-    // MSM.  The device buffer only holds the barrier counters of the last-levels launch, one 128-byte line each.
-    ZCHK(ctx().result.ensure(4 * PYR_BAR_STRIDE * W));
-    if (ctx().host_result_cap < 256 * W * c + 4 * W) {
-        if (ctx().host_result) HIPCHK(hipHostFree(ctx().host_result));
-        ctx().host_result = nullptr;
-        ctx().host_result_cap = 0;
-        HIPCHK(hipHostMalloc(&ctx().host_result, 256 * W * c + 4 * W, hipHostMallocPortable | hipHostMallocMapped));  // written by this slot's device
-        ctx().host_result_cap = 256 * W * c + 4 * W;
-    }
-    uint32_t* digits = reinterpret_cast<uint32_t*>(ctx().digits.p);
-    uint32_t* const sorted0 = reinterpret_cast<uint32_t*>(ctx().sorted.p);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(ctx().counts.p);
-    uint32_t* ptot = counts + W * (size_t)g.nchunk * sg.nhi;   // W x nhi
-    uint32_t* pstart = ptot + W * (size_t)sg.nhi;               // W x (nhi + 1)
-    uint32_t* ghist = pstart + W * (size_t)(sg.nhi + 1);        // W x 256 size histogram, then W x 256 rank cursors
-    uint32_t* gcur = ghist + W * 256;
-    uint2* entries_buf = reinterpret_cast<uint2*>(ctx().entries.p);
-    uint32_t* const start0 = reinterpret_cast<uint32_t*>(ctx().start.p);
-    uint32_t* const perm0 = reinterpret_cast<uint32_t*>(ctx().perm.p);
-    uint4* pieces = reinterpret_cast<uint4*>(ctx().pieces.p);
-    uint4* buckets = reinterpret_cast<uint4*>(ctx().buckets.p);
-    uint4* parts = reinterpret_cast<uint4*>(ctx().parts.p);
-    uint4* carry = reinterpret_cast<uint4*>(ctx().pyr1.p);  // hand-over array between scalar ranges: the reduction's second buffer, idle until then
-    uint32_t* tail_bar = reinterpret_cast<uint32_t*>(ctx().result.p);
-    uint4* const result_out = reinterpret_cast<uint4*>(ctx().host_result);                                       // W x c points, then
-    uint32_t* const result_flags = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx().host_result) + 256 * W * c);  // W flag words
-
-#ifdef ZKP_MSM_CHECK  // diagnosis builds: where every workspace lives, to place a faulting address
-    {
-        static bool once = false;
-        if (!once) {
-            once = true;
-            auto show = [](const char* name, const void* q, size_t bytes) {
-                fprintf(stderr, "ZKP_MSM_CHECK %-10s %p .. %p (%zu bytes)\n", name, q, static_cast<const char*>(q) + bytes, bytes);
-            };
-            show("bases", bases->d_xy, (size_t)bases->n * 128 * (bases->pre_planes ? bases->pre_planes : 1));
-            show("scalars", d_scalars[0], 32 * n);
-            show("digits", ctx().digits.p, ctx().digits.cap);
-            show("sorted", ctx().sorted.p, ctx().sorted.cap);
-            show("counts", ctx().counts.p, ctx().counts.cap);
-            show("entries", ctx().entries.p, ctx().entries.cap);
-            show("start", ctx().start.p, ctx().start.cap);
-            show("perm", ctx().perm.p, ctx().perm.cap);
-            show("over", ctx().over.p, ctx().over.cap);
-            show("pieces", ctx().pieces.p, ctx().pieces.cap);
-            show("buckets", ctx().buckets.p, ctx().buckets.cap);
-            show("pyr1", ctx().pyr1.p, ctx().pyr1.cap);
-            show("odd0", ctx().odd0.p, ctx().odd0.cap);
-            show("odd1", ctx().odd1.p, ctx().odd1.cap);
-            show("result", ctx().result.p, ctx().result.cap);
-            show("host_res", ctx().host_result, ctx().host_result_cap);
-            fprintf(stderr, "ZKP_MSM_CHECK geometry: n %zu range %llu first %llu rest %llu entries %llu nb %u nchunk %u over_cap %u desc_cap %u run_limit %u piece %u\n",
-                    n, (unsigned long long)range, (unsigned long long)lens[0], (unsigned long long)lens.back(), (unsigned long long)entries, g.nb, g.nchunk,
-                    over_cap, desc_cap, g.run_limit, g.piece);
-        }
-    }
-#endif
-    hipStream_t sst = st;  // stream of the digits + sort kernels
-    if (overlap) {
-        Ctx& cx = ctx();
-        if (!cx.sort_stream) {
-            HIPCHK(hipStreamCreateWithFlags(&cx.sort_stream, hipStreamNonBlocking));
-            for (hipEvent_t* e : {&cx.ev_sort[0], &cx.ev_sort[1], &cx.ev_acc[0], &cx.ev_acc[1], &cx.ev_begin})
-                HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-        sst = cx.sort_stream;
-        HIPCHK(hipEventRecord(cx.ev_begin, st));  // whatever the caller enqueued before (the scalars) comes first
-        HIPCHK(hipStreamWaitEvent(sst, cx.ev_begin, 0));
-    }
-    uint64_t ridx = 0;
-    // Host-fed scalars: the first range is uploaded by this thread, all later ones by the slot's uploader thread, started before the first
-    // range's kernels are enqueued (see Uploader); upload_issued = ranges whose copy and event record have been issued.
-    std::atomic<uint64_t> upload_issued{0};
-    std::atomic<int> upload_rc{ZKP_OK}, upload_go{0};
-    bool upload_submitted = false;
-    auto walk_ranges = [&]() -> int {
-    for (uint64_t off = 0, len = 0; off < n; off += len, ridx++) {
-        len = lens[ridx];
-        const size_t par = overlap ? (ridx & 1) : 0;  // buffer set of this range
-        uint32_t* sorted = sorted0 + par * W * entries;
-        uint32_t* start = start0 + par * W * (nb + 2);
-        uint32_t* perm = perm0 + par * W * nb;
-        uint4* desc = reinterpret_cast<uint4*>(reinterpret_cast<char*>(ctx().over.p) + par * over_bytes);  // W x desc_cap (16-byte aligned first)
-        uint32_t* over = reinterpret_cast<uint32_t*>(desc + W * (size_t)desc_cap);                        // W x 2
-        uint32_t* over_b = over + 2 * W;                                                                   // W x over_cap
-        uint32_t* over_off = over_b + W * (size_t)over_cap;                                                // W x (over_cap + 1)
-        if (overlap && ridx >= 2) HIPCHK(hipStreamWaitEvent(sst, ctx().ev_acc[par], 0));  // range r-2 is done with this buffer set
-        if (len != g.ns) {  // a range shorter than the longest (the last one, or the first of a host-fed walk): same buffers, smaller geometry
-            g.ns = len;
-            g.n = (uint64_t)nwin1 * len;
-            g.chunk = (g.n + g.nchunk - 1) / g.nchunk;
-        }
-        g.resume = off ? 1u : 0u;
-        g.more = off + len < n ? 1u : 0u;
-        if (feed) {  // this range's scalars: host -> device on the copy stream, the kernels below wait for them
-            hipEvent_t ev = feed->ev;
-            if (ridx == 0) {
-                // the uploader is woken FIRST and spins on upload_go while this thread is held by the first copy: a sleeping thread
-                // takes 50-300 us to come back, as long as the first upload itself
-                if (len < n) {
-                    Ctx& cx = ctx();
-                    const size_t later = lens.size() - 1;
-                    while (cx.copy_events.size() < later) {
-                        hipEvent_t e = nullptr;
-                        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                        cx.copy_events.push_back(e);
-                    }
-                    const int device = cx.device;
-                    Fr* d_dst = const_cast<Fr*>(d_scalars[0]);
-                    const uint64_t* h_src = feed->h_scalars;
-                    hipStream_t cs = feed->copy_stream;
-                    const hipEvent_t* evs = cx.copy_events.data();
-                    const uint64_t first = len;
-                    uploader(cx.slot).submit([=, &upload_issued, &upload_rc, &upload_go, &lens]() -> int {
-                        int rc = ZKP_OK;
-                        if (hipSetDevice(device) != hipSuccess) rc = ZKP_E_DEVICE;
-                        int go;
-                        while ((go = upload_go.load(std::memory_order_acquire)) == 0) __builtin_ia32_pause();  // the first copy is in the stream
-                        if (go < 0) return ZKP_OK;  // the caller gave up
-                        size_t k = 0;
-                        for (uint64_t o = first; rc == ZKP_OK && o < n; k++) {
-                            const uint64_t l = lens[k + 1];
-                            if (hipMemcpyAsync(d_dst + o, h_src + 4 * o, 32 * l, hipMemcpyHostToDevice, cs) != hipSuccess ||
-                                hipEventRecord(evs[k], cs) != hipSuccess)
-                                rc = ZKP_E_DEVICE;
-                            else
-                                upload_issued.store(k + 1, std::memory_order_release);
-                            o += l;
-                        }
-                        if (rc != ZKP_OK) upload_rc.store(rc, std::memory_order_release);
-                        return rc;
-                    });
-                    upload_submitted = true;
-                }
-                hipError_t e1 = hipMemcpyAsync(const_cast<Fr*>(d_scalars[0]), feed->h_scalars, 32 * len, hipMemcpyHostToDevice, feed->copy_stream);
-                if (e1 == hipSuccess) e1 = hipEventRecord(feed->ev, feed->copy_stream);
-                upload_go.store(e1 == hipSuccess ? 1 : -1, std::memory_order_release);
-                HIPCHK(e1);
-            } else {
-                while (upload_issued.load(std::memory_order_acquire) < ridx) {  // (host only: the GPU is busy with the ranges before)
-                    if (upload_rc.load(std::memory_order_acquire) != ZKP_OK) return fail(ZKP_E_DEVICE, "upload of a scalar range failed");
-                    __builtin_ia32_pause();
-                }
-                ev = ctx().copy_events[ridx - 1];
-            }
-            HIPCHK(hipStreamWaitEvent(sst, ev, 0));
-        }
-        {
-            ProfScope ps("msm_digits", sst);
-            DigitSources ds;  // digits laid out [msm][slice][scalar]: a shared-mode sort window is one msm
-            for (size_t m = 0; m < count; m++) ds.scalars[m] = d_scalars[m] + off;
-            hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)((len + MSM_THREADS - 1) / MSM_THREADS), (unsigned)count),
-                               dim3(MSM_THREADS), 0, sst, ds, bases->d_inf ? bases->d_inf + off : nullptr, g, nwin1, digits);
-            MSM_TRACE(sst, "digits");
-        }
-        {
-            ProfScope ps("msm_sort", sst, true);
-            hipLaunchKernelGGL(msm_parthist_kernel, dim3(g.nchunk, g.nwin), dim3(1024), 0, sst, digits, g, sg, counts);
-            MSM_TRACE(sst, "parthist");
-            hipLaunchKernelGGL(msm_partprefix_kernel, dim3((sg.nhi + 63) / 64, g.nwin), dim3(1024), 0, sst, counts, g, sg, ptot);
-            hipLaunchKernelGGL(msm_partstart_kernel, dim3(g.nwin), dim3(64), 0, sst, ptot, sg, pstart, ghist, tail_bar);
-            MSM_TRACE(sst, "partprefix + partstart");
-            const int ps_tile = partscatter_tile(sg.nhi);  // the largest tile whose staging fits the LDS next to 12 bytes per partition
-            if (ps_tile == PS_TILE_SMALL)
-                hipLaunchKernelGGL(msm_partscatter_kernel<PS_TILE_SMALL>, dim3(g.nchunk, g.nwin), dim3(1024),
-                                   partscatter_lds_bytes(sg.nhi, PS_TILE_SMALL), sst, digits, g, sg, counts, pstart, entries_buf);
-            else if (ps_tile == PS_TILE_MID)
-                hipLaunchKernelGGL(msm_partscatter_kernel<PS_TILE_MID>, dim3(g.nchunk, g.nwin), dim3(1024),
-                                   partscatter_lds_bytes(sg.nhi, PS_TILE_MID), sst, digits, g, sg, counts, pstart, entries_buf);
-            else
-                hipLaunchKernelGGL(msm_partscatter_kernel<PS_TILE_BIG>, dim3(g.nchunk, g.nwin), dim3(1024),
-                                   partscatter_lds_bytes(sg.nhi, PS_TILE_BIG), sst, digits, g, sg, counts, pstart, entries_buf);
-            MSM_TRACE(sst, "partscatter");
-            hipLaunchKernelGGL(msm_binsort_kernel, dim3(sg.nhi, g.nwin), dim3(1024), 0, sst, entries_buf, g, sg, pstart, start,
-                               sorted, ghist);
-            MSM_TRACE(sst, "binsort");
-            const dim3 rank_grid((g.nb + 1023) / 1024, g.nwin);
-            hipLaunchKernelGGL(msm_rank_kernel, rank_grid, dim3(1024), 0, sst, start, g, ghist, gcur, perm);
-            MSM_TRACE(sst, "rank");
-            hipLaunchKernelGGL(msm_order_kernel, dim3(g.nwin), dim3(1024), 0, sst, start, g, ghist, perm, over, over_b, over_off, desc,
-                               over_cap, desc_cap);
-            MSM_TRACE(sst, "order");
-        }
-        if (overlap) {
-            HIPCHK(hipEventRecord(ctx().ev_sort[par], sst));
-            HIPCHK(hipStreamWaitEvent(st, ctx().ev_sort[par], 0));
-        }
-        {
-            ProfScope ps("msm_accumulate", st, true);
-            // few entries: the lane-per-bucket kernel would be latency-bound by its longest run -> four lanes per bucket
-            // measured (tools/small_msm_bench.py, accumulate us lane -> quad): 2^16 x1 401 -> 293, x2 454 -> 525; 2^14 x3 261 -> 209;
-            // 2^12 x1 109 -> 60: four lanes per bucket up to 2^20 entries
-            const bool quad = !g.resume && !g.more && (uint64_t)g.n * g.nwin <= (1ull << 20);
-            const uint32_t per_block = quad ? ACC_THREADS / 4 : ACC_THREADS;
-            const uint32_t bucket_blocks = (uint32_t)((((uint64_t)g.nb << g.split_log) + per_block - 1) / per_block);
-            const uint32_t extra_blocks = std::min<uint32_t>((desc_cap + per_block - 1) / per_block, 64);
-            if (quad)
-                hipLaunchKernelGGL(msm_accumulate_quad_kernel, dim3((bucket_blocks + extra_blocks) * g.nwin), dim3(ACC_THREADS), 0,
-                                   st, reinterpret_cast<const uint4*>(bases->d_xy) + off * 8, sorted, start, perm, over, desc,
-                                   desc_cap, bucket_blocks, extra_blocks, g, buckets, pieces, parts, clk_record(CLK_MSM_ACCUMULATE));
-            else
-                hipLaunchKernelGGL(msm_accumulate_kernel, dim3((bucket_blocks + extra_blocks) * g.nwin), dim3(ACC_THREADS), 0, st,
-                                   reinterpret_cast<const uint4*>(bases->d_xy) + off * 8, sorted, start, perm, over, desc, desc_cap,
-                                   bucket_blocks, extra_blocks, g, buckets, pieces, parts, carry, clk_record(CLK_MSM_ACCUMULATE));
-            MSM_TRACE(st, "accumulate");
-            hipLaunchKernelGGL(msm_combine_kernel, dim3(std::min<uint32_t>(over_cap, 64), g.nwin), dim3(64), 0, st, over, over_b,
-                               over_off, over_cap, desc_cap, g, pieces, buckets, carry);
-            MSM_TRACE(st, "combine");
-            if (g.split_log) {  // buckets += parts, pairwise: split_log steps
-                const uint64_t cap = (uint64_t)g.nwin * g.nb;
-                const unsigned fold_x = (unsigned)((cap + MSM_THREADS / 4 - 1) / (MSM_THREADS / 4));
-                // a step with many adds runs one lane per add, a small one four lanes per add (latency): msm.hpp
-                static const uint64_t lane_from = getenv("ZKP_FOLD_LANE_MIN") ? strtoull(getenv("ZKP_FOLD_LANE_MIN"), nullptr, 10) : FOLD_LANE_MIN_ADDS;
-                for (uint32_t t = 0; t < g.split_log; t++) {
-                    const unsigned pairs = 1u << (g.split_log - 1 - t);
-                    if (cap * pairs >= lane_from)
-                        hipLaunchKernelGGL(msm_fold_parts_lane_kernel, dim3((unsigned)((cap + MSM_THREADS - 1) / MSM_THREADS), pairs),
-                                           dim3(MSM_THREADS), 0, st, buckets, parts, cap, t);
-                    else
-                        hipLaunchKernelGGL(msm_fold_parts_kernel, dim3(fold_x, pairs), dim3(MSM_THREADS), 0, st, buckets, parts, cap, t);
-                }
-            }
-        }
-        if (overlap) HIPCHK(hipEventRecord(ctx().ev_acc[par], st));
-    }
-    return ZKP_OK;
-    };
-    const int walk_rc = walk_ranges();
-    int up_rc = ZKP_OK;
-    if (upload_submitted) up_rc = uploader(ctx().slot).wait();  // (its job refers to this frame: joined on every path)
-    if (walk_rc != ZKP_OK || up_rc != ZKP_OK) {
-        // an early return out of the walk can leave digits / sort kernels queued on the second stream that were never joined back
-        // into st; the caller's WsOrder event covers st only, so drain them here before the workspaces can be handed to the next entry
-        if (overlap) (void)hipStreamSynchronize(sst);
-        if (feed) (void)hipStreamSynchronize(feed->copy_stream);
-        return walk_rc != ZKP_OK ? walk_rc : fail(ZKP_E_DEVICE, "upload of a scalar range failed");
-    }
-    HIPCHK(hipGetLastError());
-    for (size_t w = 0; w < W; w++) __atomic_store_n(result_flags + w, MSM_FLAG_PENDING, __ATOMIC_RELEASE);  // (the previous MSM's results were read before it returned)
-    uint4* pyr[2] = {buckets, reinterpret_cast<uint4*>(ctx().pyr1.p)};
-    uint4* odd[2] = {reinterpret_cast<uint4*>(ctx().odd0.p), reinterpret_cast<uint4*>(ctx().odd1.p)};
-    ProfScope* ps_red = new ProfScope("msm_bucket_reduce", st, true);
-    // tuning aids (A/B runs): workgroup size and count of the last-levels launch, and the per-array pair count from which it takes over
-    static const uint32_t tail_threads = getenv("ZKP_PYR_TAIL_THREADS") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_THREADS")) : PYR_TAIL_THREADS;
-    static const uint32_t tail_blocks = getenv("ZKP_PYR_TAIL_BLOCKS") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_BLOCKS")) : PYR_TAIL_BLOCKS;
-    static const uint32_t tail_half = getenv("ZKP_PYR_TAIL_HALF") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_HALF")) : 64u;
-    if (tail_threads < 64 || tail_threads > 512 || (tail_threads & 63) || !tail_blocks || tail_blocks > 256 || !tail_half)
-        return fail(ZKP_E_ARG, "ZKP_PYR_TAIL_THREADS must be a multiple of 64 up to 512, ZKP_PYR_TAIL_BLOCKS 1..256, ZKP_PYR_TAIL_HALF >= 1");
-    uint32_t level_tail = 0;  // first level whose per-array work is <= 64 pairs: the rest runs in one launch
-    while (level_tail + 1 < g.c && (g.nb >> (level_tail + 1)) > tail_half) level_tail++;
-    // ... unless even one workgroup per bucket set is more than the device keeps resident (many bucket sets, a partition with few
-    // CUs): the barrier of that launch would spin for its whole time-out, so every level runs as its own launch instead
-    const uint32_t max_waves = ctx().tail_max_waves;
-    if ((uint64_t)g.nwin * (tail_threads / 64) > max_waves) level_tail = g.c - 1;
-    for (uint32_t l = 0; l < level_tail; l++) {
-        PyrLevel L;
-        L.level = l;
-        L.half = g.nb >> (l + 1);
-        L.nb = g.nb;
-        L.nwin = g.nwin;
-        // levels with few adds are latency-bound: four lanes per add there (measured: 16 us -> ~6 us per level)
-        const uint64_t adds = (uint64_t)L.half * (l + 1) * g.nwin;
-        if (adds <= (1u << 16))  // threshold swept 2^14..2^20: 2^16 is the minimum of the reduction time
-            hipLaunchKernelGGL(msm_pyramid_quad_kernel, dim3((L.half + MSM_THREADS / 4 - 1) / (MSM_THREADS / 4), l + 1, g.nwin),
-                               dim3(MSM_THREADS), 0, st, pyr[l & 1], pyr[(l + 1) & 1], odd[l & 1], odd[(l + 1) & 1], L);
-        else
-            hipLaunchKernelGGL(msm_pyramid_kernel, dim3((L.half + MSM_THREADS - 1) / MSM_THREADS, l + 1, g.nwin),
-                               dim3(MSM_THREADS), 0, st, pyr[l & 1], pyr[(l + 1) & 1], odd[l & 1], odd[(l + 1) & 1], L);
-    }
-    if (level_tail + 1 < g.c) {
-        uint32_t* bar = tail_bar;  // zeroed by msm_partstart
-        uint32_t tb = tail_blocks;
-        while (tb > 1 && (uint64_t)tb * g.nwin * (tail_threads / 64) > max_waves) tb >>= 1;
-        // test hook (tests/test_gpu_parity.py): ask the barrier for one arrival more than there are workgroups, with a short
-        // time-out -- the path a workgroup that never became resident would take: MSM_TAIL_TIMEOUT flag, ZKP_E_DEVICE below
-        const bool starve = getenv("ZKP_TEST_TAIL_STARVE") != nullptr;
-        hipLaunchKernelGGL(msm_pyramid_tail_kernel, dim3(tb, g.nwin), dim3(tail_threads), 0, st, pyr[0], pyr[1], odd[0],
-                           odd[1], level_tail, g.c, g.nb, bar, result_out, result_flags, starve ? tb + 1 : tb,
-                           starve ? (1u << 12) : PYR_TAIL_SPIN_LIMIT);
-    } else {  // every level already ran as its own launch: only the gathering is left
-        const uint32_t fin = (g.c - 1) & 1;
-        hipLaunchKernelGGL(msm_collect_kernel, dim3(g.nwin), dim3(64), 0, st, pyr[fin], pyr[fin ^ 1], odd[fin], g.nb, g.c,
-                           result_out, result_flags);
-    }
-    delete ps_red;
-    HIPCHK(hipGetLastError());
-#ifdef ZKP_MSM_CHECK
-    {
-        uint32_t chk[32];
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipMemcpyFromSymbol(chk, HIP_SYMBOL(g_msm_check), sizeof(chk)));
-        for (int k = 0; k < 8; k++)
-            if (chk[4 * k]) fprintf(stderr, "ZKP_MSM_CHECK class %d: %u violations, first (%u, %u)\n", k, chk[4 * k], chk[4 * k + 1], chk[4 * k + 2]);
-    }
-#endif
-    // The last kernel writes the result points and then one flag word per bucket set straight into pinned host memory.  Up to 2^24
-    // entries per bucket set (an MSM of a few milliseconds) the host polls those flags instead of waiting for the stream: the
-    // runtime's wait costs 30-60 us of wake-up latency per MSM -- a quarter of the idle time of a 2^16-gate PLONK proof, which
-    // makes four of them on its critical path, and 1 % of a 2^20-term MSM (profiles/r05_k).  A kernel that never writes its flag
-    // (a fault) is caught by the stream wait the poll falls back to after two seconds.
-    if (count > 1 && !getenv("ZKP_POOL_NO_WARM")) host_pool().warm(std::chrono::microseconds(3000));  // the tails below run on the pool: wake it now
-    bool seen = false;
-    if (g.n <= (1ull << 24) && !getenv("ZKP_MSM_NO_POLL")) {
-        const auto t_poll0 = std::chrono::steady_clock::now();
-        uint64_t spins = 0;
-        for (;;) {
-            bool all = true;
-            for (size_t w = 0; w < W && all; w++)
-                all = (__atomic_load_n(result_flags + w, __ATOMIC_ACQUIRE) & MSM_FLAG_PENDING) == 0;
-            if (all) {
-                seen = true;
-                break;
-            }
-            if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t_poll0 > std::chrono::seconds(2)) break;
-            __builtin_ia32_pause();
-        }
-    }
-    if (!seen) HIPCHK(hipStreamSynchronize(st));  // the kernels' writes to the pinned buffer are visible to the host from here on
-    for (size_t w = 0; w < W; w++)
-        if (result_flags[w] & MSM_TAIL_TIMEOUT)
-            return fail(ZKP_E_DEVICE, "bucket reduction: the workgroups of the last levels did not all become resident (device shared "
-                                      "with another job?); no result was produced");
-    const auto t_tail0 = std::chrono::steady_clock::now();
-
-    // serial tail on the host.  Per bucket set: V = S + sum_l 2^l U_l.  Per-window mode: total = sum_w 2^(c w) V_w, and
-    // every (w, l) lands on its own bit position c w + l, so ONE Horner chain over the positions does it with c W
-    // doublings.  Shared mode: the expanded bases already carry the 2^(c w) factors, total = V of the single bucket set.
-    const uint32_t wins_per_msm = shared ? 1u : nwin1;
-    const uint32_t* host_res = reinterpret_cast<const uint32_t*>(ctx().host_result);  // (the pool's threads are in no context)
-    auto tail = [&](size_t m) {
-        const uint32_t* res = host_res + m * wins_per_msm * c * 64;  // 64 words / point
-        HXyzz total = HXyzz::infinity();
-        for (int pos = (int)(wins_per_msm * c) - 1; pos >= 0; pos--) {
-            total = total.dbl();
-            const int w = pos / (int)c, l = pos % (int)c;
-            const uint32_t* rw = res + (size_t)w * c * 64;
-            if (l <= (int)c - 2) total = total.add(xyzz_from_internal(rw + (size_t)(1 + l) * 64));
-            if (l == 0) total = total.add(xyzz_from_internal(rw));
-        }
-        out[m] = total;
-    };
-    if (count == 1) {
-        tail(0);
-    } else {  // the tails of a batch are independent serial chains: spread over the resident host workers
-        const std::function<void(size_t)> job = tail;
-        host_pool().run(job, count);
-    }
-    prof_host("msm_tail_host", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail0).count());
-    return ZKP_OK;
-}
-
-int msm_partial(const zkp_bases* bases, const Fr* d_scalars, size_t n, hipStream_t st, HXyzz* out) {
-    return msm_partial_batch(bases, &d_scalars, 1, n, st, out);
-}
+#include "msm_host.inc"  // msm_partial_batch: plan, workspaces, range walk, bucket reduction, host tail
 
 int ensure_fixed_base_table(hipStream_t st) {
     if (ctx().fb_ready) return ZKP_OK;
@@ -2112,36 +1599,7 @@ int msm_host_scalars(const zkp_bases* bases, const uint64_t* scalars, size_t n, 
             HIPCHK(hipStreamCreateWithFlags(&ctx().copy_stream, hipStreamNonBlocking));
             HIPCHK(hipEventCreateWithFlags(&ctx().copy_event, hipEventDisableTiming));
         }
-        MsmFeed feed{scalars, ctx().copy_stream, ctx().copy_event, 0, 0};
-        // two ranges: the upload of the second hides behind the first one's kernels; more ranges cost more in accumulate
-        // efficiency (shorter runs per bucket, one bucket read-modify-write per range) than the shorter exposed first upload
-        // saves -- 2^20: 1 range 3.49 ms, 2: 3.36-3.41, 4: 3.46-3.51, 8: 3.93 (gpurun_out/pcie_ranges.txt, round 2).
-        // Round 4: the two ranges need not be equal.  The first one's upload is exposed and both ranges pay a pass over the buckets,
-        // so the first is made just long enough for its kernels to cover the upload of the rest (profiles/r04_i).
-        uint64_t parts = 2;
-        // Round 5, with the uploader thread (profiles/r05_o): 25 % + 75 % up to 2^21 terms; from there a THIRD range pays for its pass over
-        // the buckets -- 10 % + 30 % + 60 %: the first upload is short, and 40 % of the insertions are done by the time the last upload ends
-        // (2^24: 36.0 -> 34.0 ms, 2^22: 9.8 -> 9.4-9.7; 2^20: 2.77 -> 2.80, not used there).
-        unsigned first_pct = n >= (1u << 21) ? 10 : 25;
-        if (const char* e = getenv("ZKP_MSM_FEED_RANGES")) {  // equal ranges, as rounds 2-3 (tuning aid)
-            const int v = atoi(e);
-            if (v >= 1 && v <= 64) { parts = (uint64_t)v; first_pct = 0; }
-        }
-        if (const char* e = getenv("ZKP_MSM_FEED_FIRST_PCT")) {  // tuning aid: share of the scalars in the first range (0 = equal ranges)
-            const int v = atoi(e);
-            if (v >= 0 && v <= 90) first_pct = (unsigned)v;
-        }
-        unsigned second_pct = n >= (1u << 21) ? 30 : 0;
-        if (const char* e = getenv("ZKP_MSM_FEED_SECOND_PCT")) {  // tuning aid: a second short range before the rest
-            const int v = atoi(e);
-            if (v >= 0 && v <= 80) second_pct = (unsigned)v;
-        }
-        if (first_pct) {
-            feed.first_len = std::max<uint64_t>(1024, ((uint64_t)n * first_pct / 100) & ~(uint64_t)1023);
-            if (second_pct) feed.second_len = std::max<uint64_t>(1024, ((uint64_t)n * second_pct / 100) & ~(uint64_t)1023);
-            parts = 1;  // the rest in one piece (or as many as the range limit asks for)
-        }
-        while ((parts << feed.range_log) < n) feed.range_log++;
+        const MsmFeed feed{scalars, ctx().copy_stream, ctx().copy_event, msm_feed_ranges(n)};  // (the range policy: msm_plan.hpp)
         return msm_partial_batch(bases, &d_sc, 1, n, st, r, &feed);
     }
     HIPCHK(hipMemcpyAsync(ctx().scalars.p, scalars, 32 * n, hipMemcpyHostToDevice, st));

@@ -1,6 +1,6 @@
-// Host-side thread helpers of the library (pure C++17, no HIP): the resident pool for the serial tails of MSM batches and the uploader
-// thread of host-fed MSMs.  In a header of their own so that tests/abi/host_threads_stress.cpp can run them under ThreadSanitizer
-// (tests/test_host_threads_cpu.py); api.hip includes this file inside its anonymous namespace.
+// Host-side thread helpers of the library (pure C++17, no HIP): the resident pool for the serial tails of MSM batches, the uploader
+// thread of host-fed MSMs and the caller's guard of an uploader job.  In a header of their own so that tests/abi/host_threads_stress.cpp
+// can run them under ThreadSanitizer (tests/test_host_threads_cpu.py); api.hip includes this file inside its anonymous namespace.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -155,4 +155,56 @@ Uploader& uploader(int slot) {  // one per device slot (the chunk MSMs of sharde
     while (all.size() <= (size_t)slot) all.push_back(new Uploader);
     return *all[(size_t)slot];
 }
+
+// The caller's side of one Uploader job that issues the later scalar ranges of a host-fed MSM.  It owns everything the job shares
+// with the caller (the hand-over flags and the range lengths), so the job never refers to the caller's frame; join() -- also run by
+// the destructor, on every way out of the caller's scope, exceptions included -- cancels a job that was never released and waits
+// for it.  The job is submitted before the caller issues the first range and spins until release(): a sleeping thread takes
+// 50-300 us to come back, as long as the first upload itself.
+class RangeUpload {
+    std::atomic<uint64_t> issued_{0};  // later ranges whose upload has been issued
+    std::atomic<int> rc_{ZKP_HOST_THREADS_OK}, go_{0};  // go: 0 wait, 1 issue, -1 give up
+    std::vector<uint64_t> lens_;       // the later ranges' lengths
+    Uploader* up_ = nullptr;           // != nullptr: a job was submitted and not yet joined
+
+public:
+    RangeUpload() = default;
+    RangeUpload(const RangeUpload&) = delete;
+    RangeUpload& operator=(const RangeUpload&) = delete;
+    ~RangeUpload() { (void)join(); }
+    // prepare() runs first; after release(true), issue(k, offset, length) for the later ranges k = 0, 1, ... (offsets from `first`)
+    // until one returns an error
+    template <class Prepare, class Issue>
+    void submit(Uploader& up, std::vector<uint64_t> later, uint64_t first, Prepare prepare, Issue issue) {
+        lens_ = std::move(later);
+        up.submit([this, first, prepare, issue]() -> int {
+            int rc = prepare();
+            int go;
+            while ((go = go_.load(std::memory_order_acquire)) == 0) __builtin_ia32_pause();  // the first range is being issued
+            if (go < 0) return ZKP_HOST_THREADS_OK;  // the caller gave up
+            uint64_t o = first;
+            for (size_t k = 0; rc == ZKP_HOST_THREADS_OK && k < lens_.size(); o += lens_[k++])
+                if ((rc = issue(k, o, lens_[k])) == ZKP_HOST_THREADS_OK) issued_.store(k + 1, std::memory_order_release);
+            if (rc != ZKP_HOST_THREADS_OK) rc_.store(rc, std::memory_order_release);
+            return rc;
+        });
+        up_ = &up;
+    }
+    void release(bool ok) { go_.store(ok ? 1 : -1, std::memory_order_release); }
+    // true once the first k later ranges have been issued; false if the upload failed first
+    bool wait_issued(uint64_t k) const {
+        for (; issued_.load(std::memory_order_acquire) < k; __builtin_ia32_pause())
+            if (rc_.load(std::memory_order_acquire) != ZKP_HOST_THREADS_OK) return false;
+        return true;
+    }
+    // the job's result (ZKP_HOST_THREADS_OK when none was submitted); a job still waiting for release() is cancelled first
+    int join() {
+        if (!up_) return ZKP_HOST_THREADS_OK;
+        int unreleased = 0;
+        go_.compare_exchange_strong(unreleased, -1, std::memory_order_acq_rel);
+        Uploader* up = up_;
+        up_ = nullptr;
+        return up->wait();
+    }
+};
 

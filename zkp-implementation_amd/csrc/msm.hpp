@@ -17,35 +17,19 @@
 #include "g1.hpp"
 #include "g1_28.hpp"
 #include "fq28_inv.hpp"
+#include "msm_plan.hpp"  // MsmGeom, SortGeom and the limits the host plan shares with the kernels
 
 namespace zkp {
 
 constexpr int MSM_THREADS = 256;
 constexpr int ACC_THREADS = 256;  // workgroup size of msm_accumulate (64 and 128 measure the same)
-
-// Two modes.  Per-window buckets (default): every c-bit window of every MSM of a batch is its own "sort window" with
-// n = ns entries and 2^(c-1) buckets.  Shared buckets (bases expanded with zkp_g1_bases_precompute): the W windows of a
-// scalar address W pre-multiplied copies of the base (planes 2^(c s) P_i), so ALL of them fall into ONE bucket set:
-// the sort window has n = W * ns entries, entry e = s * ns + i selects plane s, point i.
-struct MsmGeom {
-    uint32_t c;        // window bits
-    uint32_t nwin;     // sort windows (bucket sets) in this pass
-    uint32_t nb;       // buckets per window = 2^(c-1)   (bucket ids 1..nb)
-    uint32_t nchunk;   // chunks per window in the counting sort
-    uint64_t n;        // entries per sort window
-    uint64_t chunk;    // entries per chunk
-    uint64_t ns;       // scalars per MSM
-    uint64_t plane_stride;  // points per plane of the expanded bases (shared mode)
-    uint32_t nslice;   // c-bit windows per scalar
-    uint32_t shared;   // 1: shared bucket set
-    uint32_t run_limit;  // buckets with more entries are cut into pieces (msm_order)
-    uint32_t piece;      // entries per piece
-    uint32_t resume;     // 1: the buckets already hold the sums of earlier passes over other scalar ranges (shared mode)
-    uint16_t off[36];    // bit offset of every slice of a scalar (off[nslice] >= 256); widths <= c
-    uint32_t interleave; // 1: msm_accumulate walks the bucket sets interleaved (see there)
-    uint32_t split_log;  // 2^split_log lanes (quads) share a bucket's run, one contiguous part each (small problems, see msm_accumulate)
-    uint32_t more;       // 1: another scalar range follows: the bucket sums go to the hand-over array (msm_accumulate_body), not to `buckets`
-};
+// The kernels below take MsmGeom and SortGeom (msm_plan.hpp) by value: their layout is part of this file's kernels, pinned here
+#define ZKP_AT(f, o) offsetof(MsmGeom, f) == o
+static_assert(sizeof(MsmGeom) == 152 && ZKP_AT(c, 0) && ZKP_AT(nwin, 4) && ZKP_AT(nb, 8) && ZKP_AT(nchunk, 12) && ZKP_AT(n, 16) && ZKP_AT(chunk, 24) &&
+              ZKP_AT(ns, 32) && ZKP_AT(plane_stride, 40) && ZKP_AT(nslice, 48) && ZKP_AT(shared, 52) && ZKP_AT(run_limit, 56) && ZKP_AT(piece, 60) &&
+              ZKP_AT(resume, 64) && ZKP_AT(off, 68) && ZKP_AT(interleave, 140) && ZKP_AT(split_log, 144) && ZKP_AT(more, 148), "MsmGeom layout");
+#undef ZKP_AT
+static_assert(sizeof(SortGeom) == 8 && offsetof(SortGeom, lo_bits) == 0 && offsetof(SortGeom, nhi) == 4, "SortGeom layout");
 
 // Bucket, pyramid and odd-sum arrays are PLANE-MAJOR: a 256-byte XYZZ entry is 16 chunks of 16 bytes, and chunk q of entry e
 // lives at base[q * capacity + e] (capacity = nwin * nb entries, the same for all five arrays of a pass).  Lanes of a wave work
@@ -63,7 +47,6 @@ ZKP_DEV bool msm_check_fail(int cls, uint32_t v0, uint32_t v1) {
 }
 #endif
 // digit encoding in memory: (|d| << 1) | (d < 0); 0 = skip
-constexpr int MSM_MAX_BATCH = 64;
 struct DigitSources {
     const Fr* scalars[MSM_MAX_BATCH];  // one scalar vector per MSM of the batch (blockIdx.y), already offset to this range
 };
@@ -106,13 +89,6 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_digits_kernel(DigitSources sr
 //   level B: one workgroup per (window, partition) sorts its entries by the low 8 bits inside a few hundred KB.
 // Bucket ids are 1..nb; (b - 1) = hi * 2^lo_bits + lo.
 // ---------------------------------------------------------------------------------------------------------
-struct SortGeom {
-    uint32_t lo_bits;  // 8 or 9 (at most c - 1): bins of the second pass
-    uint32_t nhi;      // partitions per window = nb >> lo_bits
-};
-
-constexpr uint32_t SORT_MAX_PART = 8192;  // partitions per window: 2^(c-1) buckets = partitions x (256 .. 1024 bins)
-constexpr uint32_t MSM_MAX_WINDOW_BITS = 24;  // widest window of zkp_g1_bases_precompute (bounded by the sort geometry above)
 
 // base[0..nbins] = exclusive prefix of cnt[0..nbins) by ONE wave: lanes own ceil(nbins / 64) consecutive bins each and
 // a shuffle scan joins them.  Called by the first wave of the workgroup between two barriers.
@@ -197,7 +173,6 @@ __global__ __launch_bounds__(1024) void msm_partprefix_kernel(uint32_t* __restri
     }
 }
 
-constexpr uint32_t PYR_BAR_STRIDE = 32;  // words between the barrier counters of two windows (msm_pyramid_tail): a 128-byte line each
 // One workgroup per window: pstart[w][hi] (nhi + 1 entries) = exclusive prefix of the partition sizes.
 __global__ __launch_bounds__(64) void msm_partstart_kernel(const uint32_t* __restrict__ tot, SortGeom sg,
                                                            uint32_t* __restrict__ pstart, uint32_t* __restrict__ ghist,

@@ -1,0 +1,362 @@
+// msm_host.inc -- the MSM driver, included by api.hip inside its anonymous namespace.  msm_partial_batch: plan_msm (msm_plan.hpp)
+// sizes the pass, an MsmPass walks the scalar ranges (sort, accumulate) and reduces the buckets, msm_host_tail finishes on the host.
+
+#ifdef ZKP_MSM_CHECK  // diagnosis builds: wait for every kernel of the walk and say which one was reached
+#define MSM_TRACE(stream, ridx, what) do { hipError_t e_ = hipStreamSynchronize(stream); fprintf(stderr, "ZKP_MSM_CHECK range %llu: %s done (%d)\n", (unsigned long long)(ridx), what, (int)e_); } while (0)
+#else
+#define MSM_TRACE(stream, ridx, what) do { } while (0)
+#endif
+
+// Host scalars fed range by range: the upload of range k+1 (copy stream) overlaps the kernels of range k (shared-bucket mode only:
+// later ranges add into the same buckets).  Used by the host-pointer entry zkp_msm_g1.
+struct MsmFeed {
+    const uint64_t* h_scalars;  // n x 4 limbs on the host
+    hipStream_t copy_stream;    // non-blocking
+    hipEvent_t ev;
+    MsmFeedRanges ranges;       // msm_feed_ranges
+};
+
+// What the accumulate of a range reads: one of plan.nbuf buffer sets, so that the sort of the next range can fill the other
+struct RangeBuffers {
+    uint32_t *sorted, *start, *perm;
+    uint4* desc;                         // W x desc_cap (16-byte aligned first), then
+    uint32_t *over, *over_b, *over_off;  // W x 2, W x over_cap, W x (over_cap + 1)
+};
+
+// One pass of the kernels over the plan's scalar ranges.  The workspaces are the slot's buffers (Ctx); grow() sizes them to the plan
+// and names the parts carved out of them.
+struct MsmPass {
+    const MsmPlan& p;
+    MsmGeom g;  // the plan's geometry, narrowed to each range in turn (left at the last one)
+    const zkp_bases* bases;
+    const Fr* const* scalars;
+    size_t count;
+    const MsmFeed* feed;
+    hipStream_t st, sst;  // accumulate + reduction; digits + sort (a second stream when ranges overlap)
+    Ctx& cx = ctx();
+    const size_t W = p.g.nwin, nhi = p.sg.nhi;
+    uint32_t *ptot, *pstart, *ghist, *gcur;  // counts = W x nchunk x nhi, then W x nhi, W x (nhi + 1), W x 256 size histogram, W x 256
+    uint4* result_out;                       // pinned: W x c result points, then
+    uint32_t* result_flags;                  // W flag words
+    RangeUpload up;                          // host feed: the uploader's job for the later ranges, joined when the pass ends
+
+    std::array<std::tuple<const char*, DevBuf*, size_t>, 14> buffers() {
+        const MsmSizes& b = p.bytes;
+        return {{{"digits", &cx.digits, b.digits}, {"sorted", &cx.sorted, b.sorted}, {"counts", &cx.counts, b.counts},
+                 {"entries", &cx.entries, b.entries}, {"start", &cx.start, b.start}, {"perm", &cx.perm, b.perm}, {"over", &cx.over, b.over},
+                 {"pieces", &cx.pieces, b.pieces}, {"buckets", &cx.buckets, b.buckets}, {"parts", &cx.parts, b.parts},
+                 {"pyr1", &cx.pyr1, b.pyr1}, {"odd0", &cx.odd0, b.odd0}, {"odd1", &cx.odd1, b.odd1}, {"result", &cx.result, b.result}}};
+    }
+    // The result points and flag words go straight to pinned host memory (5 KB over PCIe: a device-to-host copy would be one more
+    // blit launch per MSM); the device `result` buffer holds the barrier counters of the last launch.
+    int grow() {
+        for (const auto& [name, buf, bytes] : buffers()) ZCHK(buf->ensure(bytes));
+        if (cx.host_result_cap < p.bytes.host_result) {
+            if (cx.host_result) HIPCHK(hipHostFree(cx.host_result));
+            cx.host_result = nullptr;
+            cx.host_result_cap = 0;
+            HIPCHK(hipHostMalloc(&cx.host_result, p.bytes.host_result, hipHostMallocPortable | hipHostMallocMapped));  // written by this slot's device
+            cx.host_result_cap = p.bytes.host_result;
+        }
+        ptot = cx.counts.get() + W * g.nchunk * nhi;
+        pstart = ptot + W * nhi;
+        ghist = pstart + W * (nhi + 1);
+        gcur = ghist + W * 256;
+        result_out = static_cast<uint4*>(cx.host_result);
+        result_flags = reinterpret_cast<uint32_t*>(result_out + 16 * W * g.c);
+        return ZKP_OK;
+    }
+    RangeBuffers range_buffers(size_t par) const {
+        uint4* desc = reinterpret_cast<uint4*>(static_cast<char*>(cx.over.p) + par * p.over_bytes);
+        uint32_t* over = reinterpret_cast<uint32_t*>(desc + W * p.desc_cap);
+        return {cx.sorted.get() + par * W * p.g.n, cx.start.get() + par * W * (p.g.nb + 2), cx.perm.get() + par * W * p.g.nb, desc, over,
+                over + 2 * W, over + 2 * W + W * p.over_cap};
+    }
+#ifdef ZKP_MSM_CHECK  // diagnosis builds: where every workspace lives, to place a faulting address
+    void dump(size_t n) {
+        static bool once = false;
+        if (once) return;
+        once = true;
+        auto show = [](const char* name, const void* q, size_t bytes) {
+            fprintf(stderr, "ZKP_MSM_CHECK %-10s %p .. %p (%zu bytes)\n", name, q, static_cast<const char*>(q) + bytes, bytes);
+        };
+        show("bases", bases->d_xy, (size_t)bases->n * 128 * std::max(bases->pre_planes, 1u));
+        show("scalars", scalars[0], 32 * n);
+        for (const auto& [name, buf, bytes] : buffers()) show(name, buf->p, buf->cap);
+        show("host_res", cx.host_result, cx.host_result_cap);
+        fprintf(stderr, "ZKP_MSM_CHECK geometry: n %zu range %llu first %llu rest %llu entries %llu nb %u nchunk %u over_cap %u desc_cap %u run_limit %u piece %u\n",
+                n, (unsigned long long)p.range, (unsigned long long)p.lens[0], (unsigned long long)p.lens.back(), (unsigned long long)p.g.n,
+                p.g.nb, p.g.nchunk, p.over_cap, p.desc_cap, p.g.run_limit, p.g.piece);
+    }
+#endif
+
+    // Host feed, first range: uploaded by this thread; the later ones are handed to the slot's uploader thread first, which issues them
+    // as soon as the first copy is in the stream (see Uploader)
+    int feed_first_range() {
+        Fr* const dst = const_cast<Fr*>(scalars[0]);
+        if (p.lens.size() > 1) {
+            while (cx.copy_events.size() < p.lens.size() - 1) {
+                hipEvent_t e = nullptr;
+                HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                cx.copy_events.push_back(e);
+            }
+            up.submit(uploader(cx.slot), std::vector<uint64_t>(p.lens.begin() + 1, p.lens.end()), p.lens[0],
+                      [device = cx.device] { return hipSetDevice(device) == hipSuccess ? (int)ZKP_OK : (int)ZKP_E_DEVICE; },
+                      [dst, f = *feed, evs = cx.copy_events.data()](size_t k, uint64_t o, uint64_t l) {
+                          const bool ok = hipMemcpyAsync(dst + o, f.h_scalars + 4 * o, 32 * l, hipMemcpyHostToDevice, f.copy_stream) == hipSuccess &&
+                                          hipEventRecord(evs[k], f.copy_stream) == hipSuccess;
+                          return ok ? (int)ZKP_OK : (int)ZKP_E_DEVICE;
+                      });
+        }
+        hipError_t e1 = hipMemcpyAsync(dst, feed->h_scalars, 32 * p.lens[0], hipMemcpyHostToDevice, feed->copy_stream);
+        if (e1 == hipSuccess) e1 = hipEventRecord(feed->ev, feed->copy_stream);
+        up.release(e1 == hipSuccess);
+        HIPCHK(e1);
+        return ZKP_OK;
+    }
+
+    // The scalar ranges in order.  With overlap the digits + sort of range r+1 run on `sst` under the accumulate of range r on `st`.
+    int walk() {
+        if (p.overlap) {  // the sort stream starts after whatever the caller enqueued on st (the scalars)
+            if (!cx.sort_stream) {
+                HIPCHK(hipStreamCreateWithFlags(&cx.sort_stream, hipStreamNonBlocking));
+                for (hipEvent_t* e : {&cx.ev_sort[0], &cx.ev_sort[1], &cx.ev_acc[0], &cx.ev_acc[1], &cx.ev_begin})
+                    HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+            }
+            sst = cx.sort_stream;
+            HIPCHK(hipEventRecord(cx.ev_begin, st));
+            HIPCHK(hipStreamWaitEvent(sst, cx.ev_begin, 0));
+        }
+        for (size_t ridx = 0, off = 0; ridx < p.lens.size(); off += p.lens[ridx++]) {
+            const uint64_t len = p.lens[ridx];
+            const size_t par = p.overlap ? (ridx & 1) : 0;  // buffer set of this range
+            const RangeBuffers rb = range_buffers(par);
+            if (p.overlap && ridx >= 2) HIPCHK(hipStreamWaitEvent(sst, cx.ev_acc[par], 0));  // range r-2 is done with this buffer set
+            if (len != g.ns) {  // a range shorter than the longest (the last one, or the first of a host-fed walk): smaller geometry
+                g.ns = len;
+                g.n = (uint64_t)p.nwin1 * len;
+                g.chunk = (g.n + g.nchunk - 1) / g.nchunk;
+            }
+            g.resume = off ? 1u : 0u;
+            g.more = ridx + 1 < p.lens.size() ? 1u : 0u;
+            if (feed) {  // this range's scalars: host -> device on the copy stream, the kernels below wait for them
+                if (ridx == 0)
+                    ZCHK(feed_first_range());
+                else if (!up.wait_issued(ridx))  // (host only: the GPU is busy with the ranges before)
+                    return fail(ZKP_E_DEVICE, "upload of a scalar range failed");
+                HIPCHK(hipStreamWaitEvent(sst, ridx == 0 ? feed->ev : cx.copy_events[ridx - 1], 0));
+            }
+            launch_sort(rb, off, ridx);
+            if (p.overlap) {
+                HIPCHK(hipEventRecord(cx.ev_sort[par], sst));
+                HIPCHK(hipStreamWaitEvent(st, cx.ev_sort[par], 0));
+            }
+            launch_accumulate(rb, off, ridx);
+            if (p.overlap) HIPCHK(hipEventRecord(cx.ev_acc[par], st));
+        }
+        return ZKP_OK;
+    }
+
+    template <int TILE> void launch_partscatter() {
+        hipLaunchKernelGGL(msm_partscatter_kernel<TILE>, dim3(g.nchunk, g.nwin), dim3(1024), partscatter_lds_bytes(nhi, TILE), sst,
+                           cx.digits.get(), g, p.sg, cx.counts.get(), pstart, cx.entries.get());
+    }
+    // Digits and counting sort of the range at `off` (g.ns scalars)
+    void launch_sort(const RangeBuffers& rb, uint64_t off, size_t ridx) {
+        const SortGeom& sg = p.sg;
+        {
+            ProfScope ps("msm_digits", sst);
+            DigitSources ds;  // digits laid out [msm][slice][scalar]: a shared-mode sort window is one msm
+            for (size_t m = 0; m < count; m++) ds.scalars[m] = scalars[m] + off;
+            hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)((g.ns + MSM_THREADS - 1) / MSM_THREADS), (unsigned)count), dim3(MSM_THREADS), 0,
+                               sst, ds, bases->d_inf ? bases->d_inf + off : nullptr, g, p.nwin1, cx.digits.get());
+            MSM_TRACE(sst, ridx, "digits");
+        }
+        ProfScope ps("msm_sort", sst, true);
+        hipLaunchKernelGGL(msm_parthist_kernel, dim3(g.nchunk, g.nwin), dim3(1024), 0, sst, cx.digits.get(), g, sg, cx.counts.get());
+        MSM_TRACE(sst, ridx, "parthist");
+        hipLaunchKernelGGL(msm_partprefix_kernel, dim3((sg.nhi + 63) / 64, g.nwin), dim3(1024), 0, sst, cx.counts.get(), g, sg, ptot);
+        hipLaunchKernelGGL(msm_partstart_kernel, dim3(g.nwin), dim3(64), 0, sst, ptot, sg, pstart, ghist, cx.result.get());
+        MSM_TRACE(sst, ridx, "partprefix + partstart");
+        switch (partscatter_tile(sg.nhi)) {  // the largest tile whose staging fits the LDS next to 12 bytes per partition
+            case PS_TILE_SMALL: launch_partscatter<PS_TILE_SMALL>(); break;
+            case PS_TILE_MID: launch_partscatter<PS_TILE_MID>(); break;
+            default: launch_partscatter<PS_TILE_BIG>(); break;
+        }
+        MSM_TRACE(sst, ridx, "partscatter");
+        hipLaunchKernelGGL(msm_binsort_kernel, dim3(sg.nhi, g.nwin), dim3(1024), 0, sst, cx.entries.get(), g, sg, pstart, rb.start, rb.sorted, ghist);
+        MSM_TRACE(sst, ridx, "binsort");
+        hipLaunchKernelGGL(msm_rank_kernel, dim3((g.nb + 1023) / 1024, g.nwin), dim3(1024), 0, sst, rb.start, g, ghist, gcur, rb.perm);
+        MSM_TRACE(sst, ridx, "rank");
+        hipLaunchKernelGGL(msm_order_kernel, dim3(g.nwin), dim3(1024), 0, sst, rb.start, g, ghist, rb.perm, rb.over, rb.over_b, rb.over_off,
+                           rb.desc, p.over_cap, p.desc_cap);
+        MSM_TRACE(sst, ridx, "order");
+    }
+
+    // Accumulate the sorted range at `off` into the buckets, combine the pieces of oversized buckets, fold split runs
+    void launch_accumulate(const RangeBuffers& rb, uint64_t off, size_t ridx) {
+        ProfScope ps("msm_accumulate", st, true);
+        // up to 2^20 entries four lanes per bucket: one lane would be latency-bound by its longest run (tools/small_msm_bench.py)
+        const bool quad = !g.resume && !g.more && (uint64_t)g.n * g.nwin <= (1ull << 20);
+        const uint32_t per_block = quad ? ACC_THREADS / 4 : ACC_THREADS;
+        const uint32_t bucket_blocks = (uint32_t)((((uint64_t)g.nb << g.split_log) + per_block - 1) / per_block);
+        const uint32_t extra_blocks = std::min<uint32_t>((p.desc_cap + per_block - 1) / per_block, 64);
+        const dim3 grid((bucket_blocks + extra_blocks) * g.nwin);
+        const uint4* xy = reinterpret_cast<const uint4*>(bases->d_xy) + off * 8;
+        uint4 *buckets = cx.buckets.get(), *pieces = cx.pieces.get(), *parts = cx.parts.get(), *carry = cx.pyr1.get();
+        if (quad)
+            hipLaunchKernelGGL(msm_accumulate_quad_kernel, grid, dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,
+                               p.desc_cap, bucket_blocks, extra_blocks, g, buckets, pieces, parts, clk_record(CLK_MSM_ACCUMULATE));
+        else
+            hipLaunchKernelGGL(msm_accumulate_kernel, grid, dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,
+                               p.desc_cap, bucket_blocks, extra_blocks, g, buckets, pieces, parts, carry, clk_record(CLK_MSM_ACCUMULATE));
+        MSM_TRACE(st, ridx, "accumulate");
+        hipLaunchKernelGGL(msm_combine_kernel, dim3(std::min<uint32_t>(p.over_cap, 64), g.nwin), dim3(64), 0, st, rb.over, rb.over_b,
+                           rb.over_off, p.over_cap, p.desc_cap, g, pieces, buckets, carry);
+        MSM_TRACE(st, ridx, "combine");
+        // buckets += parts, pairwise: split_log steps; a step with many adds runs one lane per add, a small one four (latency): msm.hpp
+        const uint64_t cap = (uint64_t)g.nwin * g.nb;
+        static const uint64_t lane_from = getenv("ZKP_FOLD_LANE_MIN") ? strtoull(getenv("ZKP_FOLD_LANE_MIN"), nullptr, 10) : FOLD_LANE_MIN_ADDS;
+        for (uint32_t t = 0; t < g.split_log; t++) {
+            const unsigned pairs = 1u << (g.split_log - 1 - t), per = cap * pairs >= lane_from ? MSM_THREADS : MSM_THREADS / 4;  // adds per workgroup
+            hipLaunchKernelGGL(per == MSM_THREADS ? msm_fold_parts_lane_kernel : msm_fold_parts_kernel, dim3((unsigned)((cap + per - 1) / per), pairs),
+                               dim3(MSM_THREADS), 0, st, buckets, parts, cap, t);
+        }
+    }
+
+    // The weighted bucket sums: pyramid levels as their own launches, then the last levels (or only the gathering) in one launch
+    // that writes the c result points and the flag word of every bucket set to pinned host memory
+    int reduce() {
+        // tuning aids (A/B runs): workgroup size and count of the last-levels launch, and the per-array pair count from which it takes over
+        static const uint32_t tail_threads = getenv("ZKP_PYR_TAIL_THREADS") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_THREADS")) : PYR_TAIL_THREADS;
+        static const uint32_t tail_blocks = getenv("ZKP_PYR_TAIL_BLOCKS") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_BLOCKS")) : PYR_TAIL_BLOCKS;
+        static const uint32_t tail_half = getenv("ZKP_PYR_TAIL_HALF") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_HALF")) : 64u;
+        if (tail_threads < 64 || tail_threads > 512 || (tail_threads & 63) || !tail_blocks || tail_blocks > 256 || !tail_half)
+            return fail(ZKP_E_ARG, "ZKP_PYR_TAIL_THREADS must be a multiple of 64 up to 512, ZKP_PYR_TAIL_BLOCKS 1..256, ZKP_PYR_TAIL_HALF >= 1");
+        for (size_t w = 0; w < W; w++) __atomic_store_n(result_flags + w, MSM_FLAG_PENDING, __ATOMIC_RELEASE);  // (the previous MSM's results were read before it returned)
+        uint4* pyr[2] = {cx.buckets.get(), cx.pyr1.get()};
+        uint4* odd[2] = {cx.odd0.get(), cx.odd1.get()};
+        ProfScope ps("msm_bucket_reduce", st, true);
+        uint32_t level_tail = 0;  // first level whose per-array work is <= 64 pairs: the rest runs in one launch
+        while (level_tail + 1 < g.c && (g.nb >> (level_tail + 1)) > tail_half) level_tail++;
+        // ... unless even one workgroup per bucket set is more than the device keeps resident (many bucket sets, a partition with few
+        // CUs): the barrier of that launch would spin for its whole time-out, so every level runs as its own launch instead
+        const uint32_t max_waves = cx.tail_max_waves;
+        if ((uint64_t)g.nwin * (tail_threads / 64) > max_waves) level_tail = g.c - 1;
+        for (uint32_t l = 0; l < level_tail; l++) {
+            const PyrLevel L{l, g.nb >> (l + 1), g.nb, g.nwin};
+            // levels with few adds are latency-bound: four lanes per add there (threshold swept 2^14..2^20: 2^16 is the minimum)
+            const bool quad = (uint64_t)L.half * (l + 1) * g.nwin <= (1u << 16);
+            const uint32_t per = quad ? MSM_THREADS / 4 : MSM_THREADS;  // adds per workgroup
+            hipLaunchKernelGGL(quad ? msm_pyramid_quad_kernel : msm_pyramid_kernel, dim3((L.half + per - 1) / per, l + 1, g.nwin),
+                               dim3(MSM_THREADS), 0, st, pyr[l & 1], pyr[(l + 1) & 1], odd[l & 1], odd[(l + 1) & 1], L);
+        }
+        if (level_tail + 1 < g.c) {
+            uint32_t tb = tail_blocks;
+            while (tb > 1 && (uint64_t)tb * g.nwin * (tail_threads / 64) > max_waves) tb >>= 1;
+            // test hook (tests/test_gpu_parity.py): ask the barrier for one arrival more than there are workgroups, with a short
+            // time-out -- the path a workgroup that never became resident would take: MSM_TAIL_TIMEOUT flag, ZKP_E_DEVICE
+            const bool starve = getenv("ZKP_TEST_TAIL_STARVE") != nullptr;
+            hipLaunchKernelGGL(msm_pyramid_tail_kernel, dim3(tb, g.nwin), dim3(tail_threads), 0, st, pyr[0], pyr[1], odd[0], odd[1], level_tail,
+                               g.c, g.nb, cx.result.get(), result_out, result_flags, starve ? tb + 1 : tb, starve ? (1u << 12) : PYR_TAIL_SPIN_LIMIT);
+        } else {  // every level already ran as its own launch: only the gathering is left
+            const uint32_t fin = (g.c - 1) & 1;
+            hipLaunchKernelGGL(msm_collect_kernel, dim3(g.nwin), dim3(64), 0, st, pyr[fin], pyr[fin ^ 1], odd[fin], g.nb, g.c, result_out,
+                               result_flags);
+        }
+        return ZKP_OK;
+    }
+};
+
+// Up to 2^24 entries per bucket set the host polls the result flags: the stream wait costs 30-60 us of wake-up per MSM (profiles/r05_k).
+// A kernel that never writes its flag (a fault) is caught by the stream wait the poll falls back to after two seconds.
+int wait_msm_result(const MsmGeom& g, const uint32_t* flags, hipStream_t st) {
+    bool seen = false;
+    if (g.n <= (1ull << 24) && !getenv("ZKP_MSM_NO_POLL")) {
+        const auto t_poll0 = std::chrono::steady_clock::now();
+        for (uint64_t spins = 0;; __builtin_ia32_pause()) {
+            bool all = true;
+            for (size_t w = 0; w < g.nwin && all; w++) all = (__atomic_load_n(flags + w, __ATOMIC_ACQUIRE) & MSM_FLAG_PENDING) == 0;
+            if ((seen = all)) break;
+            if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t_poll0 > std::chrono::seconds(2)) break;
+        }
+    }
+    if (!seen) HIPCHK(hipStreamSynchronize(st));  // the kernels' writes to the pinned buffer are visible to the host from here on
+    for (size_t w = 0; w < g.nwin; w++)
+        if (flags[w] & MSM_TAIL_TIMEOUT)
+            return fail(ZKP_E_DEVICE, "bucket reduction: the workgroups of the last levels did not all become resident (device shared "
+                                      "with another job?); no result was produced");
+    return ZKP_OK;
+}
+
+// Serial tail on the host.  Per bucket set: V = S + sum_l 2^l U_l.  Per-window mode: total = sum_w 2^(c w) V_w, and every (w, l)
+// lands on its own bit position c w + l, so ONE Horner chain over the positions does it with c W doublings.  Shared mode: the
+// expanded bases already carry the 2^(c w) factors, total = V of the single bucket set.
+void msm_host_tail(const uint32_t* host_res, size_t count, uint32_t wins_per_msm, uint32_t c, HXyzz* out) {
+    const auto t_tail0 = std::chrono::steady_clock::now();
+    auto tail = [&](size_t m) {
+        const uint32_t* res = host_res + m * wins_per_msm * c * 64;  // 64 words / point
+        HXyzz total = HXyzz::infinity();
+        for (int pos = (int)(wins_per_msm * c) - 1; pos >= 0; pos--) {
+            total = total.dbl();
+            const int w = pos / (int)c, l = pos % (int)c;
+            const uint32_t* rw = res + (size_t)w * c * 64;
+            if (l <= (int)c - 2) total = total.add(xyzz_from_internal(rw + (size_t)(1 + l) * 64));
+            if (l == 0) total = total.add(xyzz_from_internal(rw));
+        }
+        out[m] = total;
+    };
+    if (count == 1)
+        tail(0);
+    else  // the tails of a batch are independent serial chains: spread over the resident host workers
+        host_pool().run(std::function<void(size_t)>(tail), count);
+    prof_host("msm_tail_host", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail0).count());
+}
+
+// out[m] = sum_i scalars[m][i] * bases[i] as extended-Jacobian points (host), for `count` scalar vectors of the same length over
+// the same bases.  The vectors are stacked as extra windows of ONE pass through the kernels, so that a batch of small MSMs (the
+// 3 + 1 + 3 + 2 commitments of a PLONK proof) fills the GPU and pays the latency-bound bucket reduction once.  With expanded bases
+// (zkp_g1_bases_precompute) all windows of a scalar share one bucket set.
+int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t count, size_t n, hipStream_t st, HXyzz* out,
+                      const MsmFeed* feed = nullptr) {
+    MsmPlan p;
+    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off}, count, n, feed ? &feed->ranges : nullptr, &p))
+        return fail(rc, p.error);
+    if (p.lens.empty()) {
+        for (size_t m = 0; m < count; m++) out[m] = HXyzz::infinity();
+        return ZKP_OK;
+    }
+    MsmPass pass{p, p.g, bases, d_scalars, count, feed, st, st};
+    ZCHK(pass.grow());
+#ifdef ZKP_MSM_CHECK
+    pass.dump(n);
+#endif
+    const int walk_rc = pass.walk(), up_rc = pass.up.join();
+    if (walk_rc != ZKP_OK || up_rc != ZKP_OK) {
+        // an early return out of the walk can leave digits / sort kernels queued on the second stream that were never joined back
+        // into st; the caller's WsOrder event covers st only, so drain them here before the workspaces can be handed to the next entry
+        if (p.overlap) (void)hipStreamSynchronize(pass.sst);
+        if (feed) (void)hipStreamSynchronize(feed->copy_stream);
+        return walk_rc != ZKP_OK ? walk_rc : fail(ZKP_E_DEVICE, "upload of a scalar range failed");
+    }
+    HIPCHK(hipGetLastError());
+    ZCHK(pass.reduce());
+    HIPCHK(hipGetLastError());
+#ifdef ZKP_MSM_CHECK
+    {
+        uint32_t chk[32];
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyFromSymbol(chk, HIP_SYMBOL(g_msm_check), sizeof(chk)));
+        for (int k = 0; k < 8; k++)
+            if (chk[4 * k]) fprintf(stderr, "ZKP_MSM_CHECK class %d: %u violations, first (%u, %u)\n", k, chk[4 * k], chk[4 * k + 1], chk[4 * k + 2]);
+    }
+#endif
+    if (count > 1 && !getenv("ZKP_POOL_NO_WARM")) host_pool().warm(std::chrono::microseconds(3000));  // the tails below run on the pool: wake it now
+    ZCHK(wait_msm_result(pass.g, pass.result_flags, st));
+    msm_host_tail(reinterpret_cast<const uint32_t*>(pass.result_out), count, p.g.shared ? 1u : p.nwin1, p.g.c, out);  // (the pool's threads are in no context)
+    return ZKP_OK;
+}
+
+int msm_partial(const zkp_bases* bases, const Fr* d_scalars, size_t n, hipStream_t st, HXyzz* out) {
+    return msm_partial_batch(bases, &d_scalars, 1, n, st, out);
+}

@@ -1,0 +1,194 @@
+// msm_plan.hpp -- the host-side plan of one MSM pass (msm_partial_batch, msm_host.inc): window choice, scalar ranges, the
+// geometry the kernels of msm.hpp receive and the byte size of every workspace.  Plain C++17 without HIP, so that
+// tests/host/msm_plan_table.cpp can check it with g++ alone; msm.hpp includes it for MsmGeom / SortGeom.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+#include "../../include/zkp_hip.h"
+
+namespace zkp {
+
+// Two modes.  Per-window buckets (default): every c-bit window of every MSM of a batch is its own "sort window" with
+// n = ns entries and 2^(c-1) buckets.  Shared buckets (bases expanded with zkp_g1_bases_precompute): the W windows of a
+// scalar address W pre-multiplied copies of the base (planes 2^(c s) P_i), so ALL of them fall into ONE bucket set:
+// the sort window has n = W * ns entries, entry e = s * ns + i selects plane s, point i.
+struct MsmGeom {
+    uint32_t c;        // window bits
+    uint32_t nwin;     // sort windows (bucket sets) in this pass
+    uint32_t nb;       // buckets per window = 2^(c-1)   (bucket ids 1..nb)
+    uint32_t nchunk;   // chunks per window in the counting sort
+    uint64_t n;        // entries per sort window
+    uint64_t chunk;    // entries per chunk
+    uint64_t ns;       // scalars per MSM
+    uint64_t plane_stride;  // points per plane of the expanded bases (shared mode)
+    uint32_t nslice;   // c-bit windows per scalar
+    uint32_t shared;   // 1: shared bucket set
+    uint32_t run_limit;  // buckets with more entries are cut into pieces (msm_order)
+    uint32_t piece;      // entries per piece
+    uint32_t resume;     // 1: the buckets already hold the sums of earlier passes over other scalar ranges (shared mode)
+    uint16_t off[36];    // bit offset of every slice of a scalar (off[nslice] >= 256); widths <= c
+    uint32_t interleave; // 1: msm_accumulate walks the bucket sets interleaved (see there)
+    uint32_t split_log;  // 2^split_log lanes (quads) share a bucket's run, one contiguous part each (small problems, see msm_accumulate)
+    uint32_t more;       // 1: another scalar range follows: the bucket sums go to the hand-over array (msm_accumulate_body), not to `buckets`
+};
+
+// Counting sort geometry (msm.hpp): bucket ids are 1..nb; (b - 1) = hi * 2^lo_bits + lo.
+struct SortGeom {
+    uint32_t lo_bits;  // 8 or 9 (at most c - 1): bins of the second pass
+    uint32_t nhi;      // partitions per window = nb >> lo_bits
+};
+
+constexpr int MSM_MAX_BATCH = 64;
+constexpr uint32_t SORT_MAX_PART = 8192;  // partitions per window: 2^(c-1) buckets = partitions x (256 .. 1024 bins)
+constexpr uint32_t MSM_MAX_WINDOW_BITS = 24;  // widest window of zkp_g1_bases_precompute (bounded by the sort geometry above)
+constexpr uint32_t PYR_BAR_STRIDE = 32;  // words between the barrier counters of two windows (msm_pyramid_tail): a 128-byte line each
+// bucket lanes / bucket quads below which a bucket's run is split: enough for TWO generations of workgroups, so that the dispatcher
+// evens out the longest runs (PLONK 2^16: 3.83 -> 3.75 ms per proof, round 5)
+constexpr uint64_t SPLIT_FILL_LANES = 6 * 1024 * 64, SPLIT_FILL_QUADS = 2 * 1024 * 64 / 4 * 2;
+constexpr uint64_t FOLD_LANE_MIN_ADDS = 1ull << 15;  // adds in one fold launch from which one lane per add is used (profiles/r05_m_fold_lane.md)
+constexpr uint32_t MSM_MAX_SPLIT_LOG = 2;  // eight parts measured no better than four (2^16 single 0.535 against 0.529 ms, batches worse)
+
+inline int msm_env_int(const char* name, int lo, int hi, int dflt) {  // a tuning knob in [lo, hi], read on every call
+    const int v = getenv(name) ? atoi(getenv(name)) : dflt;
+    return v >= lo && v <= hi ? v : dflt;
+}
+
+// Window width: only widths dividing 256 leave no sparse top window (others 4-9x slower, profiles/r01_window_sweep.txt); below 8 bits
+// a scalar has more than 32 windows (MsmGeom::off holds 36 offsets).
+inline unsigned pick_window_bits(size_t n) { return (unsigned)msm_env_int("ZKP_MSM_C", 8, 16, n >= 2048 ? 16 : 8); }
+
+// The shape of the bases an MSM runs over (zkp_bases): pre_c != 0 means pre_planes expanded planes, plane s = 2^pre_off[s] * P
+struct MsmBases { uint64_t n; uint32_t pre_c, pre_planes; const uint16_t* pre_off; };
+
+// Host-fed scalars (zkp_msm_g1, shared-bucket mode): ranges of at most 2^range_log scalars; first_len != 0: a short first range (its
+// upload is the exposed one), second_len != 0: then a second short one, then the rest
+struct MsmFeedRanges { uint64_t range_log = 0, first_len = 0, second_len = 0; };
+
+// The ranges a host feed of n scalars asks for.  The first range's upload is exposed and every range pays a pass over the buckets,
+// so the first is just long enough for its kernels to cover the next upload: 25 % + 75 % up to 2^21 terms, from there
+// 10 % + 30 % + 60 % (2^24: 36.0 -> 34.0 ms; profiles/r04_i, profiles/r05_o).
+inline MsmFeedRanges msm_feed_ranges(uint64_t n) {
+    MsmFeedRanges f;
+    uint64_t parts = 2;
+    unsigned first_pct = n >= (1u << 21) ? 10 : 25;
+    const int ranges = msm_env_int("ZKP_MSM_FEED_RANGES", 1, 64, 0);  // equal ranges, as rounds 2-3 (tuning aid)
+    if (ranges) { parts = (uint64_t)ranges; first_pct = 0; }
+    first_pct = (unsigned)msm_env_int("ZKP_MSM_FEED_FIRST_PCT", 0, 90, (int)first_pct);  // share of the first range (0 = equal ranges)
+    const unsigned second_pct = (unsigned)msm_env_int("ZKP_MSM_FEED_SECOND_PCT", 0, 80, n >= (1u << 21) ? 30 : 0);  // a second short range
+    if (first_pct) {
+        f.first_len = std::max<uint64_t>(1024, (n * first_pct / 100) & ~(uint64_t)1023);
+        if (second_pct) f.second_len = std::max<uint64_t>(1024, (n * second_pct / 100) & ~(uint64_t)1023);
+        parts = 1;  // the rest in one piece (or as many as the range limit asks for)
+    }
+    while ((parts << f.range_log) < n) f.range_log++;
+    return f;
+}
+
+// Byte sizes of the workspaces of one pass (Ctx's DevBufs of the same names; host_result is pinned)
+struct MsmSizes {
+    size_t digits, sorted, counts, entries, start, perm, over, pieces, buckets, parts, pyr1, odd0, odd1, result, host_result;
+};
+
+struct MsmPlan {
+    MsmGeom g;                  // geometry of the longest range (msm_partial_batch narrows it for shorter ones)
+    SortGeom sg;
+    std::vector<uint64_t> lens; // the scalar ranges in order; empty: nothing to compute (count == 0 or n == 0)
+    uint64_t range;             // the longest range: what the workspaces and the sort geometry are sized for
+    bool overlap;               // several ranges: digits + sort of range r+1 on a second stream under the accumulate of range r
+    uint32_t nwin1, over_cap, desc_cap;  // windows (slices) per scalar; oversized buckets and piece descriptors per window (msm_order)
+    size_t nbuf, over_bytes;    // buffer sets of sorted / start / perm / over (2 with overlap); bytes of one set of `over`
+    MsmSizes bytes;
+    const char* error;          // the message of a refusal (plan_msm's return value != ZKP_OK)
+};
+
+// Everything msm_partial_batch decides before it touches the device.  Reads the ZKP_MSM_* / ZKP_SORT_LO_BITS tuning knobs.
+inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeedRanges* feed, MsmPlan* p) {
+    auto refuse = [p](int code, const char* msg) { p->error = msg; return code; };
+    p->lens.clear();
+    if (n > bases.n) return refuse(ZKP_E_SIZE, "more scalars than bases (kzg/src/scheme.rs:86)");
+    if (count == 0 || n == 0) return ZKP_OK;
+    if (n >= (1ull << 31)) return refuse(ZKP_E_ARG, "n >= 2^31");
+    if (count > (size_t)MSM_MAX_BATCH) return refuse(ZKP_E_ARG, "batch of more than 64 MSMs");
+    // expanded bases: always the shared bucket set (even 2^10 terms: 0.35 vs 0.85 ms on the per-window path)
+    const bool shared = bases.pre_c != 0;
+    MsmGeom& g = p->g = MsmGeom{};
+    g.c = shared ? bases.pre_c : pick_window_bits(n);
+    const uint32_t nwin1 = shared ? bases.pre_planes : 256 / g.c + (256 % g.c ? 1 : 0);
+    p->nwin1 = g.nslice = nwin1;
+    static_assert(sizeof(MsmGeom::off) / sizeof(uint16_t) == 36, "MsmGeom::off");
+    if (nwin1 + 1 > 36) return refuse(ZKP_E_ARG, "more than 35 windows per scalar");
+    for (uint32_t s = 0; s <= nwin1; s++) g.off[s] = shared ? bases.pre_off[s] : (uint16_t)(s * g.c);
+    g.shared = shared ? 1u : 0u;
+    // Shared mode walks the scalars in ranges: random 128-byte reads over more than ~26 GB of planes fall off a translation cliff
+    // (profiles/r01_f_shared_buckets.md, profiles/r02_j_sort_under_accumulate.md).  Later ranges add into the same buckets.
+    std::vector<uint64_t>& lens = p->lens;
+    if (shared) {
+        const uint64_t max_range = bases.pre_planes <= 12 ? 1ull << 24 : 1ull << 23;
+        uint64_t cap = feed ? std::min<uint64_t>(max_range, 1ull << feed->range_log) : max_range;
+        if (const int v = msm_env_int("ZKP_MSM_RANGE_LOG", 10, 30, 0)) cap = 1ull << v;
+        uint64_t want_first = feed ? feed->first_len : 0;
+        if (!feed && count == 1) {  // tuning aid (resident scalars): a short first range whose sort is the exposed one
+            const int v = msm_env_int("ZKP_MSM_FIRST_PCT", 1, 90, 0);
+            if (v) want_first = std::max<uint64_t>(1024, ((uint64_t)n * v / 100) & ~(uint64_t)1023);
+        }
+        uint64_t done = 0;  // short ranges first (they obey the range limit like the others), then the rest in equal ranges of at most `cap`
+        for (uint64_t want : {want_first, feed && want_first ? feed->second_len : (uint64_t)0})
+            if (want && done + want < n) {
+                lens.push_back(std::min<uint64_t>(want, cap));
+                done += lens.back();
+            }
+        const uint64_t rest = n - done, rpass = (rest + cap - 1) / cap, rr = (rest + rpass - 1) / rpass;
+        for (; done < n; done += lens.back()) lens.push_back(std::min<uint64_t>(rr, n - done));
+    } else {
+        lens.push_back(n);
+    }
+    const uint64_t range = p->range = *std::max_element(lens.begin(), lens.end());
+    g.ns = range;
+    g.plane_stride = bases.n;
+    g.nwin = shared ? (uint32_t)count : nwin1 * (uint32_t)count;  // sort windows = bucket sets
+    g.n = shared ? (uint64_t)nwin1 * range : n;                   // entries per sort window
+    if (g.n >= (1ull << 31)) return refuse(ZKP_E_ARG, "windows x scalars >= 2^31 with expanded bases");
+    g.nb = 1u << (g.c - 1);
+    g.interleave = (g.nwin > 1 && g.n <= (1ull << 22)) ? 1u : 0u;  // measured: +5 % at 2^22, 0 at 2^23, -5 % at 2^24
+    const uint64_t entries = g.n;
+    g.nchunk = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(1, (512 + g.nwin - 1) / g.nwin), (entries + 4095) / 4096);
+    if (const int v = msm_env_int("ZKP_MSM_NCHUNK", 1, 4096, 0)) g.nchunk = (uint32_t)std::min<uint64_t>((uint64_t)v, entries);
+    g.chunk = (entries + g.nchunk - 1) / g.nchunk;
+    // a bucket is oversized above 4x the average run; its pieces are no longer than an average run (they execute next to
+    // the ordinary lanes, so a longer piece would become the critical path)
+    g.run_limit = (uint32_t)std::max<uint64_t>(128, 4 * (entries / g.nb));
+    g.piece = (uint32_t)std::max<uint64_t>(32, entries / g.nb);
+    SortGeom& sg = p->sg;
+    // 2^19 buckets: 1024 partitions x 512 bins; 21..24-bit windows: 1024 bins per partition (measured, round 2)
+    sg.lo_bits = std::min<uint32_t>(g.c >= 21 ? 10 : g.c >= 20 ? 9 : 8, g.c - 1);
+    if (const int lo = msm_env_int("ZKP_SORT_LO_BITS", 6, 10, 0); lo && (uint32_t)lo < g.c) sg.lo_bits = (uint32_t)lo;  // tuning aid
+    sg.nhi = g.nb >> sg.lo_bits;
+    if (sg.nhi > SORT_MAX_PART) return refuse(ZKP_E_ARG, "window width above 24 bits is not supported by the sort");
+    const size_t W = g.nwin, nb = g.nb, c = g.c;
+    // Several scalar ranges: the (memory-bound) sort of range r+1 runs under the (issue-bound) accumulate of range r, on its own buffers
+    p->overlap = shared && range < n && !getenv("ZKP_MSM_NO_OVERLAP");
+    const size_t nbuf = p->nbuf = p->overlap ? 2 : 1;
+    // oversized-bucket bookkeeping (msm_order): at most n / LIMIT oversized buckets and n / PIECE + that many pieces
+    p->over_cap = (uint32_t)std::min<uint64_t>(entries / 128 + 1, (uint64_t)nb);  // also bounds the saturated bin
+    p->desc_cap = (uint32_t)(entries / g.piece + entries / g.run_limit + 2);
+    p->over_bytes = ((4 * W * (2 + (size_t)p->over_cap + p->over_cap + 1) + 16 * W * (size_t)p->desc_cap) + 255) & ~(size_t)255;
+    // Few buckets for the machine (a small MSM over narrow windows, single pass): 2 or 4 lanes / quads share a bucket's run
+    // (msm.hpp, split_run) so that narrow windows -- a short bucket reduction -- still fill the SIMDs.
+    const uint64_t units = (uint64_t)nb * W;  // lane or quad kernel: the choice made at the accumulate launch
+    const uint64_t want_units = (uint64_t)g.n * g.nwin <= (1ull << 20) ? SPLIT_FILL_QUADS : SPLIT_FILL_LANES;
+    if (range >= n) {
+        while (g.split_log < MSM_MAX_SPLIT_LOG && (units << g.split_log) < want_units) g.split_log++;
+        g.split_log = (uint32_t)msm_env_int("ZKP_MSM_SPLIT_LOG", 0, (int)MSM_MAX_SPLIT_LOG, (int)g.split_log);  // tuning aid
+    }
+    p->bytes = MsmSizes{4 * W * entries, nbuf * 4 * W * entries, 4 * W * ((size_t)g.nchunk * sg.nhi + 2 * sg.nhi + 1 + 512),
+                        8 * W * entries, nbuf * 4 * W * (nb + 2), nbuf * 4 * W * nb, nbuf * p->over_bytes,
+                        256 * W * (size_t)p->desc_cap, 256 * W * nb, 256 * W * nb * ((1u << g.split_log) - 1),
+                        256 * W * nb, 256 * W * nb, 256 * W * nb, 4 * PYR_BAR_STRIDE * W, 256 * W * c + 4 * W};
+    return ZKP_OK;
+}
+
+}  // namespace zkp
