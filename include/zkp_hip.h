@@ -397,6 +397,98 @@ int zkp_plonk_verify(zkp_plonk_prover *p, const uint64_t g2s_xy[24], const zkp_p
  * 7 tx_compact 8 t (before round 5). */
 int zkp_plonk_get_poly(zkp_plonk_prover *p, int which, uint64_t *out, size_t cap_elems, size_t *len);
 
+/* ---- Nova folding (NIFS) over a sparse R1CS: nova/src/nifs/mod.rs, nifs_prover.rs, nifs_verifier.rs, r1cs/mod.rs.
+ *      R1CS (r1cs/mod.rs:9-16): A, B, C with `rows` rows over z = (W || x || u), |W| = num_vars, |x| = num_io, so columns
+ *      0..num_vars+num_io.  The reference holds dense ragged rows (utils.rs:14-22: an entry beyond a row's length is zero); here each
+ *      matrix is host CSR: row_ptr (rows + 1 entries, row_ptr[0] = 0, non-decreasing), cols (row_ptr[rows] column indices) and vals
+ *      (row_ptr[rows] Fr, Montgomery).  Duplicate (row, column) entries add up and explicit zeros are kept, as in the dense sum.
+ *      ZKP_E_ARG for a null pointer, rows == 0, num_vars == 0, a column >= num_vars + num_io + 1, a row_ptr that does not start at 0
+ *      or decreases, or an SRS sharded over several slots (the handle is single-slot, like the PLONK prover: it lives on the SRS's
+ *      device).  z is never materialised: column c reads W[c] (c < num_vars), x[c - num_vars], or u (the last column), so a
+ *      resident W is used in place.  E and T have `rows` entries, W has num_vars.  Rows are split at create time: rows with at most
+ *      64 entries in A, B and C together run one lane per row, longer ones one wave per row. ---- */
+typedef struct zkp_nova_r1cs zkp_nova_r1cs;
+typedef struct {
+    const uint64_t *row_ptr; /* rows + 1 */
+    const uint32_t *cols;    /* row_ptr[rows] */
+    const uint64_t *vals;    /* row_ptr[rows] x 4 limbs */
+} zkp_csr;
+int zkp_nova_r1cs_create(const zkp_bases *srs, size_t rows, size_t num_vars, size_t num_io, const zkp_csr *a, const zkp_csr *b,
+                         const zkp_csr *c, zkp_nova_r1cs **out);
+void zkp_nova_r1cs_destroy(zkp_nova_r1cs *r);
+/* FInstance (r1cs/mod.rs:19-26): x points to num_io x 4 limbs owned by the caller (an output instance writes them). */
+typedef struct {
+    uint64_t com_e_xy[12];
+    uint8_t com_e_is_inf;
+    uint64_t u[4];
+    uint64_t com_w_xy[12];
+    uint8_t com_w_is_inf;
+    uint64_t *x;
+} zkp_nova_instance;
+/* NIFSProof (nifs/mod.rs:19-25) with each KzgOpening (kzg/src/opening.rs:12) as point + evaluation. */
+typedef struct {
+    uint64_t r[4];
+    uint64_t opening_point[4];
+    uint64_t open_e_xy[12];
+    uint8_t open_e_is_inf;
+    uint64_t eval_e[4];
+    uint64_t open_w_xy[12];
+    uint8_t open_w_is_inf;
+    uint64_t eval_w[4];
+} zkp_nova_proof;
+/* NIFS::compute_t, nifs/mod.rs:34-59: d_t = A z1 o B z2 + A z2 o B z1 - u1 C z2 - u2 C z1 in one pass over the matrices (the six
+ * products are never written).  d_w1 / d_w2: num_vars Fr on the device; x1 / x2: num_io Fr on the host; d_t: rows Fr. */
+int zkp_nova_cross_term_dev(zkp_nova_r1cs *r, const void *d_w1, const uint64_t *x1, const uint64_t u1[4], const void *d_w2,
+                            const uint64_t *x2, const uint64_t u2[4], void *d_t, void *stream);
+/* NIFS::fold_witness, nifs/mod.rs:64-82: E = E1 + r T + r^2 E2, W = W1 + r W2, one pass.  d_e_out / d_w_out may be d_e1 / d_w1
+ * (the running instance of an IVC chain folded in place); they must not overlap the other inputs. */
+int zkp_nova_fold_witness_dev(zkp_nova_r1cs *r, const uint64_t rr[4], const void *d_e1, const void *d_w1, const void *d_e2,
+                              const void *d_w2, const void *d_t, void *d_e_out, void *d_w_out, void *stream);
+/* The equation of is_r1cs_satisfied, r1cs/mod.rs:94-127: *bad_rows = the number of rows i with (A z)_i (B z)_i != u (C z)_i + E_i
+ * (0 = satisfied).  The commitment half of that check is zkp_kzg_commit on W and E.  Synchronises `stream`. */
+int zkp_nova_relaxed_residual_dev(zkp_nova_r1cs *r, const void *d_w, const uint64_t *x, const uint64_t u[4], const void *d_e,
+                                  void *stream, uint64_t *bad_rows);
+
+/* ---- Transcript<Sha256>, nova/src/transcript.rs:69-114 (host).  feed = the PLONK ChallengeGenerator feed (96 bytes of
+ *      serialize_uncompressed(G1)); feed_scalar hashes prev || serialize_uncompressed(Fr): the canonical integer as 32 little-endian
+ *      bytes (ark-serialize 0.4 for a 255-bit field, restated and PARITY-UNPINNED: no reference fixture fixes those bytes);
+ *      challenges draws n Fr (memory form) through StdRng::seed_from_u64 + Fr::rand.  Drawing twice without feeding, or before
+ *      any feed, is ZKP_E_ARG (the reference panics, transcript.rs:91-93). ---- */
+typedef struct zkp_nova_transcript zkp_nova_transcript;
+int zkp_nova_transcript_create(zkp_nova_transcript **out);
+void zkp_nova_transcript_destroy(zkp_nova_transcript *t);
+int zkp_nova_transcript_feed(zkp_nova_transcript *t, const uint64_t xy[12], uint8_t is_inf);
+int zkp_nova_transcript_feed_scalar(zkp_nova_transcript *t, const uint64_t s[4]);
+int zkp_nova_transcript_challenges(zkp_nova_transcript *t, size_t n, uint64_t *out);
+
+/* ---- NIFS::prover, nifs_prover.rs:11-47: T on the device (zkp_nova_cross_term_dev), com_T = commit_vector(T) with the resident MSM
+ *      (trailing zeros trimmed; ZKP_E_SIZE when the SRS is empty or shorter, like zkp_kzg_commit), feed u1, u2, com_T and draw r,
+ *      fold the witness on the device into d_e_out / d_w_out (aliasing as zkp_nova_fold_witness_dev), and fold the instance on the
+ *      host (fold_instance, nifs/mod.rs:88-106): com_E = com_E1 + r com_T + r^2 com_E2, com_W = com_W1 + r com_W2, u = u1 + r u2,
+ *      x = x1 + r x2.  *out may be *fi1 (and out->x may be fi1->x).  Synchronises `stream` (the MSM result is read back). ---- */
+int zkp_nova_nifs_prover_dev(zkp_nova_r1cs *r, const void *d_e1, const void *d_w1, const void *d_e2, const void *d_w2,
+                             const zkp_nova_instance *fi1, const zkp_nova_instance *fi2, zkp_nova_transcript *t, void *d_e_out,
+                             void *d_w_out, void *stream, zkp_nova_instance *out, uint64_t com_t_xy[12], uint8_t *com_t_is_inf,
+                             uint64_t r_out[4]);
+/* Host-pointer form: uploads E1, W1, E2, W2, calls the form above and reads E, W back (e_out / w_out may be e1 / w1). */
+int zkp_nova_nifs_prover(zkp_nova_r1cs *r, const uint64_t *e1, const uint64_t *w1, const uint64_t *e2, const uint64_t *w2,
+                         const zkp_nova_instance *fi1, const zkp_nova_instance *fi2, zkp_nova_transcript *t, uint64_t *e_out,
+                         uint64_t *w_out, zkp_nova_instance *out, uint64_t com_t_xy[12], uint8_t *com_t_is_inf, uint64_t r_out[4]);
+/* NIFS::prove, nifs_prover.rs:49-70: feed com_E, com_W of fi, draw the opening point, and open E and W there ON THE DEVICE
+ * (evaluation and quotient by X - z with the PLONK scan and evaluation kernels, then the MSM): the same values zkp_kzg_open returns
+ * for those vectors.  An E that is all zeros opens like zkp_kzg_open opens it: evaluation 0 and the identity (the reference
+ * panics there, kzg/src/scheme.rs:136-137).  Synchronises `stream`. */
+int zkp_nova_nifs_prove_dev(zkp_nova_r1cs *r, const uint64_t rr[4], const void *d_e, const void *d_w, const zkp_nova_instance *fi,
+                            zkp_nova_transcript *t, void *stream, zkp_nova_proof *out);
+int zkp_nova_nifs_prove(zkp_nova_r1cs *r, const uint64_t rr[4], const uint64_t *e, const uint64_t *w, const zkp_nova_instance *fi,
+                        zkp_nova_transcript *t, zkp_nova_proof *out);
+/* NIFS::verify, nifs_verifier.rs:22-91 (host): re-derives r from u1, u2, com_T, then the opening point from fi3's com_E, com_W, then
+ * runs zkp_kzg_verify for W and for E.  *accepted = 1 accepted, -1 "Error in computing random r", -2 "Error in computing random
+ * opening point", 0 "Folding wrong at W", -3 "Folding wrong at E" (checked in that order, as the reference). */
+int zkp_nova_nifs_verify(const uint64_t g2s_xy[24], const zkp_nova_proof *proof, const zkp_nova_instance *fi1,
+                         const zkp_nova_instance *fi2, const zkp_nova_instance *fi3, const uint64_t com_t_xy[12], uint8_t com_t_is_inf,
+                         zkp_nova_transcript *t, int *accepted);
+
 #ifdef __cplusplus
 }
 #endif

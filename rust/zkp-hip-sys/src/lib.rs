@@ -16,6 +16,8 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_bases { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_plonk_prover { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_plonk_transcript { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_nova_r1cs { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
 
 /// struct Proof of plonk/src/prover.rs:23-41 in ABI form
 #[repr(C)]
@@ -49,6 +51,38 @@ pub struct zkp_ntt_shard_geometry {
     pub cw: usize,
     pub slab: usize,
 }
+/// one R1CS matrix as host CSR (zkp_nova_r1cs_create)
+#[repr(C)]
+pub struct zkp_csr {
+    pub row_ptr: *const u64,
+    pub cols: *const u32,
+    pub vals: *const u64,
+}
+
+/// FInstance of nova/src/r1cs/mod.rs:19-26 in ABI form; x = num_io x 4 limbs owned by the caller
+#[repr(C)]
+pub struct zkp_nova_instance {
+    pub com_e_xy: [u64; 12],
+    pub com_e_is_inf: u8,
+    pub u: [u64; 4],
+    pub com_w_xy: [u64; 12],
+    pub com_w_is_inf: u8,
+    pub x: *mut u64,
+}
+
+/// NIFSProof of nova/src/nifs/mod.rs:19-25 in ABI form
+#[repr(C)]
+pub struct zkp_nova_proof {
+    pub r: [u64; 4],
+    pub opening_point: [u64; 4],
+    pub open_e_xy: [u64; 12],
+    pub open_e_is_inf: u8,
+    pub eval_e: [u64; 4],
+    pub open_w_xy: [u64; 12],
+    pub open_w_is_inf: u8,
+    pub eval_w: [u64; 4],
+}
+
 pub const ZKP_NTT_NATURAL: i32 = 0;
 pub const ZKP_NTT_K1SLAB: i32 = 1;
 pub const ZKP_NTT_COLUMNS: i32 = 2;
@@ -128,6 +162,21 @@ extern "C" {
     pub fn zkp_kzg_aggregate_commitments(commits_xy: *const u64, commits_is_inf: *const u8, n: usize, challenge: *const u64, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_plonk_verify(p: *mut zkp_plonk_prover, g2s_xy: *const u64, proof: *const zkp_plonk_proof, accepted: *mut i32) -> i32;
     pub fn zkp_plonk_get_poly(p: *mut zkp_plonk_prover, which: i32, out: *mut u64, cap_elems: usize, len: *mut usize) -> i32;
+    pub fn zkp_nova_r1cs_create(srs: *const zkp_bases, rows: usize, num_vars: usize, num_io: usize, a: *const zkp_csr, b: *const zkp_csr, c: *const zkp_csr, out: *mut *mut zkp_nova_r1cs) -> i32;
+    pub fn zkp_nova_r1cs_destroy(r: *mut zkp_nova_r1cs);
+    pub fn zkp_nova_cross_term_dev(r: *mut zkp_nova_r1cs, d_w1: *const c_void, x1: *const u64, u1: *const u64, d_w2: *const c_void, x2: *const u64, u2: *const u64, d_t: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_nova_fold_witness_dev(r: *mut zkp_nova_r1cs, rr: *const u64, d_e1: *const c_void, d_w1: *const c_void, d_e2: *const c_void, d_w2: *const c_void, d_t: *const c_void, d_e_out: *mut c_void, d_w_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_nova_relaxed_residual_dev(r: *mut zkp_nova_r1cs, d_w: *const c_void, x: *const u64, u: *const u64, d_e: *const c_void, stream: *mut c_void, bad_rows: *mut u64) -> i32;
+    pub fn zkp_nova_transcript_create(out: *mut *mut zkp_nova_transcript) -> i32;
+    pub fn zkp_nova_transcript_destroy(t: *mut zkp_nova_transcript);
+    pub fn zkp_nova_transcript_feed(t: *mut zkp_nova_transcript, xy: *const u64, is_inf: u8) -> i32;
+    pub fn zkp_nova_transcript_feed_scalar(t: *mut zkp_nova_transcript, s: *const u64) -> i32;
+    pub fn zkp_nova_transcript_challenges(t: *mut zkp_nova_transcript, n: usize, out: *mut u64) -> i32;
+    pub fn zkp_nova_nifs_prover_dev(r: *mut zkp_nova_r1cs, d_e1: *const c_void, d_w1: *const c_void, d_e2: *const c_void, d_w2: *const c_void, fi1: *const zkp_nova_instance, fi2: *const zkp_nova_instance, t: *mut zkp_nova_transcript, d_e_out: *mut c_void, d_w_out: *mut c_void, stream: *mut c_void, out: *mut zkp_nova_instance, com_t_xy: *mut u64, com_t_is_inf: *mut u8, r_out: *mut u64) -> i32;
+    pub fn zkp_nova_nifs_prover(r: *mut zkp_nova_r1cs, e1: *const u64, w1: *const u64, e2: *const u64, w2: *const u64, fi1: *const zkp_nova_instance, fi2: *const zkp_nova_instance, t: *mut zkp_nova_transcript, e_out: *mut u64, w_out: *mut u64, out: *mut zkp_nova_instance, com_t_xy: *mut u64, com_t_is_inf: *mut u8, r_out: *mut u64) -> i32;
+    pub fn zkp_nova_nifs_prove_dev(r: *mut zkp_nova_r1cs, rr: *const u64, d_e: *const c_void, d_w: *const c_void, fi: *const zkp_nova_instance, t: *mut zkp_nova_transcript, stream: *mut c_void, out: *mut zkp_nova_proof) -> i32;
+    pub fn zkp_nova_nifs_prove(r: *mut zkp_nova_r1cs, rr: *const u64, e: *const u64, w: *const u64, fi: *const zkp_nova_instance, t: *mut zkp_nova_transcript, out: *mut zkp_nova_proof) -> i32;
+    pub fn zkp_nova_nifs_verify(g2s_xy: *const u64, proof: *const zkp_nova_proof, fi1: *const zkp_nova_instance, fi2: *const zkp_nova_instance, fi3: *const zkp_nova_instance, com_t_xy: *const u64, com_t_is_inf: u8, t: *mut zkp_nova_transcript, accepted: *mut i32) -> i32;
 }
 
 /// The thread-local message of the last failed call.

@@ -8,7 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRIM = {"uint64_t": "u64", "uint8_t": "u8", "int": "i32", "unsigned": "u32", "size_t": "usize", "void": "c_void", "char": "c_char",
         "double": "f64", "zkp_bases": "zkp_bases", "zkp_plonk_prover": "zkp_plonk_prover",
         "zkp_plonk_transcript": "zkp_plonk_transcript", "zkp_plonk_proof": "zkp_plonk_proof", "zkp_ntt_layout": "zkp_ntt_layout",
-        "zkp_ntt_shard_geometry": "zkp_ntt_shard_geometry"}
+        "zkp_ntt_shard_geometry": "zkp_ntt_shard_geometry", "zkp_nova_r1cs": "zkp_nova_r1cs", "zkp_nova_transcript": "zkp_nova_transcript",
+        "zkp_csr": "zkp_csr", "zkp_nova_instance": "zkp_nova_instance", "zkp_nova_proof": "zkp_nova_proof"}
 RET = {"int": "i32", "void": "()", "size_t": "usize", "const char *": "*const c_char", "const char*": "*const c_char"}
 
 
@@ -56,6 +57,8 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_bases { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_plonk_prover { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_plonk_transcript { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_nova_r1cs { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
 
 /// struct Proof of plonk/src/prover.rs:23-41 in ABI form
 #[repr(C)]
@@ -89,6 +92,38 @@ pub struct zkp_ntt_shard_geometry {
     pub cw: usize,
     pub slab: usize,
 }
+/// one R1CS matrix as host CSR (zkp_nova_r1cs_create)
+#[repr(C)]
+pub struct zkp_csr {
+    pub row_ptr: *const u64,
+    pub cols: *const u32,
+    pub vals: *const u64,
+}
+
+/// FInstance of nova/src/r1cs/mod.rs:19-26 in ABI form; x = num_io x 4 limbs owned by the caller
+#[repr(C)]
+pub struct zkp_nova_instance {
+    pub com_e_xy: [u64; 12],
+    pub com_e_is_inf: u8,
+    pub u: [u64; 4],
+    pub com_w_xy: [u64; 12],
+    pub com_w_is_inf: u8,
+    pub x: *mut u64,
+}
+
+/// NIFSProof of nova/src/nifs/mod.rs:19-25 in ABI form
+#[repr(C)]
+pub struct zkp_nova_proof {
+    pub r: [u64; 4],
+    pub opening_point: [u64; 4],
+    pub open_e_xy: [u64; 12],
+    pub open_e_is_inf: u8,
+    pub eval_e: [u64; 4],
+    pub open_w_xy: [u64; 12],
+    pub open_w_is_inf: u8,
+    pub eval_w: [u64; 4],
+}
+
 pub const ZKP_NTT_NATURAL: i32 = 0;
 pub const ZKP_NTT_K1SLAB: i32 = 1;
 pub const ZKP_NTT_COLUMNS: i32 = 2;

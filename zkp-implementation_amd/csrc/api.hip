@@ -13,6 +13,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -26,6 +27,7 @@
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "plonk.hpp"
+#include "nova.hpp"
 #include "fri.hpp"
 #include "transcript_host.hpp"
 #include "pairing_host.hpp"
@@ -2034,3 +2036,4 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "plonk_host.inc"
 #include "fri_host.inc"
 #include "verify_host.inc"
+#include "nova_host.inc"

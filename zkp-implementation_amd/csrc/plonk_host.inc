@@ -730,6 +730,29 @@ int zkp_plonk_get_poly(zkp_plonk_prover* p, int which, uint64_t* out, size_t cap
 
 }  // extern "C"
 
+// Elements of scratch open_eval_div_dev needs for `len` coefficients: q (len) | scale + scan scratch (2 len) | scan totals | evaluation
+// partials
+uint64_t open_scratch_elems(uint64_t len) {
+    return 3 * len + scan_scratch_elems(len) + len / (EVAL_CHUNK * PK_THREADS) + 2;
+}
+
+// y = p(z) and q = (p - y) / (X - z) for `len` >= 1 coefficients resident at d_c: q (len - 1 coefficients) is left at the start of
+// `scratch` (open_scratch_elems(len) elements that do not overlap d_c); *q_out points to it.  Enqueued on `st`; y is read back.
+int open_eval_div_dev(Fr* scratch, const Fr* d_c, uint64_t len, const HFr& z, hipStream_t st, HFr* y, Fr** q_out) {
+    zkp_plonk_prover w;  // only its scratch pointers are used by the helpers
+    const uint64_t n_tot = scan_scratch_elems(len);
+    w.partial_cap = (unsigned)(len / (EVAL_CHUNK * PK_THREADS) + 2);
+    Fr* d_q = scratch;
+    w.ev = d_q + len;
+    w.scan = w.ev + 2 * len;
+    w.scan_cap = n_tot;
+    w.partial = w.scan + n_tot;
+    ZCHK(eval_dev(&w, d_c, len, z, st, y));
+    if (len > 1) ZCHK(div_linear_dev(&w, d_c, len, z, d_q, st));
+    *q_out = d_q;
+    return ZKP_OK;
+}
+
 // KzgScheme::open (kzg/src/scheme.rs:108-120) with the polynomial work on the device: y = p(z) by chunked Horner,
 // q = (p - y) / (X - z) by weighted suffix sums, W = MSM(q).
 int kzg_open_device(const zkp_bases* srs, const uint64_t* coeffs, size_t len, const uint64_t z_limbs[4], uint64_t out_xy[12],
@@ -751,24 +774,15 @@ int kzg_open_device(const zkp_bases* srs, const uint64_t* coeffs, size_t len, co
         CTX_ENTER(sharded ? srs->shards[0]->slot : srs->slot);
         hipStream_t st = nullptr;
         WsOrder ord(st);
-        // scratch carved from the staging buffer: coeffs | q | scale+scan scratch (2 len) | scan totals | eval partials
-        zkp_plonk_prover w;  // only its scratch pointers are used by the helpers
-        const size_t n_tot = scan_scratch_elems(len);
-        w.partial_cap = (unsigned)(len / (EVAL_CHUNK * PK_THREADS) + 2);
-        ZCHK(ctx().tmp.ensure(32 * (4 * len + n_tot + w.partial_cap) + 64));
+        // scratch carved from the staging buffer: coeffs | open_eval_div_dev's scratch
+        ZCHK(ctx().tmp.ensure(32 * (len + open_scratch_elems(len)) + 64));
         Fr* d_c = reinterpret_cast<Fr*>(ctx().tmp.p);
-        Fr* d_q = d_c + len;
-        w.ev = d_q + len;
-        w.scan = w.ev + 2 * len;
-        w.scan_cap = n_tot;
-        w.partial = w.scan + n_tot;
         HIPCHK(hipMemcpyAsync(d_c, coeffs, 32 * len, hipMemcpyHostToDevice, st));
-        const HFr z = HFr::load(z_limbs);
         HFr y;
-        ZCHK(eval_dev(&w, d_c, len, z, st, &y));
+        Fr* d_q = nullptr;
+        ZCHK(open_eval_div_dev(d_c + len, d_c, len, HFr::load(z_limbs), st, &y, &d_q));
         y.store(out_eval);
         if (len > 1) {
-            ZCHK(div_linear_dev(&w, d_c, len, z, d_q, st));
             if (sharded) {
                 h_q.resize(4 * (len - 1));
                 HIPCHK(hipMemcpyAsync(h_q.data(), d_q, 32 * (len - 1), hipMemcpyDeviceToHost, st));

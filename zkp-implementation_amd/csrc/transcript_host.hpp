@@ -239,9 +239,13 @@ public:
             bytes[48 + i] = infinity ? 0 : static_cast<uint8_t>(y[5 - i / 8] >> (56 - 8 * (i % 8)));
         }
         if (infinity) bytes[0] |= 1 << 6;
+        absorb(bytes, 96);
+    }
+    // data = SHA-256(prev || bytes): the step every feed of the reference's transcripts shares (also nova/src/transcript.rs:69-88)
+    void absorb(const uint8_t* bytes, size_t n) {
         Sha256 h;
         if (has_data_) h.update(data_.data(), 32);
-        h.update(bytes, 96);
+        h.update(bytes, n);
         data_ = h.finish();
         has_data_ = true;
         generated_ = false;

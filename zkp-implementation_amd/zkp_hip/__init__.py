@@ -106,6 +106,21 @@ _SIGS = {
     "zkp_plonk_get_poly": ([_VP, C.c_int, _VP, _SZ, C.POINTER(C.c_size_t)], C.c_int),
     "zkp_kzg_commit": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_kzg_open": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_nova_r1cs_create": ([_VP, _SZ, _SZ, _SZ, _VP, _VP, _VP, C.POINTER(_VP)], C.c_int),
+    "zkp_nova_r1cs_destroy": ([_VP], None),
+    "zkp_nova_cross_term_dev": ([_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_nova_fold_witness_dev": ([_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_nova_relaxed_residual_dev": ([_VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64)], C.c_int),
+    "zkp_nova_transcript_create": ([C.POINTER(_VP)], C.c_int),
+    "zkp_nova_transcript_destroy": ([_VP], None),
+    "zkp_nova_transcript_feed": ([_VP, _VP, C.c_uint8], C.c_int),
+    "zkp_nova_transcript_feed_scalar": ([_VP, _VP], C.c_int),
+    "zkp_nova_transcript_challenges": ([_VP, _SZ, _VP], C.c_int),
+    "zkp_nova_nifs_prover_dev": ([_VP] * 15, C.c_int),
+    "zkp_nova_nifs_prover": ([_VP] * 14, C.c_int),
+    "zkp_nova_nifs_prove_dev": ([_VP] * 8, C.c_int),
+    "zkp_nova_nifs_prove": ([_VP] * 7, C.c_int),
+    "zkp_nova_nifs_verify": ([_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint8, _VP, C.POINTER(C.c_int)], C.c_int),
 }
 
 
@@ -800,3 +815,8 @@ class PlonkProver:
         if ln.value:
             _chk(lib().zkp_plonk_get_poly(self._h, POLY_IDS[name], _ptr(out), ln.value, C.byref(ln)))
         return out
+
+
+# ----------------------------------------------------------------------------- Nova folding (nova/src), zkp_hip/nova.py
+from .nova import (FInstance, FWitness, NifsProof, NovaR1CS, NovaTranscript, csr_from_dense, is_r1cs_satisfied,  # noqa: E402,F401
+                   nifs_prove, nifs_prover, nifs_verify)
