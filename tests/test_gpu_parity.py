@@ -689,6 +689,22 @@ def test_precompute_reports_an_expansion_that_does_not_fit(zkp, orc, monkeypatch
     assert inf == einf and np.array_equal(out, exp)
 
 
+def test_allocation_failure_reports_the_bare_hip_error(zkp):
+    """A handle whose device buffers cannot be allocated (here 4 PiB of bases) is refused with ZKP_E_NOMEM and the bare HIP error
+    text the C ABI has always given for it (zkp_last_error, read by the Rust -sys callers), and no handle is handed out."""
+    import ctypes as C
+    import torch
+    t = torch.zeros(12, dtype=torch.int64, device="cuda")
+    h = C.c_void_p()
+    rc = zkp.lib().zkp_g1_bases_create_dev(C.c_void_p(t.data_ptr()), None, 1 << 45, None, C.byref(h))
+    assert rc == zkp.ZKP_E_NOMEM and not h.value
+    assert zkp.lib().zkp_last_error().decode() == "out of memory"
+    # the failed hipMalloc is also this thread's HIP last error, as it always was: read it off, so that the next torch launch check in
+    # this process does not report it
+    zkp.lib().hipGetLastError()
+    assert torch.ones(4, dtype=torch.int64, device="cuda").sum().item() == 4
+
+
 @pytest.mark.gpu
 def test_msm_2_24_expanded_two_ranges_trapdoor(zkp, orc):
     """2^24 + 5 terms over an SRS expanded at the AUTOMATIC width (precompute(0): 12 balanced slices of 21/22 bits over 2^21 buckets,

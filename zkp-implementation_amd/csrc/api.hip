@@ -69,6 +69,15 @@ int on_exception() noexcept {
             return fail(e_ == hipErrorOutOfMemory ? ZKP_E_NOMEM : ZKP_E_DEVICE,                             \
                         std::string(#expr) + ": " + hipGetErrorString(e_));                                 \
     } while (0)
+// A failed HIP call as HIPCHK reports it (what + the HIP error text; `what` empty where an entry reports the bare text)
+int hip_fail(hipError_t e, const std::string& what) {
+    return fail(e == hipErrorOutOfMemory ? ZKP_E_NOMEM : ZKP_E_DEVICE, what + hipGetErrorString(e));
+}
+#define HIPCHK_BARE(expr)                            \
+    do {                                             \
+        hipError_t e_ = (expr);                      \
+        if (e_ != hipSuccess) return hip_fail(e_, ""); \
+    } while (0)
 #define ZCHK(expr)             \
     do {                       \
         int r_ = (expr);       \
@@ -76,6 +85,7 @@ int on_exception() noexcept {
     } while (0)
 
 #include "host_threads.hpp"  // HostPool (host_pool()), Uploader (uploader(slot))
+#include "dev_res.hpp"       // DevBuf, TypedBuf, PinnedBuf, Stream, Event
 static_assert(ZKP_HOST_THREADS_E_DEVICE == ZKP_E_DEVICE && ZKP_HOST_THREADS_OK == ZKP_OK, "host_threads.hpp error codes");
 
 // ----------------------------------------------------------------------------------------------------
@@ -150,10 +160,10 @@ void device_workers_stop() { g_workers.stop(); }
 // optional per-phase timing: HIP events on the launch stream (zkp_profile_* in include/zkp_hip.h)
 // ----------------------------------------------------------------------------------------------------
 struct ProfRec {
-    const char* name;
-    hipEvent_t a, b;  // device phases
-    double host_ms;   // host phases (a == nullptr)
-    bool owns_a;      // false: `a` is the end event of the previous record (chained scope)
+    const char* name = nullptr;
+    hipEvent_t a = nullptr;  // device phases: start (own_a, or the previous record's end event for a chained scope) and end
+    Event own_a, b;
+    double host_ms = 0;      // host phases (a == nullptr)
 };
 std::atomic<int> g_prof_on{0};  // 0 off, 1 every phase, 2 the dominant kernel only (zkp_profile_enable)
 struct Ctx;
@@ -174,22 +184,20 @@ struct ProfScope {
         if (!on) return;
         if (level == 2) chain = false;  // the scope before it was not recorded
         rec.name = name;
-        rec.host_ms = 0;
-        rec.owns_a = true;
         std::vector<ProfRec>& recs = prof_records();
         if (chain && !recs.empty() && recs.back().b && prof_last_stream() == s) {
-            rec.a = recs.back().b;
-            rec.owns_a = false;
-            if (hipEventCreate(&rec.b) != hipSuccess) on = false;
+            rec.a = recs.back().b;  // borrowed: the records are released together (zkp_profile_reset, ~Ctx)
+            if (rec.b.make(hipEventDefault) != hipSuccess) on = false;
             return;
         }
-        if (hipEventCreate(&rec.a) != hipSuccess || hipEventCreate(&rec.b) != hipSuccess) { on = false; return; }
+        if (rec.own_a.make(hipEventDefault) != hipSuccess || rec.b.make(hipEventDefault) != hipSuccess) { on = false; return; }
+        rec.a = rec.own_a;
         (void)hipEventRecord(rec.a, st);
     }
     ~ProfScope() {
         if (!on) return;
         (void)hipEventRecord(rec.b, st);
-        prof_records().push_back(rec);
+        prof_records().push_back(std::move(rec));
         prof_last_stream() = st;
     }
 };
@@ -197,34 +205,9 @@ void prof_host(const char* name, double ms) {
     if (g_prof_on.load(std::memory_order_relaxed) != 1) return;
     ProfRec r;
     r.name = name;
-    r.a = nullptr;
-    r.b = nullptr;
-    r.owns_a = false;
     r.host_ms = ms;
-    prof_records().push_back(r);
+    prof_records().push_back(std::move(r));
 }
-
-struct DevBuf {  // grow-only device allocation
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return ZKP_OK;
-        if (p) HIPCHK(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        HIPCHK(hipMalloc(&p, bytes));
-        cap = bytes;
-        return ZKP_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-template <class T> struct TypedBuf : DevBuf {  // the same, holding T elements
-    T* get() const { return static_cast<T*>(p); }
-};
 
 // ----------------------------------------------------------------------------------------------------
 // host <-> device field views
@@ -263,17 +246,16 @@ struct NttPlan {
     int passes = 0;
     int r[4] = {0, 0, 0, 0};
     const typename NttOps<F>::W* tw[4] = {nullptr, nullptr, nullptr, nullptr};
-    typename NttOps<F>::W* inter_lo = nullptr;
-    typename NttOps<F>::W* inter_hi = nullptr;
+    TypedBuf<typename NttOps<F>::W> inter_lo, inter_hi;
     // inverse plans: inter_lo times 1/n.  Pass 0 multiplies every element by one inter-pass twiddle anyway, so reading it from
     // this table applies the 1/n of the inverse transform for free (no scaling product at the store of the last pass)
-    typename NttOps<F>::W* inter_lo_ninv = nullptr;
+    TypedBuf<typename NttOps<F>::W> inter_lo_ninv;
     uint32_t h = 0;
     // passes 1 .. P-2 work on sub-problems of size M_p = n >> (r_0 + .. + r_{p-1}); up to 2^17 their inter-pass twiddles
     // omega_{M_p}^e come from a direct table (one load, no product of a low and a high factor)
-    typename NttOps<F>::W* direct[4] = {nullptr, nullptr, nullptr, nullptr};
+    TypedBuf<typename NttOps<F>::W> direct[4];
     // pass 0's inter-pass twiddles as a matrix shaped like the data (NttOps::PASS0_MATRIX); [1] = times 1/n.  Built on first use.
-    F* tw_matrix[2] = {nullptr, nullptr};
+    TypedBuf<F> tw_matrix[2];
     typename HostField<F>::H n_inv;
 };
 
@@ -284,9 +266,7 @@ struct CosetCache {
     int inverse = 0;
     uint64_t key[4] = {0, 0, 0, 0};
     uint64_t ckey[4] = {0, 0, 0, 0};  // the constant factor c of the table c * g^e
-    typename NttOps<F>::W* lo = nullptr;
-    typename NttOps<F>::W* hi = nullptr;
-    size_t lo_cap = 0, hi_cap = 0;
+    TypedBuf<typename NttOps<F>::W> lo, hi;  // grow-only
     uint32_t h = 0;
 };
 
@@ -299,18 +279,23 @@ struct Ctx {
     int slot = 0;
     int device = -1;
     std::mutex mu;
-    hipStream_t stream = nullptr;  // non-blocking; the per-slot workers of the multi-device entries launch on it
+    // Members are released in reverse declaration order, after ~Ctx has drained the device: the streams come first so that they
+    // outlive every event and buffer that work on them used.
+    Stream stream;       // non-blocking; the per-slot workers of the multi-device entries launch on it
+    Stream copy_stream;  // zkp_msm_g1: upload of the next scalar range
+    Stream sort_stream;  // shared-bucket MSM in several scalar ranges: digits + sort of range r+1 under accumulate r
+    Stream xstream;      // ntt_sharded.inc: the peer copies
     // Workspaces and cached tables are shared by every call on this slot, whatever stream the caller passes.  The `*_dev`
     // entries return without synchronising, so a later call on ANOTHER stream must not touch them before the earlier work
     // is done: each entry records ws_event on its stream when it has enqueued everything, and an entry that arrives with a
     // different stream makes it wait for that event first (WsOrder).
-    hipEvent_t ws_event = nullptr;
+    Event ws_event;
     hipStream_t ws_stream = nullptr;
     bool ws_pending = false;
     std::vector<ProfRec> prof;
     hipStream_t prof_last = nullptr;
     // NTT
-    std::map<std::pair<int, int>, void*> radix_tw[2];  // [field] (log_r, inverse) -> table
+    std::map<std::pair<int, int>, DevBuf> radix_tw[2];  // [field] (log_r, inverse) -> table
     std::map<std::pair<unsigned, int>, NttPlan<Fr>> plans_fr;
     std::map<std::pair<unsigned, int>, NttPlan<Gl>> plans_gl;
     // a few (size, direction, coset) tables per field: a PLONK proof alternates forward and inverse transforms on the 4n
@@ -320,43 +305,44 @@ struct Ctx {
     CosetCache<Gl> coset_gl[COSET_WAYS];
     unsigned coset_victim[2] = {0, 0};
     DevBuf ntt_scratch;
-    std::map<std::pair<unsigned, int>, void*> axis0_tw[2];  // [field] (log_len, inverse) -> omega_len^e, e < len (run_ntt_axis0)
+    std::map<std::pair<unsigned, int>, DevBuf> axis0_tw[2];  // [field] (log_len, inverse) -> omega_len^e, e < len (run_ntt_axis0)
     // MSM
     DevBuf scalars, over;
     TypedBuf<uint32_t> digits, sorted, counts, start, perm, result;
     TypedBuf<uint2> entries;
     TypedBuf<uint4> pieces, buckets, parts, pyr1, odd0, odd1;
-    void* host_result = nullptr;  // pinned
-    size_t host_result_cap = 0;
-    void* fri_small = nullptr;    // pinned: the few dozen words zkp_fri_prove reads back after the folding phase
-    size_t fri_small_cap = 0;
+    PinnedBuf host_result;
+    PinnedBuf fri_small;          // the few dozen words zkp_fri_prove reads back after the folding phase
     DevBuf fb_table;              // fixed-base table (32 x 255 affine points)
     bool fb_ready = false;
     DevBuf tmp;                   // staging for host-pointer entry points
-    hipStream_t copy_stream = nullptr;  // zkp_msm_g1: upload of the next scalar range
-    hipEvent_t copy_event = nullptr;
-    std::vector<hipEvent_t> copy_events;  // one per scalar range of a host-fed MSM beyond the first (created on demand)
-    hipStream_t sort_stream = nullptr;  // shared-bucket MSM in several scalar ranges: digits + sort of range r+1 under accumulate r
-    hipEvent_t ev_sort[2] = {nullptr, nullptr}, ev_acc[2] = {nullptr, nullptr}, ev_begin = nullptr;
+    Event copy_event;
+    std::vector<Event> copy_events;  // one per scalar range of a host-fed MSM beyond the first (created on demand)
+    Event ev_sort[2], ev_acc[2], ev_begin;
     DevBuf fri_arena, fri_meta;   // zkp_fri_prove: layers (evaluations + Merkle nodes) and the gather descriptors
     DevBuf clk;                   // in-kernel clock stamps (ClkRec per instrumented kernel family, msm.hpp), zkp_profile_clock_read
-    // in-process multi-GPU transform (ntt_sharded.inc): two exchange buffers of one slab each, the stream the peer copies run on
-    // (under the transforms of the launch stream) and the events that order both against the other slots
+    // in-process multi-GPU transform (ntt_sharded.inc): two exchange buffers of one slab each and the events that order the peer
+    // copies of `xstream` (under the transforms of the launch stream) against the other slots
     uint32_t tail_max_waves = 2048;  // co-residency bound of msm_pyramid_tail_kernel on this device (create_slot_locked)
     DevBuf xchg_a, xchg_b;
-    hipStream_t xstream = nullptr;
-    std::vector<hipEvent_t> xev;
+    std::vector<Event> xev;
     bool peers_enabled = false;
+    // Once no entry is inside the slot: finish its work on the device, then let the members go
+    ~Ctx() {
+        std::lock_guard<std::mutex> lk(mu);
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
 };
 enum { CLK_MSM_ACCUMULATE = 0, CLK_MAD_PROBE = 1, CLK_NTT_FR = 2, CLK_NTT_GL = 3, CLK_COUNT = 4 };
 static const char* const kClkNames[CLK_COUNT] = {"msm_accumulate", "mad_probe", "ntt_fr_pass", "ntt_gl_pass"};
 
 struct Runtime {
     std::mutex mu;              // guards `slots` (creation / shutdown); never held while a context works
-    std::vector<Ctx*> slots;
+    std::vector<std::unique_ptr<Ctx>> slots;
     bool multi = false;         // zkp_init_devices() with more than one slot
 };
-Runtime g_rt;
+Runtime& g_rt = *new Runtime;  // intentionally leaked: no HIP call at process exit (zkp_shutdown releases the slots)
 
 // The record the stamps of kernel family `which` go to while profiling is on (nullptr otherwise: the kernels then execute no stamp)
 ClkRec* clk_record(int which) {
@@ -400,7 +386,7 @@ struct CtxScope {
                 rc = fail(ZKP_E_ARG, "device slot out of range (zkp_init_devices / zkp_set_device)");
                 return;
             }
-            c = g_rt.slots[(size_t)s];
+            c = g_rt.slots[(size_t)s].get();
         }
         lk = std::unique_lock<std::mutex>(c->mu);
         t_cur = c;
@@ -426,8 +412,7 @@ struct WsOrder {
     }
     ~WsOrder() {
         Ctx& c = ctx();
-        if (!c.ws_event && hipEventCreateWithFlags(&c.ws_event, hipEventDisableTiming) != hipSuccess) {
-            c.ws_event = nullptr;
+        if (c.ws_event.make(hipEventDisableTiming) != hipSuccess) {
             (void)hipStreamSynchronize(st);  // no event to order later callers with: be done before returning
             c.ws_pending = false;
             return;
@@ -465,6 +450,26 @@ int make_pow_table(const typename HostField<F>::H& base, const typename HostFiel
     return ZKP_OK;
 }
 
+// A cached table of w^e, e < count, shared by later calls on any stream: filled and drained before the caller publishes it.  On a
+// failure st is drained too before the table is freed, since its fill kernel may still be queued.
+template <class F>
+int build_pow_table(const typename HostField<F>::H& w, uint32_t count, DevBuf* out, hipStream_t st) {
+    typedef typename NttOps<F>::W W;
+    DevBuf tab;
+    ZCHK(tab.ensure(sizeof(W) * count));
+    int rc = make_pow_table<F>(w, HostField<F>::H::one(), 0, count, static_cast<W*>(tab.p), st);
+    if (rc == ZKP_OK) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize(st): ");
+    }
+    if (rc != ZKP_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    *out = std::move(tab);
+    return ZKP_OK;
+}
+
 template <class F>
 int get_radix_table(int log_r, int inverse, const typename NttOps<F>::W** out, hipStream_t st) {
     typedef typename HostField<F>::H H;
@@ -474,15 +479,13 @@ int get_radix_table(int log_r, int inverse, const typename NttOps<F>::W** out, h
     auto it = m.find(key);
     if (it == m.end()) {
         uint32_t count = log_r ? (1u << (log_r - 1)) : 1u;
-        void* p = nullptr;
-        HIPCHK(hipMalloc(&p, sizeof(W) * count));
         H w = HostField<F>::root((unsigned)log_r);
         if (inverse) w = w.inverse();
-        ZCHK(make_pow_table<F>(w, H::one(), 0, count, reinterpret_cast<W*>(p), st));
-        HIPCHK(hipStreamSynchronize(st));  // tables are shared by later calls on any stream
-        it = m.emplace(key, p).first;
+        DevBuf tab;
+        ZCHK(build_pow_table<F>(w, count, &tab, st));
+        it = m.emplace(key, std::move(tab)).first;
     }
-    *out = reinterpret_cast<const W*>(it->second);
+    *out = static_cast<const W*>(it->second.p);
     return ZKP_OK;
 }
 
@@ -531,41 +534,36 @@ int get_plan(unsigned log_n, int inverse, bool allow_wide, NttPlan<F>** out, hip
         if (pl.passes > 1) {
             pl.h = (log_n + 1) / 2;
             uint32_t nlo = 1u << pl.h, nhi = 1u << (log_n - pl.h);
-            // a plan that fails half-way is not cached: give back what it had allocated (the kernels filling the tables may
-            // still be queued on st, so drain it first)
+            // a plan that fails half-way is not cached, and `pl` gives back what it had allocated: the kernels filling the
+            // tables may still be queued on st, so drain it first
             auto build = [&]() -> int {
-                HIPCHK(hipMalloc(reinterpret_cast<void**>(&pl.inter_lo), sizeof(W) * nlo));
-                HIPCHK(hipMalloc(reinterpret_cast<void**>(&pl.inter_hi), sizeof(W) * nhi));
-                ZCHK(make_pow_table<F>(w, H::one(), 0, nlo, pl.inter_lo, st));
-                ZCHK(make_pow_table<F>(w, H::one(), pl.h, nhi, pl.inter_hi, st));
+                ZCHK(pl.inter_lo.ensure(sizeof(W) * nlo));
+                ZCHK(pl.inter_hi.ensure(sizeof(W) * nhi));
+                ZCHK(make_pow_table<F>(w, H::one(), 0, nlo, pl.inter_lo.get(), st));
+                ZCHK(make_pow_table<F>(w, H::one(), pl.h, nhi, pl.inter_hi.get(), st));
                 if (inverse) {
-                    HIPCHK(hipMalloc(reinterpret_cast<void**>(&pl.inter_lo_ninv), sizeof(W) * nlo));
-                    ZCHK(make_pow_table<F>(w, ninv, 0, nlo, pl.inter_lo_ninv, st));
+                    ZCHK(pl.inter_lo_ninv.ensure(sizeof(W) * nlo));
+                    ZCHK(make_pow_table<F>(w, ninv, 0, nlo, pl.inter_lo_ninv.get(), st));
                 }
                 unsigned outer = pl.r[0];
                 for (int p = 1; p + 1 < pl.passes; p++) {
                     const unsigned log_m = log_n - outer;
                     if (log_m <= 17) {
-                        HIPCHK(hipMalloc(reinterpret_cast<void**>(&pl.direct[p]), sizeof(W) << log_m));
-                        ZCHK(make_pow_table<F>(w, H::one(), outer, 1u << log_m, pl.direct[p], st));  // w^(e << outer) = omega_M^e
+                        ZCHK(pl.direct[p].ensure(sizeof(W) << log_m));
+                        ZCHK(make_pow_table<F>(w, H::one(), outer, 1u << log_m, pl.direct[p].get(), st));  // w^(e << outer) = omega_M^e
                     }
                     outer += pl.r[p];
                 }
                 HIPCHK(hipStreamSynchronize(st));
                 return ZKP_OK;
             };
-            const int rc = build();
-            if (rc != ZKP_OK) {
+            if (const int rc = build(); rc != ZKP_OK) {
                 (void)hipStreamSynchronize(st);
-                (void)hipFree(pl.inter_lo);
-                (void)hipFree(pl.inter_hi);
-                (void)hipFree(pl.inter_lo_ninv);
-                for (int p = 0; p < 4; p++) (void)hipFree(pl.direct[p]);
                 (void)hipGetLastError();
                 return rc;
             }
         }
-        it = m.emplace(key, pl).first;
+        it = m.emplace(key, std::move(pl)).first;
     }
     *out = &it->second;
     return ZKP_OK;
@@ -598,24 +596,13 @@ int get_coset_tables(unsigned log_n, int inverse, const uint64_t* coset, const t
         cc.valid = false;
         uint32_t h = (log_n + 1) / 2;
         uint32_t nlo = 1u << h, nhi = 1u << (log_n - h);
-        // grow-only tables: the entry forgets a table BEFORE releasing it, so that a failing hipFree / hipMalloc leaves an empty
-        // (invalid, capacity 0) entry behind and never a dangling pointer with a stale capacity
-        auto regrow = [&](W*& tab, size_t& cap, uint32_t want) -> int {
-            if (cap >= want) return ZKP_OK;
-            W* old = tab;
-            tab = nullptr;
-            cap = 0;
-            if (old) HIPCHK(hipFree(old));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&tab), sizeof(W) * want));
-            cap = want;
-            return ZKP_OK;
-        };
-        ZCHK(regrow(cc.lo, cc.lo_cap, nlo));
-        ZCHK(regrow(cc.hi, cc.hi_cap, nhi));
+        // a failing ensure leaves an empty (invalid, capacity 0) entry behind, never a dangling pointer with a stale capacity
+        ZCHK(cc.lo.ensure(sizeof(W) * nlo));
+        ZCHK(cc.hi.ensure(sizeof(W) * nhi));
         H g = H::load(coset);
         if (inverse) g = g.inverse();
-        ZCHK(make_pow_table<F>(g, c, 0, nlo, cc.lo, st));
-        ZCHK(make_pow_table<F>(g, H::one(), h, nhi, cc.hi, st));
+        ZCHK(make_pow_table<F>(g, c, 0, nlo, cc.lo.get(), st));
+        ZCHK(make_pow_table<F>(g, H::one(), h, nhi, cc.hi.get(), st));
         cc.h = h;
         cc.log_n = log_n;
         cc.inverse = inverse;
@@ -623,8 +610,8 @@ int get_coset_tables(unsigned log_n, int inverse, const uint64_t* coset, const t
         std::memcpy(cc.ckey, ckey, sizeof ckey);
         cc.valid = true;
     }
-    out->lo = cc.lo;
-    out->hi = cc.hi;
+    out->lo = cc.lo.get();
+    out->hi = cc.hi.get();
     out->h = cc.h;
     return ZKP_OK;
 }
@@ -701,40 +688,38 @@ int run_ntt(const F* d_in, F* d_data, unsigned log_n, size_t batch, int inverse,
         sp.n = n;
         sp.inner = n >> (log_outer + pl->r[p]);
         sp.log_r = pl->r[p];
-        if (pl->direct[p]) {
+        if (pl->direct[p].p) {
             sp.tw_stride_log = 0;
-            sp.inter.lo = pl->direct[p];
-            sp.inter.hi = pl->direct[p];  // never read: every exponent is below 2^h
+            sp.inter.lo = pl->direct[p].get();
+            sp.inter.hi = pl->direct[p].get();  // never read: every exponent is below 2^h
             sp.inter.h = log_n - log_outer;
         } else {
             sp.tw_stride_log = log_outer;
-            sp.inter.lo = (p == 0 && ninv_in_pass0) ? pl->inter_lo_ninv : pl->inter_lo;
-            sp.inter.hi = pl->inter_hi;
+            sp.inter.lo = ((p == 0 && ninv_in_pass0) ? pl->inter_lo_ninv : pl->inter_lo).get();
+            sp.inter.hi = pl->inter_hi.get();
             sp.inter.h = pl->h;
         }
         if (p == 0 && NttOps<F>::PASS0_MATRIX && log_n <= pass0_matrix_max_log()) {
-            F*& mat = pl->tw_matrix[ninv_in_pass0 ? 1 : 0];
-            if (!mat) {  // (the two-level tables set above are what the matrix is made from)
+            TypedBuf<F>& mat = pl->tw_matrix[ninv_in_pass0 ? 1 : 0];
+            if (!mat.p) {  // (the two-level tables set above are what the matrix is made from)
                 // An optimisation, 32 B per element held until zkp_shutdown (512 MiB per direction at 2^24): when the device has
                 // no room for it the transform keeps the two-level tables (one more product per element) instead of failing
                 // The plan is cached: the matrix is published in it only once it is filled -- a failed fill must not leave a
                 // non-null table of garbage behind for every later transform of this size
-                F* fresh = nullptr;
-                if (hipMalloc(reinterpret_cast<void**>(&fresh), sizeof(F) * n) != hipSuccess) {
+                TypedBuf<F> fresh;
+                if (hipMalloc(&fresh.p, sizeof(F) * n) != hipSuccess) {  // (not ensure: that would set the error message of a call that succeeds)
                     (void)hipGetLastError();
                 } else {
                     hipLaunchKernelGGL(twiddle_matrix_kernel<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sp.inter, (uint64_t)n,
-                                       (uint64_t)sp.inner, fresh);
+                                       (uint64_t)sp.inner, fresh.get());
                     hipError_t fe = hipGetLastError();
                     if (fe == hipSuccess) fe = hipStreamSynchronize(st);  // shared by later calls on any stream
-                    if (fe != hipSuccess) {
-                        (void)hipFree(fresh);
-                        return fail(ZKP_E_DEVICE, std::string("twiddle matrix: ") + hipGetErrorString(fe));
-                    }
-                    mat = fresh;
+                    if (fe != hipSuccess) return fail(ZKP_E_DEVICE, std::string("twiddle matrix: ") + hipGetErrorString(fe));
+                    fresh.cap = sizeof(F) * n;
+                    mat = std::move(fresh);
                 }
             }
-            sp.tw_matrix = mat;
+            sp.tw_matrix = mat.get();
         }
         sp.pre = p == 0 ? pre : no_scale<F>();
         sp.clk = clk_record(HostField<F>::ID == 0 ? CLK_NTT_FR : CLK_NTT_GL);
@@ -858,13 +843,11 @@ int run_ntt_axis0(const F* d_in, F* d_out, unsigned log_len, size_t cols, int in
         auto& cache = ctx().axis0_tw[HostField<F>::ID];
         auto it = cache.find(key);
         if (it == cache.end()) {
-            void* p = nullptr;
-            HIPCHK(hipMalloc(&p, sizeof(W) << log_len));
             H w = HostField<F>::root(log_len);
             if (inverse) w = w.inverse();
-            ZCHK(make_pow_table<F>(w, H::one(), 0, (uint32_t)L, reinterpret_cast<W*>(p), st));
-            HIPCHK(hipStreamSynchronize(st));
-            it = cache.emplace(key, p).first;
+            DevBuf tab;
+            ZCHK(build_pow_table<F>(w, (uint32_t)L, &tab, st));
+            it = cache.emplace(key, std::move(tab)).first;
         }
         ZCHK(ctx().ntt_scratch.ensure(sizeof(F) * total));
         F* work = reinterpret_cast<F*>(ctx().ntt_scratch.p);
@@ -874,7 +857,7 @@ int run_ntt_axis0(const F* d_in, F* d_out, unsigned log_len, size_t cols, int in
         sp.inner = (uint64_t)cols << r1;
         sp.log_r = (uint32_t)r0;
         sp.tw_stride_log = 0;
-        sp.inter.lo = reinterpret_cast<const W*>(it->second);
+        sp.inter.lo = static_cast<const W*>(it->second.p);
         sp.inter.hi = sp.inter.lo;  // never read: every exponent is below 2^h
         sp.inter.h = log_len;
         launch(r0);
@@ -915,15 +898,15 @@ int ntt_host_entry(uint64_t* data, unsigned log_n, int inverse, const uint64_t* 
 }  // namespace
 
 struct zkp_bases {
-    void* d_xy = nullptr;      // n x 128 B: device-internal affine form (28-bit limbs, fq28.hpp / g1_28.hpp)
-    uint8_t* d_inf = nullptr;  // nullable
+    DevBuf d_xy;               // n x 128 B: device-internal affine form (28-bit limbs, fq28.hpp / g1_28.hpp)
+    TypedBuf<uint8_t> d_inf;   // nullable
     size_t n = 0;
     int device = 0;
     int slot = 0;              // device slot that owns d_xy (Ctx::slot)
-    // zkp_init_devices with more than one slot: the handle is a CONTAINER (d_xy == nullptr) over per-slot chunk handles,
+    // zkp_init_devices with more than one slot: the handle is a CONTAINER (no d_xy) over per-slot chunk handles,
     // chunk i = points [shard_off[i], shard_off[i] + shards[i]->n) resident on slot shards[i]->slot (contiguous
     // point/scalar chunk per GPU, sharded once at creation)
-    std::vector<zkp_bases*> shards;
+    std::vector<std::unique_ptr<zkp_bases>> shards;
     std::vector<size_t> shard_off;
     uint32_t pre_c = 0;        // != 0: d_xy holds pre_planes planes of n points, plane s = 2^pre_off[s] * P (shared-bucket MSM);
                                // pre_c = widest slice in bits (2^(pre_c-1) buckets)
@@ -986,12 +969,8 @@ int zkp_abi_version(void) { return 1; }
 void zkp_profile_enable(int on) { g_prof_on.store(on == 2 ? 2 : on != 0 ? 1 : 0); }
 void zkp_profile_reset(void) {
     std::lock_guard<std::mutex> g(g_rt.mu);
-    for (Ctx* c : g_rt.slots) {
+    for (const auto& c : g_rt.slots) {
         std::lock_guard<std::mutex> lk(c->mu);
-        for (ProfRec& r : c->prof) {
-            if (r.a && r.owns_a) (void)hipEventDestroy(r.a);
-            if (r.b) (void)hipEventDestroy(r.b);
-        }
         c->prof.clear();
         if (c->clk.p) {
             int prev = 0;
@@ -1019,7 +998,7 @@ int zkp_profile_clock_read(const char* name, uint64_t* cycles, uint64_t* ref_tic
     std::lock_guard<std::mutex> g(g_rt.mu);
     *cycles = *ref_ticks = *waves = 0;
     DeviceRestore restore;
-    for (Ctx* c : g_rt.slots) {
+    for (const auto& c : g_rt.slots) {
         std::lock_guard<std::mutex> lk(c->mu);
         if (!c->clk.p) continue;
         ClkRec r;
@@ -1048,9 +1027,9 @@ int zkp_probe_mad_rate(unsigned launches, double* lane_mads_per_s, double* clock
     uint32_t* out = reinterpret_cast<uint32_t*>(ctx().tmp.p);
     ClkRec* rec = reinterpret_cast<ClkRec*>(out + (size_t)blocks * 256);
     HIPCHK(hipMemsetAsync(rec, 0, sizeof(ClkRec), nullptr));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    Event e0, e1;
+    ZCHK(e0.ensure(hipEventDefault));
+    ZCHK(e1.ensure(hipEventDefault));
     hipLaunchKernelGGL(mad_rate_probe_kernel, dim3(blocks), dim3(256), 0, nullptr, out, 7u, (ClkRec*)nullptr);  // warm-up
     HIPCHK(hipEventRecord(e0, nullptr));
     for (unsigned i = 0; i < launches; i++)
@@ -1060,8 +1039,6 @@ int zkp_probe_mad_rate(unsigned launches, double* lane_mads_per_s, double* clock
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     ClkRec r;
     HIPCHK(hipMemcpy(&r, rec, sizeof r, hipMemcpyDeviceToHost));
     const double mads = (double)launches * blocks * 256.0 * MAD_PROBE_ITERS * MAD_PROBE_CHAINS;
@@ -1077,7 +1054,7 @@ int zkp_profile_read(const char* name, double* total_ms, uint64_t* count) try {
     double tot = 0;
     uint64_t cnt = 0;
     DeviceRestore restore;
-    for (Ctx* c : g_rt.slots) {
+    for (const auto& c : g_rt.slots) {
         std::lock_guard<std::mutex> lk(c->mu);
         HIPCHK(hipSetDevice(c->device));
         for (ProfRec& r : c->prof) {
@@ -1123,7 +1100,7 @@ int create_slot_locked(int device) {
     ZCHK(allow_big_lds(msm_partscatter_kernel<PS_TILE_MID>));
     ZCHK(allow_big_lds(msm_partscatter_kernel<PS_TILE_SMALL>));
     ZCHK(allow_big_lds(fri_tail_kernel));
-    Ctx* c = new Ctx;
+    auto c = std::make_unique<Ctx>();
     c->device = device;
     c->slot = (int)g_rt.slots.size();
     {   // what the last-levels launch of the bucket reduction may assume resident: two waves per SIMD (four SIMDs per CU), and no
@@ -1136,59 +1113,9 @@ int create_slot_locked(int device) {
             (void)hipGetLastError();
         c->tail_max_waves = std::max<uint32_t>(cap, 4);
     }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return fail(ZKP_E_DEVICE, "hipStreamCreate failed");
-    }
-    g_rt.slots.push_back(c);
+    if (c->stream.make(hipStreamNonBlocking) != hipSuccess) return fail(ZKP_E_DEVICE, "hipStreamCreate failed");
+    g_rt.slots.push_back(std::move(c));
     return ZKP_OK;
-}
-
-void destroy_slot(Ctx* c) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    for (ProfRec& r : c->prof) {
-        if (r.a && r.owns_a) (void)hipEventDestroy(r.a);
-        if (r.b) (void)hipEventDestroy(r.b);
-    }
-    for (int f = 0; f < 2; f++) {
-        for (auto& kv : c->radix_tw[f]) (void)hipFree(kv.second);
-        for (auto& kv : c->axis0_tw[f]) (void)hipFree(kv.second);
-    }
-    for (auto& kv : c->plans_fr) {
-        (void)hipFree(kv.second.inter_lo); (void)hipFree(kv.second.inter_hi); (void)hipFree(kv.second.inter_lo_ninv);
-        for (auto* d : kv.second.direct) (void)hipFree(d);
-        for (auto* d : kv.second.tw_matrix) (void)hipFree(d);
-    }
-    for (auto& kv : c->plans_gl) {
-        (void)hipFree(kv.second.inter_lo); (void)hipFree(kv.second.inter_hi); (void)hipFree(kv.second.inter_lo_ninv);
-        for (auto* d : kv.second.direct) (void)hipFree(d);
-    }
-    for (int i = 0; i < Ctx::COSET_WAYS; i++) {
-        if (c->coset_fr[i].lo) (void)hipFree(c->coset_fr[i].lo);
-        if (c->coset_fr[i].hi) (void)hipFree(c->coset_fr[i].hi);
-        if (c->coset_gl[i].lo) (void)hipFree(c->coset_gl[i].lo);
-        if (c->coset_gl[i].hi) (void)hipFree(c->coset_gl[i].hi);
-    }
-    DevBuf* bufs[] = {&c->ntt_scratch, &c->scalars, &c->digits, &c->sorted, &c->entries, &c->counts, &c->start, &c->perm, &c->over,
-                      &c->pieces, &c->buckets, &c->parts, &c->pyr1, &c->odd0, &c->odd1, &c->result, &c->fb_table, &c->tmp, &c->fri_arena,
-                      &c->fri_meta, &c->clk, &c->xchg_a, &c->xchg_b};
-    for (DevBuf* b : bufs) b->release();
-    if (c->host_result) (void)hipHostFree(c->host_result);
-    if (c->fri_small) (void)hipHostFree(c->fri_small);
-    if (c->copy_event) (void)hipEventDestroy(c->copy_event);
-    for (hipEvent_t e : c->copy_events) (void)hipEventDestroy(e);
-    c->copy_events.clear();
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (hipEvent_t e : {c->ev_sort[0], c->ev_sort[1], c->ev_acc[0], c->ev_acc[1], c->ev_begin})
-        if (e) (void)hipEventDestroy(e);
-    if (c->sort_stream) (void)hipStreamDestroy(c->sort_stream);
-    for (hipEvent_t e : c->xev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->xstream) (void)hipStreamDestroy(c->xstream);
-    if (c->ws_event) (void)hipEventDestroy(c->ws_event);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
 }
 
 }  // namespace
@@ -1223,7 +1150,6 @@ int zkp_init_devices(const int* devices, int n_devices) try {
     for (int d : want) {
         const int rc = create_slot_locked(d);
         if (rc != ZKP_OK) {
-            for (Ctx* c : g_rt.slots) { destroy_slot(c); delete c; }
             g_rt.slots.clear();
             return rc;
         }
@@ -1250,10 +1176,6 @@ int zkp_set_device(int slot) try {
 void zkp_shutdown(void) {
     device_workers_stop();
     std::lock_guard<std::mutex> g(g_rt.mu);
-    for (Ctx* c : g_rt.slots) {
-        destroy_slot(c);
-        delete c;
-    }
     g_rt.slots.clear();
     g_rt.multi = false;
 }
@@ -1264,19 +1186,14 @@ void zkp_shutdown(void) {
 namespace {
 
 int bases_alloc(size_t n, bool with_inf, zkp_bases** out) {
-    zkp_bases* b = new (std::nothrow) zkp_bases();
+    std::unique_ptr<zkp_bases> b(new (std::nothrow) zkp_bases());
     if (!b) return fail(ZKP_E_NOMEM, "host allocation failed");
     b->n = n;
     b->device = ctx().device;
     b->slot = ctx().slot;
-    hipError_t e = hipMalloc(&b->d_xy, std::max<size_t>(128 * n, 128));
-    if (e == hipSuccess && with_inf) e = hipMalloc(reinterpret_cast<void**>(&b->d_inf), std::max<size_t>(n, 1));
-    if (e != hipSuccess) {
-        if (b->d_xy) (void)hipFree(b->d_xy);
-        delete b;
-        return fail(e == hipErrorOutOfMemory ? ZKP_E_NOMEM : ZKP_E_DEVICE, hipGetErrorString(e));
-    }
-    *out = b;
+    HIPCHK_BARE(b->d_xy.grow(std::max<size_t>(128 * n, 128)));
+    if (with_inf) HIPCHK_BARE(b->d_inf.grow(std::max<size_t>(n, 1)));
+    *out = b.release();
     return ZKP_OK;
 }
 
@@ -1305,10 +1222,10 @@ int bases_create_single(int slot, const uint64_t* xy, const uint8_t* is_inf, siz
         if (e == hipSuccess) {
             hipLaunchKernelGGL(g1_to_internal_kernel, dim3((unsigned)((n + MSM_THREADS - 1) / MSM_THREADS)),
                                dim3(MSM_THREADS), 0, st, reinterpret_cast<const uint4*>(ctx().tmp.p), (uint64_t)n,
-                               reinterpret_cast<uint4*>(b->d_xy));
+                               static_cast<uint4*>(b->d_xy.p));
             e = hipGetLastError();
         }
-        if (e == hipSuccess && is_inf) e = hipMemcpyAsync(b->d_inf, is_inf, n, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && is_inf) e = hipMemcpyAsync(b->d_inf.p, is_inf, n, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
     if (e != hipSuccess) {
@@ -1387,7 +1304,7 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool check_only = fals
         cmax = base + (rem ? 1 : 0);
         for (uint32_t s = 0; s < planes; s++) so.off[s + 1] = (uint16_t)(so.off[s] + base + (s < rem ? 1 : 0));
     }
-    void* p = nullptr;
+    DevBuf p;
     {   // The expansion is `planes` x the SRS (13 x at 20 bits, 12 x at 22: 103 GB for 2^26 points, and a 2^27 SRS no longer fits one
         // device).  Say so with the numbers instead of a bare allocation failure; the handle stays usable unexpanded (per-window MSM).
         const size_t need = 128 * (size_t)planes * b->n;
@@ -1404,28 +1321,25 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool check_only = fals
         };
         if (need > budget) return too_large(need > free_b && free_b ? "device memory" : "ZKP_SRS_EXPAND_MAX_BYTES");
         if (check_only) return ZKP_OK;
-        if (hipMalloc(&p, need) != hipSuccess) {
+        if (p.ensure(need) != ZKP_OK) {
             (void)hipGetLastError();
             return too_large("hipMalloc");
         }
     }
-    hipError_t e = hipMemcpyAsync(p, b->d_xy, 128 * b->n, hipMemcpyDeviceToDevice, st);
+    hipError_t e = hipMemcpyAsync(p.p, b->d_xy.p, 128 * b->n, hipMemcpyDeviceToDevice, st);
     const uint64_t step = std::min<uint64_t>(b->n, 1ull << 18);  // points per launch: bounds the scratch area (ZZ, ZZZ, products)
     if (e == hipSuccess && ctx().tmp.ensure(192 * (size_t)planes * step) != ZKP_OK) e = hipErrorOutOfMemory;
     for (uint64_t off = 0; e == hipSuccess && off < b->n; off += step) {
         const uint64_t cnt = std::min<uint64_t>(step, b->n - off);
         hipLaunchKernelGGL(g1_expand_planes_kernel, dim3((unsigned)((cnt + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS),
-                           0, st, reinterpret_cast<uint4*>(p), reinterpret_cast<uint4*>(ctx().tmp.p), off, cnt,
+                           0, st, static_cast<uint4*>(p.p), reinterpret_cast<uint4*>(ctx().tmp.p), off, cnt,
                            (uint64_t)b->n, planes, so);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
+    if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? ZKP_E_NOMEM : ZKP_E_DEVICE, std::string("SRS expansion: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(b->d_xy);
-    b->d_xy = p;
+    b->d_xy = std::move(p);
     b->pre_c = cmax;
     b->pre_req = window_bits;
     b->pre_planes = planes;
@@ -1439,16 +1353,12 @@ int unexpand_single(zkp_bases* b) {
     CTX_ENTER(b->slot);
     hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
     WsOrder ord(st);
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, 128 * std::max<size_t>(b->n, 1)));
-    hipError_t e = hipMemcpyAsync(p, b->d_xy, 128 * b->n, hipMemcpyDeviceToDevice, st);
+    DevBuf p;
+    ZCHK(p.ensure(128 * std::max<size_t>(b->n, 1)));
+    hipError_t e = hipMemcpyAsync(p.p, b->d_xy.p, 128 * b->n, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return fail(ZKP_E_DEVICE, hipGetErrorString(e));
-    }
-    (void)hipFree(b->d_xy);
-    b->d_xy = p;
+    if (e != hipSuccess) return fail(ZKP_E_DEVICE, hipGetErrorString(e));
+    b->d_xy = std::move(p);
     b->pre_c = b->pre_req = b->pre_planes = 0;
     return ZKP_OK;
 }
@@ -1470,7 +1380,7 @@ int zkp_g1_bases_create(const uint64_t* xy, const uint8_t* is_inf, size_t n, zkp
     if (!c) return fail(ZKP_E_NOMEM, "host allocation failed");
     c->n = n;
     c->slot = -1;
-    c->shards.assign(nslots, nullptr);
+    c->shards.resize(nslots);
     c->shard_off.assign(nslots, 0);
     for (size_t i = 0; i < nslots; i++) {
         size_t hi = 0;
@@ -1479,7 +1389,10 @@ int zkp_g1_bases_create(const uint64_t* xy, const uint8_t* is_inf, size_t n, zkp
     const int rc = for_each_shard(c, [&](size_t i) {  // (shards[i] is still null here: for_each_shard only reads its slot on failure)
         size_t lo = 0, hi = 0;
         shard_range(n, i, nslots, &lo, &hi);
-        return bases_create_single((int)i, xy + 12 * lo, is_inf ? is_inf + lo : nullptr, hi - lo, &c->shards[i]);
+        zkp_bases* s = nullptr;
+        const int r = bases_create_single((int)i, xy + 12 * lo, is_inf ? is_inf + lo : nullptr, hi - lo, &s);
+        c->shards[i].reset(s);
+        return r;
     });
     if (rc != ZKP_OK) {
         zkp_g1_bases_destroy(c);
@@ -1512,10 +1425,10 @@ int zkp_g1_bases_create_dev(const void* d_xy, const uint8_t* d_is_inf, size_t n,
     hipError_t e = hipSuccess;
     if (n) {
         hipLaunchKernelGGL(g1_to_internal_kernel, dim3((unsigned)((n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS),
-                           0, st, reinterpret_cast<const uint4*>(d_xy), (uint64_t)n, reinterpret_cast<uint4*>(b->d_xy));
+                           0, st, reinterpret_cast<const uint4*>(d_xy), (uint64_t)n, static_cast<uint4*>(b->d_xy.p));
         e = hipGetLastError();
     }
-    if (e == hipSuccess && n && d_is_inf) e = hipMemcpyAsync(b->d_inf, d_is_inf, n, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && n && d_is_inf) e = hipMemcpyAsync(b->d_inf.p, d_is_inf, n, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         zkp_g1_bases_destroy(b);
@@ -1532,20 +1445,20 @@ int zkp_g1_bases_precompute(zkp_bases* b, unsigned window_bits) try {
     // automatic width comes from the largest chunk, every chunk's device is asked for room BEFORE any of them allocates, and a
     // failure half way rolls the finished chunks back to the plain points.
     size_t nmax = 0, expanded = 0;
-    for (const zkp_bases* sh : b->shards) nmax = std::max(nmax, sh->n), expanded += sh->pre_c ? 1 : 0;
+    for (const auto& sh : b->shards) nmax = std::max(nmax, sh->n), expanded += sh->pre_c ? 1 : 0;
     if (window_bits == 0) {
         if (expanded == b->shards.size() || !(window_bits = auto_window_bits(nmax))) return ZKP_OK;
         if (expanded) window_bits = b->shards[0]->pre_req ? b->shards[0]->pre_req : window_bits;
     }
-    ZCHK(for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i], window_bits, true); }));
+    ZCHK(for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i].get(), window_bits, true); }));
     std::vector<uint8_t> was(b->shards.size());
     for (size_t i = 0; i < b->shards.size(); i++) was[i] = b->shards[i]->pre_c ? 1 : 0;
-    const int rc = for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i], window_bits); });  // every chunk on its own device
+    const int rc = for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i].get(), window_bits); });  // every chunk on its own device
     if (rc != ZKP_OK) {
         const std::string why = zkp_last_error();
         bool mixed = false;
         for (size_t i = 0; i < b->shards.size(); i++)
-            if (!was[i] && b->shards[i]->pre_c && unexpand_single(b->shards[i]) != ZKP_OK) mixed = true;
+            if (!was[i] && b->shards[i]->pre_c && unexpand_single(b->shards[i].get()) != ZKP_OK) mixed = true;
         return fail(rc, why + (mixed ? " -- and a finished chunk could not be rolled back: the handle is expanded in part (still usable)"
                                      : " -- every chunk is back to the plain points"));
     }
@@ -1556,7 +1469,7 @@ size_t zkp_g1_bases_len(const zkp_bases* b) { return b ? b->n : 0; }
 
 int zkp_g1_bases_info(const zkp_bases* b, unsigned* window_bits, unsigned* slices) try {
     if (!b || !window_bits || !slices) return fail(ZKP_E_ARG, "null argument");
-    const zkp_bases* s = b->shards.empty() ? b : b->shards[0];  // every chunk of a sharded handle is expanded alike
+    const zkp_bases* s = b->shards.empty() ? b : b->shards[0].get();  // every chunk of a sharded handle is expanded alike
     if (!s) return fail(ZKP_E_ARG, "empty handle");
     *window_bits = s->pre_req;
     *slices = s->pre_c ? s->pre_planes : 0;
@@ -1565,15 +1478,9 @@ int zkp_g1_bases_info(const zkp_bases* b, unsigned* window_bits, unsigned* slice
 
 void zkp_g1_bases_destroy(zkp_bases* b) {
     if (!b) return;
-    for (zkp_bases* s : b->shards) zkp_g1_bases_destroy(s);
-    if (b->d_xy || b->d_inf) {
-        int prev = 0;
-        const bool restore = hipGetDevice(&prev) == hipSuccess && prev != b->device;
-        if (restore) (void)hipSetDevice(b->device);
-        if (b->d_xy) (void)hipFree(b->d_xy);
-        if (b->d_inf) (void)hipFree(b->d_inf);
-        if (restore) (void)hipSetDevice(prev);
-    }
+    for (auto& s : b->shards) zkp_g1_bases_destroy(s.release());
+    DeviceRestore restore;
+    (void)hipSetDevice(b->device);
     delete b;
 }
 
@@ -1597,10 +1504,8 @@ int msm_host_scalars(const zkp_bases* bases, const uint64_t* scalars, size_t n, 
     const Fr* d_sc = reinterpret_cast<const Fr*>(ctx().scalars.p);
     const bool shared = bases->pre_c != 0;
     if (shared && n >= (1u << 19)) {  // pipeline the PCIe upload against the kernels
-        if (!ctx().copy_stream) {
-            HIPCHK(hipStreamCreateWithFlags(&ctx().copy_stream, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&ctx().copy_event, hipEventDisableTiming));
-        }
+        ZCHK(ctx().copy_stream.ensure(hipStreamNonBlocking));
+        ZCHK(ctx().copy_event.ensure(hipEventDisableTiming));
         const MsmFeed feed{scalars, ctx().copy_stream, ctx().copy_event, msm_feed_ranges(n)};  // (the range policy: msm_plan.hpp)
         return msm_partial_batch(bases, &d_sc, 1, n, st, r, &feed);
     }
@@ -1620,7 +1525,7 @@ int msm_host_scalars_any(const zkp_bases* bases, const uint64_t* scalars, size_t
         const size_t lo = bases->shard_off[i];
         if (lo >= n) return (int)ZKP_OK;
         const size_t len = std::min(bases->shards[i]->n, n - lo);
-        return msm_host_scalars(bases->shards[i], scalars + 4 * lo, len, &part[i]);
+        return msm_host_scalars(bases->shards[i].get(), scalars + 4 * lo, len, &part[i]);
     }));
     HXyzz acc = HXyzz::infinity();
     for (size_t i = 0; i < k; i++) acc = acc.add(part[i]);
@@ -1668,7 +1573,7 @@ int zkp_g1_bases_shard_count(const zkp_bases* b) { return !b ? 0 : b->shards.emp
 int zkp_g1_bases_shard(const zkp_bases* b, size_t i, int* slot, int* device, size_t* offset, size_t* len) try {
     if (!b || !slot || !device || !offset || !len) return fail(ZKP_E_ARG, "null argument");
     if (i >= (size_t)zkp_g1_bases_shard_count(b)) return fail(ZKP_E_ARG, "chunk index out of range");
-    const zkp_bases* s = b->shards.empty() ? b : b->shards[i];
+    const zkp_bases* s = b->shards.empty() ? b : b->shards[i].get();
     *slot = s->slot;
     *device = s->device;
     *offset = b->shards.empty() ? 0 : b->shard_off[i];
@@ -1708,7 +1613,7 @@ int zkp_msm_g1_sharded_dev_after(const zkp_bases* bases, const void* const* d_sc
         std::vector<HXyzz> part(k, HXyzz::infinity());
         ZCHK(for_each_shard(bases, [&](size_t i) {
             const size_t lo = bases->shard_off[i];
-            const zkp_bases* sh = bases->shards[i];
+            const zkp_bases* sh = bases->shards[i].get();
             if (lo >= n || !sh->n) return (int)ZKP_OK;
             const size_t len = std::min(sh->n, n - lo);
             CTX_ENTER(sh->slot);

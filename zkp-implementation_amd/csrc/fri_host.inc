@@ -192,14 +192,8 @@ int zkp_fri_prove(const uint64_t* coeffs, size_t d, size_t blowup, size_t num_qu
     FriTranscriptState* dstate = reinterpret_cast<FriTranscriptState*>(base + state_off);
     uint64_t* d_r = base + state_off + 8;  // one challenge per large layer
     uint64_t* d_roots = d_r + L + 1;       // and its Merkle root (written by fri_transcript_kernel)
-    if (ctx().fri_small_cap < 8 * small_words) {  // pinned: a D2H into pageable memory costs ~20 us per call
-        if (ctx().fri_small) HIPCHK(hipHostFree(ctx().fri_small));
-        ctx().fri_small = nullptr;
-        ctx().fri_small_cap = 0;
-        HIPCHK(hipHostMalloc(&ctx().fri_small, 8 * small_words, hipHostMallocDefault));
-        ctx().fri_small_cap = 8 * small_words;
-    }
-    uint64_t* h_small = static_cast<uint64_t*>(ctx().fri_small);
+    ZCHK(ctx().fri_small.ensure(8 * small_words, hipHostMallocDefault));  // pinned: a D2H into pageable memory costs ~20 us per call
+    uint64_t* h_small = static_cast<uint64_t*>(ctx().fri_small.p);
     HIPCHK(hipMemcpyAsync(dstate, &hstate, sizeof hstate, hipMemcpyHostToDevice, st));
     size_t l = 0;
     auto prep = [&](const uint64_t* src, uint64_t src_len, const uint64_t* r_ptr, const HGl& cs, uint64_t next_dom, uint64_t* next_poly,

@@ -51,18 +51,12 @@ struct MsmPass {
     // blit launch per MSM); the device `result` buffer holds the barrier counters of the last launch.
     int grow() {
         for (const auto& [name, buf, bytes] : buffers()) ZCHK(buf->ensure(bytes));
-        if (cx.host_result_cap < p.bytes.host_result) {
-            if (cx.host_result) HIPCHK(hipHostFree(cx.host_result));
-            cx.host_result = nullptr;
-            cx.host_result_cap = 0;
-            HIPCHK(hipHostMalloc(&cx.host_result, p.bytes.host_result, hipHostMallocPortable | hipHostMallocMapped));  // written by this slot's device
-            cx.host_result_cap = p.bytes.host_result;
-        }
+        ZCHK(cx.host_result.ensure(p.bytes.host_result, hipHostMallocPortable | hipHostMallocMapped));  // written by this slot's device
         ptot = cx.counts.get() + W * g.nchunk * nhi;
         pstart = ptot + W * nhi;
         ghist = pstart + W * (nhi + 1);
         gcur = ghist + W * 256;
-        result_out = static_cast<uint4*>(cx.host_result);
+        result_out = static_cast<uint4*>(cx.host_result.p);
         result_flags = reinterpret_cast<uint32_t*>(result_out + 16 * W * g.c);
         return ZKP_OK;
     }
@@ -80,10 +74,10 @@ struct MsmPass {
         auto show = [](const char* name, const void* q, size_t bytes) {
             fprintf(stderr, "ZKP_MSM_CHECK %-10s %p .. %p (%zu bytes)\n", name, q, static_cast<const char*>(q) + bytes, bytes);
         };
-        show("bases", bases->d_xy, (size_t)bases->n * 128 * std::max(bases->pre_planes, 1u));
+        show("bases", bases->d_xy.p, (size_t)bases->n * 128 * std::max(bases->pre_planes, 1u));
         show("scalars", scalars[0], 32 * n);
         for (const auto& [name, buf, bytes] : buffers()) show(name, buf->p, buf->cap);
-        show("host_res", cx.host_result, cx.host_result_cap);
+        show("host_res", cx.host_result.p, cx.host_result.cap);
         fprintf(stderr, "ZKP_MSM_CHECK geometry: n %zu range %llu first %llu rest %llu entries %llu nb %u nchunk %u over_cap %u desc_cap %u run_limit %u piece %u\n",
                 n, (unsigned long long)p.range, (unsigned long long)p.lens[0], (unsigned long long)p.lens.back(), (unsigned long long)p.g.n,
                 p.g.nb, p.g.nchunk, p.over_cap, p.desc_cap, p.g.run_limit, p.g.piece);
@@ -96,9 +90,9 @@ struct MsmPass {
         Fr* const dst = const_cast<Fr*>(scalars[0]);
         if (p.lens.size() > 1) {
             while (cx.copy_events.size() < p.lens.size() - 1) {
-                hipEvent_t e = nullptr;
-                HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                cx.copy_events.push_back(e);
+                Event e;
+                ZCHK(e.ensure(hipEventDisableTiming));
+                cx.copy_events.push_back(std::move(e));
             }
             up.submit(uploader(cx.slot), std::vector<uint64_t>(p.lens.begin() + 1, p.lens.end()), p.lens[0],
                       [device = cx.device] { return hipSetDevice(device) == hipSuccess ? (int)ZKP_OK : (int)ZKP_E_DEVICE; },
@@ -118,11 +112,8 @@ struct MsmPass {
     // The scalar ranges in order.  With overlap the digits + sort of range r+1 run on `sst` under the accumulate of range r on `st`.
     int walk() {
         if (p.overlap) {  // the sort stream starts after whatever the caller enqueued on st (the scalars)
-            if (!cx.sort_stream) {
-                HIPCHK(hipStreamCreateWithFlags(&cx.sort_stream, hipStreamNonBlocking));
-                for (hipEvent_t* e : {&cx.ev_sort[0], &cx.ev_sort[1], &cx.ev_acc[0], &cx.ev_acc[1], &cx.ev_begin})
-                    HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-            }
+            ZCHK(cx.sort_stream.ensure(hipStreamNonBlocking));
+            for (Event* e : {&cx.ev_sort[0], &cx.ev_sort[1], &cx.ev_acc[0], &cx.ev_acc[1], &cx.ev_begin}) ZCHK(e->ensure(hipEventDisableTiming));
             sst = cx.sort_stream;
             HIPCHK(hipEventRecord(cx.ev_begin, st));
             HIPCHK(hipStreamWaitEvent(sst, cx.ev_begin, 0));
@@ -169,7 +160,7 @@ struct MsmPass {
             DigitSources ds;  // digits laid out [msm][slice][scalar]: a shared-mode sort window is one msm
             for (size_t m = 0; m < count; m++) ds.scalars[m] = scalars[m] + off;
             hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)((g.ns + MSM_THREADS - 1) / MSM_THREADS), (unsigned)count), dim3(MSM_THREADS), 0,
-                               sst, ds, bases->d_inf ? bases->d_inf + off : nullptr, g, p.nwin1, cx.digits.get());
+                               sst, ds, bases->d_inf.p ? bases->d_inf.get() + off : nullptr, g, p.nwin1, cx.digits.get());
             MSM_TRACE(sst, ridx, "digits");
         }
         ProfScope ps("msm_sort", sst, true);
@@ -202,7 +193,7 @@ struct MsmPass {
         const uint32_t bucket_blocks = (uint32_t)((((uint64_t)g.nb << g.split_log) + per_block - 1) / per_block);
         const uint32_t extra_blocks = std::min<uint32_t>((p.desc_cap + per_block - 1) / per_block, 64);
         const dim3 grid((bucket_blocks + extra_blocks) * g.nwin);
-        const uint4* xy = reinterpret_cast<const uint4*>(bases->d_xy) + off * 8;
+        const uint4* xy = static_cast<const uint4*>(bases->d_xy.p) + off * 8;
         uint4 *buckets = cx.buckets.get(), *pieces = cx.pieces.get(), *parts = cx.parts.get(), *carry = cx.pyr1.get();
         if (quad)
             hipLaunchKernelGGL(msm_accumulate_quad_kernel, grid, dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,

@@ -9,7 +9,7 @@ struct zkp_nova_r1cs {
     const zkp_bases* srs = nullptr;
     int slot = 0;
     uint32_t rows = 0, nv = 0, nio = 0;
-    void* mem = nullptr;  // one allocation: per matrix row_ptr | cols | vals, then the two row lists
+    DevBuf mem;           // one allocation: per matrix row_ptr | cols | vals, then the two row lists
     NovaCsr m[3];
     const uint32_t* short_rows = nullptr;
     const uint32_t* long_rows = nullptr;
@@ -176,15 +176,9 @@ int zkp_nova_transcript_challenges(zkp_nova_transcript* t, size_t n, uint64_t* o
 // ---- R1CS handle -----------------------------------------------------------------------------------------------------------------
 void zkp_nova_r1cs_destroy(zkp_nova_r1cs* r) {
     if (!r) return;
-    {
-        CtxScope s(r->slot);
-        if (s.rc == ZKP_OK) {
-            (void)hipDeviceSynchronize();
-            if (r->mem) (void)hipFree(r->mem);
-            r->stage.release();
-        }
-    }
-    delete r;
+    CtxScope s(r->slot);
+    if (s.rc == ZKP_OK) (void)hipDeviceSynchronize();
+    delete r;  // (also when the slot is gone: its buffers are released rather than leaked, hipFree finds their device itself)
 }
 
 int zkp_nova_r1cs_create(const zkp_bases* srs, size_t rows, size_t num_vars, size_t num_io, const zkp_csr* a, const zkp_csr* b,
@@ -219,20 +213,16 @@ int zkp_nova_r1cs_create(const zkp_bases* srs, size_t rows, size_t num_vars, siz
     const size_t off_x = total; total = align(total + 32 * (2 * num_io + 1));
     const size_t off_t = total; total = align(total + 32 * rows);
     const size_t off_cnt = total; total += 8;
-    std::unique_ptr<zkp_nova_r1cs> r(new zkp_nova_r1cs());
+    CTX_ENTER(srs->slot);
+    WsOrder ord(nullptr);
+    std::unique_ptr<zkp_nova_r1cs> r(new zkp_nova_r1cs());  // handed out only complete; freed on the slot's device otherwise
     r->srs = srs;
     r->slot = srs->slot;
     r->rows = (uint32_t)rows;
     r->nv = (uint32_t)num_vars;
     r->nio = (uint32_t)num_io;
-    CTX_ENTER(srs->slot);
-    WsOrder ord(nullptr);
-    HIPCHK(hipMalloc(&r->mem, total));
-    struct FreeOnError {  // the handle is only handed out complete
-        zkp_nova_r1cs* r;
-        ~FreeOnError() { if (r && r->mem) (void)hipFree(r->mem); }
-    } guard{r.get()};
-    char* base = static_cast<char*>(r->mem);
+    ZCHK(r->mem.ensure(total));
+    char* base = static_cast<char*>(r->mem.p);
     for (int k = 0; k < 3; k++) {
         const size_t nnz = mats[k]->row_ptr[rows];
         HIPCHK(hipMemcpy(base + off[k][0], mats[k]->row_ptr, 8 * (rows + 1), hipMemcpyHostToDevice));
@@ -252,7 +242,6 @@ int zkp_nova_r1cs_create(const zkp_bases* srs, size_t rows, size_t num_vars, siz
     r->d_x = reinterpret_cast<Fr*>(base + off_x);
     r->d_t = reinterpret_cast<Fr*>(base + off_t);
     r->d_count = reinterpret_cast<unsigned long long*>(base + off_cnt);
-    guard.r = nullptr;
     *out = r.release();
     return ZKP_OK;
 } ZKP_CATCH_INT

@@ -98,7 +98,7 @@ struct ShardSlot {
     Fr* b = nullptr;
     hipStream_t main = nullptr, xs = nullptr;
     int device = -1;
-    const hipEvent_t* ev = nullptr;
+    const Event* ev = nullptr;
 };
 struct ShardCall {
     ShardGeom g;
@@ -218,12 +218,12 @@ int shard_job(ShardCall& c, size_t g, std::string* msg) {
             const size_t bytes = sizeof(Fr) * G.slab;
             ZCHK(cx.xchg_a.ensure(bytes));
             ZCHK(cx.xchg_b.ensure(bytes));
-            if (!cx.xstream) HIPCHK(hipStreamCreateWithFlags(&cx.xstream, hipStreamNonBlocking));
+            ZCHK(cx.xstream.ensure(hipStreamNonBlocking));
             const size_t nev = (size_t)(SH_EV_PER_CHUNK * C + SH_EV_EXTRA);
             while (cx.xev.size() < nev) {
-                hipEvent_t e = nullptr;
-                HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                cx.xev.push_back(e);
+                Event e;
+                ZCHK(e.ensure(hipEventDisableTiming));
+                cx.xev.push_back(std::move(e));
             }
             if (!cx.peers_enabled) {  // direct reads of the other slots' devices; without it a peer copy is staged through the host
                 for (int od : c.devices) {
@@ -430,7 +430,7 @@ int ntt_sharded_run(ShardCall& c) {
     {
         std::lock_guard<std::mutex> g(g_rt.mu);
         if (g_rt.slots.size() != W) return fail(ZKP_E_ARG, "the device slots changed during the call");
-        for (Ctx* o : g_rt.slots) c.devices.push_back(o->device);
+        for (const auto& o : g_rt.slots) c.devices.push_back(o->device);
     }
     std::vector<int> rc(W, ZKP_OK);
     std::vector<std::string> msg(W);

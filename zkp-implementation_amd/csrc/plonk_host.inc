@@ -5,35 +5,48 @@
 // boundary (they are inputs here), so a Rust shim keeps its transcript and calls one entry per round.
 // Polynomials stay resident in HBM between rounds.
 
+// The scratch the evaluation, division and scan helpers work in, by value: a prover's own buffers (zkp_plonk_prover::scratch(), made
+// per call from the owners) or scratch borrowed by open_eval_div_dev
+struct PlonkScratch {
+    Fr* ev;                       // 2 len elements per division
+    Fr* scan;
+    uint64_t scan_cap;
+    Fr* partial;
+    unsigned partial_cap;
+    uint64_t* h_pin;              // nullable (borrowed scratch): wait_stream then waits on the stream
+    unsigned long long* poll_seq;
+};
+
 struct zkp_plonk_prover {
     const zkp_bases* srs = nullptr;
     unsigned log_n = 0, log_D = 0;
     uint64_t n = 0, D = 0, cap = 0;  // cap = n + 8 coefficients per working polynomial
     HFr k1, k2;
     // device polynomials (Fr coefficients)
-    Fr* circ = nullptr;   // 12 x n: q_m q_l q_r q_o q_c pi f_a f_b f_c s1 s2 s3
-    Fr* work = nullptr;   // 8 x cap: ax bx cx z r wz wzw txc
-    Fr* t = nullptr;      // D
-    Fr* ev = nullptr;     // 15 x D
+    int device = 0;                // of the SRS's slot: where the resources below live
+    TypedBuf<Fr> circ;    // 12 x n: q_m q_l q_r q_o q_c pi f_a f_b f_c s1 s2 s3
+    TypedBuf<Fr> work;    // 8 x cap: ax bx cx z r wz wzw txc
+    TypedBuf<Fr> t;       // D
+    TypedBuf<Fr> ev;      // 15 x D
     // The 4n-coset evaluations of a(X), b(X), c(X), z(X) (slots 0..3 of the quotient's inputs) live in a buffer of their own and are
     // computed EARLY, on a second stream: those of a, b, c underneath round 1's commitments (they need no challenge), that of z
     // underneath round 2's -- a 2^16-term MSM is a chain of latencies that leaves most of the machine idle, so the transforms ride
     // along for free and round 3 starts at the quotient kernel (round 5: 0.1 ms per proof).  Every entry waits for the side stream's
     // work before it returns, so nothing of it outlives the call.
-    Fr* ev_w = nullptr;   // 4 x D
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_abc = nullptr, ev_z = nullptr;
-    Fr* scan = nullptr;   // scan scratch (plonk.hpp, scan_scratch_elems)
+    TypedBuf<Fr> ev_w;    // 4 x D
+    Stream side;
+    Event ev_fork, ev_abc, ev_z;
+    TypedBuf<Fr> scan;    // scan scratch (plonk.hpp, scan_scratch_elems)
     uint64_t scan_cap = 0;
-    Fr* partial = nullptr;
+    TypedBuf<Fr> partial;
     unsigned partial_cap = 0;
-    unsigned long long* d_len = nullptr;
-    Fr* dom_evals = nullptr;    // the 12 circuit polynomials evaluated on the domain (12 n, circuit order): circuit constants, computed by the first round 2
+    TypedBuf<unsigned long long> d_len;
+    TypedBuf<Fr> dom_evals;     // the 12 circuit polynomials evaluated on the domain (12 n, circuit order): circuit constants, computed by the first round 2
     // "No remainder expected" (prover.rs:404,431,441), decided exactly on the domain instead of by long division:
     int gate_rows_bad = -1;     // rows of the witness that violate their gate equation (-1: not checked yet; a circuit constant)
     bool perm_closes = false;   // this proof's beta, gamma: prod_i num_i == prod_i den_i, i.e. the accumulator returns to 1 (:431)
-    uint64_t* h_pin = nullptr;  // pinned host scratch (32 * partial_cap bytes) for the small read-backs: a D2H into pageable
-                                // memory costs ~20 us per call; one more line behind it holds the flag of wait_stream
+    TypedBuf<uint64_t, PinnedBuf> h_pin;  // pinned host scratch (32 * partial_cap bytes) for the small read-backs: a D2H into pageable
+                                          // memory costs ~20 us per call; one more line behind it holds the flag of wait_stream
     unsigned long long poll_seq = 0;
     uint64_t t_len = 0, chunk = 0, r_len = 0, wz_len = 0, wzw_len = 0;
     int stage = 0;
@@ -46,6 +59,7 @@ struct zkp_plonk_prover {
     // per-prover constants (host inversions are ~15 us each): 1 / Z_H on the D / n cosets of the quotient domain, 1 / n
     bool consts_ready = false;
     HFr zh_inv[8], n_inv;
+    PlonkScratch scratch() { return {ev, scan, scan_cap, partial, partial_cap, h_pin, &poll_seq}; }
     Fr* poly(int i) const { return work + (uint64_t)i * cap; }
     Fr* circuit(int i) const { return circ + (uint64_t)i * n; }
 };
@@ -107,7 +121,7 @@ int commit_batch_dev(const zkp_plonk_prover* p, const Fr* const* coeffs, size_t 
 
 // up to SCAN_MAX_BATCH independent scans with one operator in one set of three launches
 template <class Op>
-int run_scan_batch(zkp_plonk_prover* p, const ScanJob* jobs, int count, hipStream_t st) {
+int run_scan_batch(const PlonkScratch& s, const ScanJob* jobs, int count, hipStream_t st) {
     if (count < 1 || count > SCAN_MAX_BATCH) return fail(ZKP_E_ARG, "internal: scan batch");
     ScanParams sp;
     std::memset(&sp, 0, sizeof sp);
@@ -119,10 +133,10 @@ int run_scan_batch(zkp_plonk_prover* p, const ScanJob* jobs, int count, hipStrea
     if (nmax == 0) return ZKP_OK;
     sp.chunk = scan_chunk_for(nmax);
     const uint64_t blocks = scan_blocks_for(nmax);
-    if (blocks > (1u << 20) || SCAN_MAX_BATCH * blocks * 257 > p->scan_cap) return fail(ZKP_E_ARG, "internal: scan scratch too small");
+    if (blocks > (1u << 20) || SCAN_MAX_BATCH * blocks * 257 > s.scan_cap) return fail(ZKP_E_ARG, "internal: scan scratch too small");
     sp.blocks = (uint32_t)blocks;
-    sp.tpre = p->scan;
-    sp.btot = p->scan + SCAN_MAX_BATCH * blocks * 256;
+    sp.tpre = s.scan;
+    sp.btot = s.scan + SCAN_MAX_BATCH * blocks * 256;
     const dim3 grid((unsigned)blocks, (unsigned)count);
     hipLaunchKernelGGL((scan_block_kernel<Op>), grid, dim3(256), 0, st, sp);
     hipLaunchKernelGGL((scan_mid_kernel<Op>), dim3(1, (unsigned)count), dim3(256), 0, st, sp);
@@ -137,14 +151,14 @@ struct EvalReq { const Fr* c; uint64_t len; HFr z; HFr* out; };
 // quotient's length, two sets of evaluations) and the runtime's stream wait costs 30-60 us of wake-up latency each time: a one-thread
 // kernel writes a sequence number into pinned memory behind the read-back and the host polls it (as the MSM does with its result
 // flags, profiles/r05_k); after two seconds, or without a pinned buffer (zkp_kzg_open's borrowed scratch), the stream wait.
-int wait_stream(zkp_plonk_prover* p, hipStream_t st) {
+int wait_stream(const PlonkScratch& s, hipStream_t st) {
     static const bool no_poll = getenv("ZKP_PLONK_NO_POLL") != nullptr;
-    if (!p->h_pin || no_poll) {
+    if (!s.h_pin || no_poll) {
         HIPCHK(hipStreamSynchronize(st));
         return ZKP_OK;
     }
-    unsigned long long* flag = reinterpret_cast<unsigned long long*>(p->h_pin + 4 * (size_t)p->partial_cap);
-    const unsigned long long seq = ++p->poll_seq;
+    unsigned long long* flag = reinterpret_cast<unsigned long long*>(s.h_pin + 4 * (size_t)s.partial_cap);
+    const unsigned long long seq = ++*s.poll_seq;
     hipLaunchKernelGGL(stream_signal_kernel, dim3(1), dim3(1), 0, st, flag, seq);
     HIPCHK(hipGetLastError());
     const auto t0 = std::chrono::steady_clock::now();
@@ -157,7 +171,7 @@ int wait_stream(zkp_plonk_prover* p, hipStream_t st) {
     return ZKP_OK;
 }
 
-int eval_many_dev(zkp_plonk_prover* p, const std::vector<EvalReq>& reqs, hipStream_t st) {
+int eval_many_dev(const PlonkScratch& s, const std::vector<EvalReq>& reqs, hipStream_t st) {
     if (reqs.size() > EVAL_MAX_REQ) return fail(ZKP_E_ARG, "internal: too many evaluation requests");
     EvalParams ep;
     std::memset(&ep, 0, sizeof ep);
@@ -180,18 +194,18 @@ int eval_many_dev(zkp_plonk_prover* p, const std::vector<EvalReq>& reqs, hipStre
         total += blocks[i];
         max_blocks = std::max(max_blocks, blocks[i]);
     }
-    if (total > p->partial_cap) return fail(ZKP_E_ARG, "internal: evaluation scratch too small");
+    if (total > s.partial_cap) return fail(ZKP_E_ARG, "internal: evaluation scratch too small");
     if (max_blocks)
-        hipLaunchKernelGGL(fr_poly_eval_kernel, dim3(max_blocks, (unsigned)reqs.size()), dim3(PK_THREADS), 0, st, ep, p->partial);
+        hipLaunchKernelGGL(fr_poly_eval_kernel, dim3(max_blocks, (unsigned)reqs.size()), dim3(PK_THREADS), 0, st, ep, s.partial);
     HIPCHK(hipGetLastError());
     std::vector<uint64_t> pageable;
-    uint64_t* h = p->h_pin;  // total <= partial_cap
+    uint64_t* h = s.h_pin;  // total <= partial_cap
     if (!h) {  // zkp_kzg_open's borrowed scratch has no pinned buffer
         pageable.resize(4 * (size_t)std::max(total, 1u));
         h = pageable.data();
     }
-    if (total) HIPCHK(hipMemcpyAsync(h, p->partial, 32 * (size_t)total, hipMemcpyDeviceToHost, st));
-    ZCHK(wait_stream(p, st));
+    if (total) HIPCHK(hipMemcpyAsync(h, s.partial, 32 * (size_t)total, hipMemcpyDeviceToHost, st));
+    ZCHK(wait_stream(s, st));
     for (size_t i = 0; i < reqs.size(); i++) {
         HFr acc = HFr::zero();
         for (unsigned b = blocks[i]; b-- > 0;) acc = acc * zblock[i] + HFr::load(&h[4 * (size_t)(ep.part_off[i] + b)]);
@@ -199,8 +213,8 @@ int eval_many_dev(zkp_plonk_prover* p, const std::vector<EvalReq>& reqs, hipStre
     }
     return ZKP_OK;
 }
-int eval_dev(zkp_plonk_prover* p, const Fr* c, uint64_t len, const HFr& z, hipStream_t st, HFr* out) {
-    return eval_many_dev(p, {EvalReq{c, len, z, out}}, st);
+int eval_dev(const PlonkScratch& s, const Fr* c, uint64_t len, const HFr& z, hipStream_t st, HFr* out) {
+    return eval_many_dev(s, {EvalReq{c, len, z, out}}, st);
 }
 
 int trim_len_dev(zkp_plonk_prover* p, const Fr* c, uint64_t n, hipStream_t st, uint64_t* len) {
@@ -208,7 +222,7 @@ int trim_len_dev(zkp_plonk_prover* p, const Fr* c, uint64_t n, hipStream_t st, u
     hipLaunchKernelGGL(fr_trim_len_kernel, dim3((unsigned)((n + PK_THREADS - 1) / PK_THREADS)), dim3(PK_THREADS), 0, st, c, n,
                        p->d_len);
     HIPCHK(hipMemcpyAsync(p->h_pin, p->d_len, 8, hipMemcpyDeviceToHost, st));
-    ZCHK(wait_stream(p, st));
+    ZCHK(wait_stream(p->scratch(), st));
     *len = p->h_pin[0];
     return ZKP_OK;
 }
@@ -228,7 +242,7 @@ ScalePowParams scale_pow_params(const HFr& base, uint64_t e0, uint32_t chunk) {
 // q = (c(X) - c(z)) / (X - z): len - 1 coefficients into `out` (may not alias c), one or two divisions per set of launches (the two
 // opening quotients of round 5 are independent); uses ev[] as scratch (2 len elements per division)
 struct DivReq { const Fr* c; uint64_t len; HFr z; Fr* out; };
-int div_linear_batch_dev(zkp_plonk_prover* p, const DivReq* reqs, int count, hipStream_t st) {
+int div_linear_batch_dev(const PlonkScratch& s, const DivReq* reqs, int count, hipStream_t st) {
     DivReq rq[2];
     int m = 0;
     for (int i = 0; i < count; i++) {
@@ -256,7 +270,7 @@ int div_linear_batch_dev(zkp_plonk_prover* p, const DivReq* reqs, int count, hip
     std::memset(&fwd, 0, sizeof fwd);
     std::memset(&back, 0, sizeof back);
     ScanJob sj[2];
-    Fr* scratch = p->ev;
+    Fr* scratch = s.ev;
     for (int i = 0; i < m; i++) {
         Fr* d = scratch;
         Fr* sfx = scratch + rq[i].len;
@@ -270,14 +284,14 @@ int div_linear_batch_dev(zkp_plonk_prover* p, const DivReq* reqs, int count, hip
     fwd.chunk = back.chunk = chunk;
     const dim3 grid((unsigned)(((nmax + chunk - 1) / chunk + PK_THREADS - 1) / PK_THREADS), (unsigned)m);
     hipLaunchKernelGGL(fr_scale_pow_kernel, grid, dim3(PK_THREADS), 0, st, fwd);
-    ZCHK(run_scan_batch<OpAdd>(p, sj, m, st));
+    ZCHK(run_scan_batch<OpAdd>(s, sj, m, st));
     hipLaunchKernelGGL(fr_scale_pow_kernel, grid, dim3(PK_THREADS), 0, st, back);
     HIPCHK(hipGetLastError());
     return ZKP_OK;
 }
-int div_linear_dev(zkp_plonk_prover* p, const Fr* c, uint64_t len, const HFr& z, Fr* out, hipStream_t st) {
+int div_linear_dev(const PlonkScratch& s, const Fr* c, uint64_t len, const HFr& z, Fr* out, hipStream_t st) {
     const DivReq r{c, len, z, out};
-    return div_linear_batch_dev(p, &r, 1, st);
+    return div_linear_batch_dev(s, &r, 1, st);
 }
 
 struct LcTerm { const Fr* p; uint64_t len; HFr s; };
@@ -317,9 +331,10 @@ int zkp_plonk_prover_create(const zkp_bases* srs, unsigned log_n, const uint64_t
     WsOrder ord(nullptr);
     const uint64_t n = 1ull << log_n;
     if (srs->n < n + 3) return fail(ZKP_E_SIZE, "SRS must hold circuit_size + 3 points (kzg/src/srs.rs:51)");
-    zkp_plonk_prover* p = new (std::nothrow) zkp_plonk_prover();
+    std::unique_ptr<zkp_plonk_prover> p(new (std::nothrow) zkp_plonk_prover());
     if (!p) return fail(ZKP_E_NOMEM, "host allocation failed");
     p->srs = srs;
+    p->device = ctx().device;
     p->log_n = log_n;
     p->n = n;
     p->log_D = log_n + 2;
@@ -328,45 +343,36 @@ int zkp_plonk_prover_create(const zkp_bases* srs, unsigned log_n, const uint64_t
     p->cap = n + 8;
     p->k1 = HFr::load(k1);
     p->k2 = HFr::load(k2);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->circ), 32 * 12 * n);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->work), 32 * 8 * p->cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->t), 32 * std::max<uint64_t>(p->D, 2 * p->cap));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->ev), 32 * 15 * p->D);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->ev_w), 32 * 4 * p->D);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
-    for (hipEvent_t* ev : {&p->ev_fork, &p->ev_abc, &p->ev_z})
-        if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    // (every HIP failure here reports the bare HIP error text)
+    HIPCHK_BARE(p->circ.grow(32 * 12 * n));
+    HIPCHK_BARE(p->work.grow(32 * 8 * p->cap));
+    HIPCHK_BARE(p->t.grow(32 * std::max<uint64_t>(p->D, 2 * p->cap)));
+    HIPCHK_BARE(p->ev.grow(32 * 15 * p->D));
+    HIPCHK_BARE(p->ev_w.grow(32 * 4 * p->D));
+    HIPCHK_BARE(p->side.make(hipStreamNonBlocking));
+    for (Event* ev : {&p->ev_fork, &p->ev_abc, &p->ev_z}) HIPCHK_BARE(ev->make(hipEventDisableTiming));
     p->scan_cap = scan_scratch_elems(p->D);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->scan), 32 * p->scan_cap);
+    HIPCHK_BARE(p->scan.grow(32 * p->scan_cap));
     p->partial_cap = (unsigned)(8 * (p->D / (EVAL_CHUNK * PK_THREADS) + 2));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->partial), 32 * (size_t)p->partial_cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_len), 8);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&p->h_pin), 32 * (size_t)p->partial_cap + 128, hipHostMallocPortable | hipHostMallocMapped);
-    if (e == hipSuccess) p->h_pin[4 * (size_t)p->partial_cap] = 0;
-    if (e == hipSuccess) e = hipMemset(p->circ, 0, 32 * 12 * n);
-    if (e == hipSuccess) e = hipMemset(p->work, 0, 32 * 8 * p->cap);
-    for (int i = 0; i < 12 && e == hipSuccess; i++) {
-        if (lens[i] > n) { zkp_plonk_prover_destroy(p); return fail(ZKP_E_ARG, "circuit polynomial longer than n"); }
-        if (lens[i]) e = hipMemcpy(p->circuit(i), polys[i], 32 * lens[i], hipMemcpyHostToDevice);
+    HIPCHK_BARE(p->partial.grow(32 * (size_t)p->partial_cap));
+    HIPCHK_BARE(p->d_len.grow(8));
+    HIPCHK_BARE(p->h_pin.grow(32 * (size_t)p->partial_cap + 128, hipHostMallocPortable | hipHostMallocMapped));
+    p->h_pin[4 * (size_t)p->partial_cap] = 0;
+    HIPCHK_BARE(hipMemset(p->circ, 0, 32 * 12 * n));
+    HIPCHK_BARE(hipMemset(p->work, 0, 32 * 8 * p->cap));
+    for (int i = 0; i < 12; i++) {
+        if (lens[i] > n) return fail(ZKP_E_ARG, "circuit polynomial longer than n");
+        if (lens[i]) HIPCHK_BARE(hipMemcpy(p->circuit(i), polys[i], 32 * lens[i], hipMemcpyHostToDevice));
     }
-    if (e != hipSuccess) {
-        zkp_plonk_prover_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? ZKP_E_NOMEM : ZKP_E_DEVICE, hipGetErrorString(e));
-    }
-    *out = p;
+    *out = p.release();
     return ZKP_OK;
 } ZKP_CATCH_INT
 
 void zkp_plonk_prover_destroy(zkp_plonk_prover* p) {
     if (!p) return;
     if (p->side) (void)hipStreamSynchronize(p->side);
-    void* bufs[] = {p->circ, p->work, p->t, p->ev, p->ev_w, p->scan, p->partial, p->d_len, p->dom_evals};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (hipEvent_t ev : {p->ev_fork, p->ev_abc, p->ev_z})
-        if (ev) (void)hipEventDestroy(ev);
-    if (p->side) (void)hipStreamDestroy(p->side);
-    if (p->h_pin) (void)hipHostFree(p->h_pin);
+    DeviceRestore restore;
+    (void)hipSetDevice(p->device);
     delete p;
 }
 
@@ -454,8 +460,8 @@ int zkp_plonk_round2(zkp_plonk_prover* p, const uint64_t beta[4], const uint64_t
     // evaluations of f_a f_b f_c s1 s2 s3 on the domain (the reference re-evaluates by Horner at every root).  They depend on
     // the circuit only, not on blinders or challenges: six transforms once per prover, not per proof
     if (!p->dom_evals) {  // published in the prover only once the transforms are enqueued: a failure on the way must not leave
-        Fr* de_new = nullptr;  // a non-null, unfilled cache behind for the next proof
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&de_new), 32 * 12 * n));
+        TypedBuf<Fr> de_new;   // a non-null, unfilled cache behind for the next proof
+        ZCHK(de_new.ensure(32 * 12 * n));
         int rc = ZKP_OK;
         if (hipMemcpyAsync(de_new, p->circ, 32 * 12 * n, hipMemcpyDeviceToDevice, st) != hipSuccess)
             rc = fail(ZKP_E_DEVICE, "copy of the circuit polynomials failed");
@@ -474,12 +480,11 @@ int zkp_plonk_round2(zkp_plonk_prover* p, const uint64_t beta[4], const uint64_t
         // that an early return further down left behind used to switch the gate check of round 3 off (ADVICE r4)
         if (rc == ZKP_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(ZKP_E_DEVICE, "gate check: synchronisation failed");
         if (rc != ZKP_OK) {
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(de_new);
+            (void)hipStreamSynchronize(st);  // before de_new is freed
             return rc;
         }
         p->gate_rows_bad = (int)std::min<uint64_t>(p->h_pin[16], 1u << 30);
-        p->dom_evals = de_new;
+        p->dom_evals = std::move(de_new);
     }
     const Fr* de = p->dom_evals + 6 * n;  // f_a f_b f_c s1 s2 s3
     AccParams ap;
@@ -503,14 +508,14 @@ int zkp_plonk_round2(zkp_plonk_prover* p, const uint64_t beta[4], const uint64_t
     HIPCHK(hipGetLastError());
     {   // prod_{j<i} num_j (acc_e[0] = 1) and prod_{j>=i} den_j in one set of launches
         const ScanJob sj[2] = {{num, nprefix, n, 0u, 1u}, {den, dsuffix, n, 1u, 0u}};
-        ZCHK(run_scan_batch<OpMul>(p, sj, 2, st));
+        ZCHK(run_scan_batch<OpMul>(p->scratch(), sj, 2, st));
     }
     uint64_t* total = p->h_pin;
     // three field elements go home in ONE launch that writes the pinned scratch directly (three device-to-host copies are three
     // blit launches of ~6 us each)
     hipLaunchKernelGGL(fr_gather3_kernel, dim3(1), dim3(64), 0, st, dsuffix, nprefix + (n - 1), num + (n - 1), total);
     HIPCHK(hipGetLastError());
-    ZCHK(wait_stream(p, st));
+    ZCHK(wait_stream(p->scratch(), st));
     // line2 - line3 of the quotient vanishes on the domain by construction of the accumulator everywhere but at the wrap-around
     // row, where it needs prod num_i == prod den_i (the copy constraints hold): the "No remainder" of prover.rs:431
     p->perm_closes = HFr::load(total + 4) * HFr::load(total + 8) == HFr::load(total);
@@ -621,7 +626,7 @@ int zkp_plonk_round4(zkp_plonk_prover* p, const uint64_t zeta[4], uint64_t* out_
     const uint64_t n = p->n;
     p->zeta = HFr::load(zeta);
     const HFr w = fr_root_of_unity(p->log_n);
-    ZCHK(eval_many_dev(p, {{p->poly(P_AX), n + 2, p->zeta, &p->bar[0]}, {p->poly(P_BX), n + 2, p->zeta, &p->bar[1]},
+    ZCHK(eval_many_dev(p->scratch(), {{p->poly(P_AX), n + 2, p->zeta, &p->bar[0]}, {p->poly(P_BX), n + 2, p->zeta, &p->bar[1]},
                            {p->poly(P_CX), n + 2, p->zeta, &p->bar[2]}, {p->circuit(C_S1), n, p->zeta, &p->bar[3]},
                            {p->circuit(C_S2), n, p->zeta, &p->bar[4]}, {p->poly(P_Z), n + 3, p->zeta * w, &p->bar[5]},
                            {p->circuit(C_PI), n, p->zeta, &p->pi_e}}, st));
@@ -674,7 +679,7 @@ int zkp_plonk_round5(zkp_plonk_prover* p, const uint64_t v_limbs[4], uint64_t* o
     // constant term: + pi_e (line1) - (bar_c + gamma) c3 (line3) - c4 (line4's "- 1")
     ZCHK(poke_add(r, 0, p->pi_e - (bc + gamma) * c3 - c4, st));
     HFr bar_r;
-    ZCHK(eval_dev(p, r, p->r_len, zeta, st, &bar_r));
+    ZCHK(eval_dev(p->scratch(), r, p->r_len, zeta, st, &bar_r));
     // w_ev_x (prover.rs:214-229)
     const HFr v2 = v * v, v3 = v2 * v, v4 = v3 * v, v5 = v4 * v;
     std::vector<LcTerm> wt = {{r, p->r_len, HFr::one()}, {p->poly(P_AX), n + 2, v}, {p->poly(P_BX), n + 2, v2},
@@ -689,7 +694,7 @@ int zkp_plonk_round5(zkp_plonk_prover* p, const uint64_t v_limbs[4], uint64_t* o
     ZCHK(poke_add(num2, 0, bzw.neg(), st));
     {
         const DivReq dv[2] = {{num, p->r_len, zeta, p->poly(P_WZ)}, {num2, n + 3, zeta * w, p->poly(P_WZW)}};
-        ZCHK(div_linear_batch_dev(p, dv, 2, st));
+        ZCHK(div_linear_batch_dev(p->scratch(), dv, 2, st));
     }
     p->wzw_len = n + 2;
     if (p->wz_len == p->wzw_len) {
@@ -739,16 +744,12 @@ uint64_t open_scratch_elems(uint64_t len) {
 // y = p(z) and q = (p - y) / (X - z) for `len` >= 1 coefficients resident at d_c: q (len - 1 coefficients) is left at the start of
 // `scratch` (open_scratch_elems(len) elements that do not overlap d_c); *q_out points to it.  Enqueued on `st`; y is read back.
 int open_eval_div_dev(Fr* scratch, const Fr* d_c, uint64_t len, const HFr& z, hipStream_t st, HFr* y, Fr** q_out) {
-    zkp_plonk_prover w;  // only its scratch pointers are used by the helpers
     const uint64_t n_tot = scan_scratch_elems(len);
-    w.partial_cap = (unsigned)(len / (EVAL_CHUNK * PK_THREADS) + 2);
     Fr* d_q = scratch;
-    w.ev = d_q + len;
-    w.scan = w.ev + 2 * len;
-    w.scan_cap = n_tot;
-    w.partial = w.scan + n_tot;
-    ZCHK(eval_dev(&w, d_c, len, z, st, y));
-    if (len > 1) ZCHK(div_linear_dev(&w, d_c, len, z, d_q, st));
+    Fr* ev = d_q + len;
+    const PlonkScratch w{ev, ev + 2 * len, n_tot, ev + 2 * len + n_tot, (unsigned)(len / (EVAL_CHUNK * PK_THREADS) + 2), nullptr, nullptr};
+    ZCHK(eval_dev(w, d_c, len, z, st, y));
+    if (len > 1) ZCHK(div_linear_dev(w, d_c, len, z, d_q, st));
     *q_out = d_q;
     return ZKP_OK;
 }
@@ -807,7 +808,7 @@ int build_para_table(zkp_plonk_prover* p) {
         CTX_ENTER(p->srs->slot);
         WsOrder ord(nullptr);
         if (!p->srs->n) return fail(ZKP_E_SIZE, "empty SRS (unwrap() at kzg/src/scheme.rs:79)");
-        HIPCHK(hipMemcpy(raw, p->srs->d_xy, 128, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(raw, p->srs->d_xy.p, 128, hipMemcpyDeviceToHost));
     }
     HXyzz base{fq_from_limbs28(raw), fq_from_limbs28(raw + 16), HFq::one(), HFq::one()};
     p->para_table.resize(64 * 15);
@@ -886,7 +887,7 @@ void batch_to_affine(const HXyzz* pts, size_t count, uint64_t* out_xy /* count x
 
 extern "C" int zkp_plonk_prove(zkp_plonk_prover* p, const uint64_t* blinders /* b1..b9, 9 x 4 limbs */, zkp_plonk_proof* out) try {
     if (!p || !blinders || !out) return fail(ZKP_E_ARG, "null argument");
-    if (p->srs->d_inf) return fail(ZKP_E_ARG, "SRS with infinity points");
+    if (p->srs->d_inf.p) return fail(ZKP_E_ARG, "SRS with infinity points");
     if (p->para_table.empty()) ZCHK(build_para_table(p));
     std::memset(out, 0, sizeof *out);
     PlonkChallengeGenerator ch;

@@ -209,7 +209,7 @@ int zkp_plonk_verify(zkp_plonk_prover* p, const uint64_t g2s_xy[24], const zkp_p
     {
         CTX_ENTER(p->srs->slot);
         WsOrder ord(nullptr);
-        ZCHK(eval_dev(p, p->circuit(C_PI), n, zeta, nullptr, &pi_e));
+        ZCHK(eval_dev(p->scratch(), p->circuit(C_PI), n, zeta, nullptr, &pi_e));
     }
     const HFr one = HFr::one(), w = fr_root_of_unity(p->log_n);
     const HFr z_h_e = zeta.pow_u64(n) - one;                                  // verifier.rs:43
