@@ -35,7 +35,9 @@
  * than this many bytes -- it is also refused when it exceeds the device's free memory; the handle then stays usable unexpanded),
  * ZKP_MSM_BALANCE_FROM (overshoot in bits from which the slices of an expansion are balanced, default 1 = always; tuning aid),
  * ZKP_PYR_TAIL_THREADS / ZKP_PYR_TAIL_BLOCKS / ZKP_PYR_TAIL_HALF (geometry of the launch that runs the last levels of the bucket reduction:
- * workgroup size 64..512, workgroups per bucket set 1..256, pairs per array from which it takes over; defaults 256 / 16 / 64; tuning aids).
+ * workgroup size 64..512, workgroups per bucket set 1..256, pairs per array from which it takes over; defaults 256 / 16 / 64; tuning aids),
+ * ZKP_FRI_FR_TAIL_LOG (0..10: log2 of the largest layer zkp_fri_prove_fr runs in its one-workgroup tail kernel, default 9, 0 = none;
+ * tuning aid).
  */
 #ifndef ZKP_HIP_H
 #define ZKP_HIP_H
@@ -318,6 +320,35 @@ int zkp_fri_prove(const uint64_t *coeffs, size_t d, size_t blowup_factor, size_t
  * reference's error string ("wrong index!", "verify Merkle path failed!", "folding wrong!") in zkp_last_error(). */
 int zkp_fri_verify(const uint64_t *proof, size_t words);
 void zkp_free(void *p);
+
+/* ---- FRI over the BLS12-381 scalar field Fr (fri/src is generic over F: PrimeField; kzg::types::ScalarField) ----
+ * Field elements are Fr memory form: uint64_t[4] Montgomery residues, as zkp_ntt_fr.  Same objects as the Goldilocks
+ * entries above: Display is the canonical integer in decimal (up to 77 digits, zero prints as ""; ZKP_FRI_ZERO_AS_0=1
+ * switches to "0" here too), a digest is reduced mod r as a 256-bit little-endian integer, F::GENERATOR = 7.
+ * Node counts come from zkp_fri_merkle_node_count (elements, 4 words each).  zkp_fri_prove_fr runs the layers of at most 512
+ * points in one workgroup (ZKP_FRI_FR_TAIL_LOG=0..10 moves that threshold for measurements; 0 = none); its phases are recorded
+ * as "fri_merkle", "ntt_fr_pass", "fri_fold", "fri_transcript", "fri_tail" and "fri_gather". */
+/* evals[i] = poly(coset * omega_D^i), i < D = 2^log_D (fri_layer.rs:40-46); coeffs d x 4 words, d <= D; out D x 4 words. */
+int zkp_fri_layer_eval_fr(const uint64_t *coeffs, size_t d, const uint64_t coset[4], unsigned log_D, uint64_t *out);
+/* fold_polynomial, fri/src/prover.rs:34-42: out[j] = c[2j] + r*c[2j+1]; out has ceil(d/2) elements. */
+int zkp_fri_fold_fr(const uint64_t *coeffs, size_t d, const uint64_t r[4], uint64_t *out);
+int zkp_fri_merkle_tree_fr(const uint64_t *leaves, size_t n, uint64_t *nodes_out);
+int zkp_fri_merkle_tree_fr_dev(const void *d_leaves, size_t n, void *d_nodes, void *stream);
+/* Transcript replay over Fr: r_out = layers x 4 words (memory form), q_out[i] = the i-th query challenge as usize (the low
+ * limb of its canonical value, before % domain).  Host only. */
+int zkp_fri_challenges_fr(const uint64_t *roots, size_t layers, const uint64_t const_val[4], size_t num_queries, uint64_t *r_out,
+                          uint64_t *q_out);
+/* generate_proof over Fr.  *out_proof is a malloc'ed flat proof of *out_words words, layout:
+ *   [0] domain_size [1] layers = log2(domain_size) [2] number_of_queries
+ *   then 4-word fields: coset (memory form of 7), layers_root[layers], const_val
+ *   then per query, per layer l: index (1 word), evaluation (4), sym_evaluation (4),
+ *   auth path (log2(domain_size >> l) sibling hashes from the leaf level up, 4 words each), sym auth path (same length).
+ * Release with zkp_free.  A zero polynomial (after trimming trailing zeros) or blowup_factor == 0 is ZKP_E_ARG; a domain
+ * above 2^32 (the two-adicity of Fr) is ZKP_E_SIZE. */
+int zkp_fri_prove_fr(const uint64_t *coeffs, size_t d, size_t blowup_factor, size_t num_queries, uint64_t **out_proof,
+                     size_t *out_words);
+/* verify over Fr on the flat proof (host only); ZKP_OK = accepted, ZKP_E_ARG otherwise with the reference's error string. */
+int zkp_fri_verify_fr(const uint64_t *proof, size_t words);
 
 /* ---- ChallengeGenerator<Sha256>, plonk/src/challenge.rs:22-77 (host): feed commitments (serialize_uncompressed, 96
  *      bytes), then draw Fr challenges (memory form, n x 4 limbs) through StdRng::seed_from_u64 + Fr::rand.  Drawing twice

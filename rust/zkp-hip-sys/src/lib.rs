@@ -141,6 +141,13 @@ extern "C" {
     pub fn zkp_fri_prove(coeffs: *const u64, d: usize, blowup_factor: usize, num_queries: usize, out_proof: *mut *mut u64, out_words: *mut usize) -> i32;
     pub fn zkp_fri_verify(proof: *const u64, words: usize) -> i32;
     pub fn zkp_free(p: *mut c_void);
+    pub fn zkp_fri_layer_eval_fr(coeffs: *const u64, d: usize, coset: *const u64, log_D: u32, out: *mut u64) -> i32;
+    pub fn zkp_fri_fold_fr(coeffs: *const u64, d: usize, r: *const u64, out: *mut u64) -> i32;
+    pub fn zkp_fri_merkle_tree_fr(leaves: *const u64, n: usize, nodes_out: *mut u64) -> i32;
+    pub fn zkp_fri_merkle_tree_fr_dev(d_leaves: *const c_void, n: usize, d_nodes: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_fri_challenges_fr(roots: *const u64, layers: usize, const_val: *const u64, num_queries: usize, r_out: *mut u64, q_out: *mut u64) -> i32;
+    pub fn zkp_fri_prove_fr(coeffs: *const u64, d: usize, blowup_factor: usize, num_queries: usize, out_proof: *mut *mut u64, out_words: *mut usize) -> i32;
+    pub fn zkp_fri_verify_fr(proof: *const u64, words: usize) -> i32;
     pub fn zkp_plonk_transcript_create(out: *mut *mut zkp_plonk_transcript) -> i32;
     pub fn zkp_plonk_transcript_destroy(t: *mut zkp_plonk_transcript);
     pub fn zkp_plonk_transcript_feed(t: *mut zkp_plonk_transcript, xy: *const u64, is_inf: u8) -> i32;

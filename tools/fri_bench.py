@@ -1,4 +1,5 @@
-"""FRI generate_proof timing: python3 tools/fri_bench.py [LOG_D_COEFFS] [BLOWUP] [QUERIES]"""
+"""FRI generate_proof timing: python3 tools/fri_bench.py [LOG_D_COEFFS] [BLOWUP] [QUERIES] [--field gl|fr]
+(default Goldilocks; --field fr times the BLS12-381 Fr path: best / median of warm calls, phases, verify, the 2^(LOG_D+1)-leaf tree)"""
 import os
 import sys
 import time
@@ -9,10 +10,58 @@ import numpy as np
 import torch
 import zkp_hip as zkp
 
+field = "gl"
+if "--field" in sys.argv:
+    i = sys.argv.index("--field")
+    field = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 ld = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 blow = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 nq = int(sys.argv[3]) if len(sys.argv) > 3 else 32
 zkp.init()
+
+
+def bench_fr():
+    rnd = np.random.default_rng(1)
+    coeffs = rnd.integers(0, 2 ** 63, (1 << ld, 4), dtype=np.uint64)
+    coeffs[:, 3] %= np.uint64(0x73eda753299d7d48)  # < r
+    zkp.fri_prove_fr(coeffs, blow, nq)  # warm-up
+    times = []
+    for rep in range(6):
+        zkp.profile_reset()
+        zkp.profile_enable(rep == 5)
+        t0 = time.perf_counter()
+        proof = zkp.fri_prove_fr(coeffs, blow, nq)
+        times.append(time.perf_counter() - t0)
+        zkp.profile_enable(False)
+    ph = {k: zkp.profile_read(k) for k in ("fri_merkle", "ntt_fr_pass", "fri_fold", "fri_transcript", "fri_tail", "fri_gather")}
+    _, mhz, _ = zkp.probe_mad_rate(5)  # shader clock right after the timed calls
+    warm = sorted(times[:5])
+    print(f"fri_prove_fr 2^{ld} coeffs x{blow} q{nq}: best {warm[0] * 1e3:.2f} ms, median {warm[2] * 1e3:.2f} ms (5 warm calls), "
+          f"profiled call {times[5] * 1e3:.2f} ms, proof {proof.size * 8 / 1024:.1f} KiB, clock {mhz:.0f} MHz, phases (ms, records) {ph}")
+    t0 = time.perf_counter()
+    ok = zkp.fri_verify_fr(proof)
+    print("verify_fr", ok, f"{(time.perf_counter() - t0) * 1e3:.2f} ms")
+    n = 1 << (ld + 1)
+    d_leaves = torch.from_numpy(np.ascontiguousarray(rnd.integers(0, 2 ** 63, (n, 4), dtype=np.uint64) >> np.uint64(2)).view(np.int64)).cuda()
+    d_nodes = torch.zeros(zkp.fri_merkle_node_count(n) * 4, dtype=torch.int64, device="cuda")
+    for _ in range(2):
+        zkp.fri_merkle_tree_fr_dev(d_leaves, n, d_nodes)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        zkp.fri_merkle_tree_fr_dev(d_leaves, n, d_nodes)
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    ts.sort()
+    print(f"merkle tree fr 2^{ld + 1} leaves: best {ts[0] * 1e3:.3f} ms, median {ts[2] * 1e3:.3f} ms = "
+          f"{(2 * n - 1) / ts[0] / 1e9:.3f} G hashes/s")
+
+
+if field == "fr":
+    bench_fr()
+    sys.exit(0)
 rnd = np.random.default_rng(1)
 coeffs = rnd.integers(1, 2 ** 63, 1 << ld, dtype=np.uint64)
 for rep in range(3):

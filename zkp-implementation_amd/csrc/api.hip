@@ -1942,3 +1942,6 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "fri_host.inc"
 #include "verify_host.inc"
 #include "nova_host.inc"
+// FRI over Fr last: its kernels follow every other kernel in the code object
+#include "fri_fr.hpp"
+#include "fri_fr_host.inc"

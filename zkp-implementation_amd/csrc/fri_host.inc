@@ -80,9 +80,87 @@ uint64_t host_hash_slice(const uint64_t* canon, size_t n, bool z0) {
     return (uint64_t)acc;
 }
 
-size_t fri_proof_words(size_t domain_size, size_t nq) {
+// The field-specific parts of the FRI proof shape and verifier (fri/src is generic over F: PrimeField): W words per element,
+// the host field type, canonical values, hash / hash_slice, roots of unity and the transcript replay.  Goldilocks here, Fr in
+// fri_fr_host.inc (FriFrTraits).
+struct FriGlTraits {
+    static constexpr size_t W = 1;
+    typedef HGl H;
+    typedef std::array<uint64_t, 1> C;
+    static C canon(const uint64_t* mont) { return C{gl_canon(*mont)}; }
+    static C hash(const C* in, size_t n, bool z0) {
+        uint64_t v[2] = {in[0][0], n > 1 ? in[1][0] : 0};
+        return C{host_hash_slice(v, n, z0)};
+    }
+    static H root(unsigned log_n) { return gl_root_of_unity(log_n); }
+    static int challenges(const uint64_t* roots, size_t L, const uint64_t* cst, size_t nq, uint64_t* r, uint64_t* q) {
+        return zkp_fri_challenges(roots, L, *cst, nq, r, q);
+    }
+};
+
+// Flat proof length: [0] D [1] L [2] nq, W-word coset, roots[L], const_val, then per query and layer l
+// index + evaluation + sym_evaluation + 2 depth_l path nodes
+template <class T>
+size_t fri_proof_words_t(size_t domain_size, size_t nq) {
     const size_t L = merkle_depth(domain_size);
-    return 4 + L + 1 + nq * (3 * L + L * (L + 1));
+    return 3 + T::W * (L + 2) + nq * (L * (1 + 2 * T::W) + T::W * L * (L + 1));
+}
+size_t fri_proof_words(size_t domain_size, size_t nq) { return fri_proof_words_t<FriGlTraits>(domain_size, nq); }
+
+// fri/src/verifier.rs:10-127 on the flat proof of either field.  ZKP_OK = accepted; ZKP_E_ARG with the reference's error
+// string otherwise.
+template <class T>
+int fri_verify_t(const uint64_t* proof, size_t words) {
+    typedef typename T::H H;
+    typedef typename T::C C;
+    constexpr size_t W = T::W;
+    if (!proof || words < 3 + 2 * W) return fail(ZKP_E_ARG, "malformed proof");
+    const size_t D = proof[0], L = proof[1], nq = proof[2];
+    if (D == 0 || (D & (D - 1)) || merkle_depth(D) != L || L > 32 || words != fri_proof_words_t<T>(D, nq))
+        return fail(ZKP_E_ARG, "malformed proof");
+    const bool z0 = fri_zero_as_0();
+    const uint64_t* roots = proof + 3 + W;
+    const uint64_t* cst_p = roots + W * L;
+    std::vector<uint64_t> r(W * L), qs(nq);
+    ZCHK(T::challenges(roots, L, cst_p, nq, r.data(), qs.data()));
+    const H cst = H::load(cst_p);
+    const H two_inv = H::from_u64(2).inverse();
+    const uint64_t* p = cst_p + W;
+    for (size_t q = 0; q < nq && L; q++) {
+        const size_t ch = qs[q] % D;
+        H coset = H::load(proof + 3);
+        size_t ds = D;
+        for (size_t l = 0; l < L; l++, ds /= 2) {  // verify_query, verifier.rs:49-121
+            const size_t idx = ch % ds, sym = (idx + ds / 2) % ds, depth = L - l;
+            const uint64_t* rec = p;
+            p += 1 + W * (2 + 2 * depth);
+            if (rec[0] != idx) return fail(ZKP_E_ARG, "wrong index!");
+            const C want_root = T::canon(roots + W * l);
+            for (int pass = 0; pass < 2; pass++) {  // verify_merkle_proof, merkle_tree.rs:119-135
+                size_t c = pass ? sym : idx;
+                C pair[2];
+                pair[0] = T::canon(rec + 1 + W * pass);
+                C h = T::hash(pair, 1, z0);
+                const uint64_t* path = rec + 1 + W * (2 + pass * depth);
+                for (size_t i = 0; i < depth; i++) {
+                    pair[c & 1] = h;
+                    pair[1 - (c & 1)] = T::canon(path + W * i);
+                    h = T::hash(pair, 2, z0);
+                    c /= 2;
+                }
+                if (h != want_root) return fail(ZKP_E_ARG, "verify Merkle path failed!");
+            }
+            // q_fold = (r + w) e / (2 w) - (r - w) s / (2 w),  w = omega_ds^idx * coset (verifier.rs:96-101)
+            const H w = T::root((unsigned)depth).pow_u64(idx) * coset;
+            const H rl = H::load(&r[W * l]), e = H::load(rec + 1), s = H::load(rec + 1 + W);
+            const H i2w = two_inv * w.inverse();
+            const H qf = (rl + w) * e * i2w - (rl - w) * s * i2w;
+            const H expect = l + 1 < L ? H::load(p + 1) : cst;  // next layer's evaluation of this query, or const_val
+            if (!(qf == expect)) return fail(ZKP_E_ARG, "folding wrong!");
+            coset = coset * coset;
+        }
+    }
+    return ZKP_OK;
 }
 
 }  // namespace
@@ -309,52 +387,7 @@ int zkp_fri_prove(const uint64_t* coeffs, size_t d, size_t blowup, size_t num_qu
 
 // fri/src/verifier.rs:10-127.  ZKP_OK = accepted; ZKP_E_ARG with the reference's error string otherwise.
 int zkp_fri_verify(const uint64_t* proof, size_t words) try {
-    if (!proof || words < 5) return fail(ZKP_E_ARG, "malformed proof");
-    const size_t D = proof[0], L = proof[1], nq = proof[2];
-    if (D == 0 || (D & (D - 1)) || merkle_depth(D) != L || L > 32 || words != fri_proof_words(D, nq))
-        return fail(ZKP_E_ARG, "malformed proof");
-    const bool z0 = fri_zero_as_0();
-    std::vector<uint64_t> r(L), qs(nq);
-    ZCHK(zkp_fri_challenges(proof + 4, L, proof[4 + L], nq, r.data(), qs.data()));
-    const HGl cst = HGl::load(&proof[4 + L]);
-    const HGl two_inv = HGl::from_u64(2).inverse();
-    const uint64_t* p = proof + 4 + L + 1;
-    for (size_t q = 0; q < nq && L; q++) {
-        const size_t ch = qs[q] % D;
-        HGl coset = HGl::load(&proof[3]);
-        size_t ds = D;
-        for (size_t l = 0; l < L; l++, ds /= 2) {  // verify_query, verifier.rs:49-121
-            const size_t idx = ch % ds, sym = (idx + ds / 2) % ds, depth = L - l;
-            const uint64_t* rec = p;
-            p += 3 + 2 * depth;
-            if (rec[0] != idx) return fail(ZKP_E_ARG, "wrong index!");
-            const uint64_t want_root = gl_canon(proof[4 + l]);
-            for (int pass = 0; pass < 2; pass++) {  // verify_merkle_proof, merkle_tree.rs:119-135
-                size_t c = pass ? sym : idx;
-                uint64_t leaf = gl_canon(rec[1 + pass]);
-                uint64_t h = host_hash_slice(&leaf, 1, z0);
-                const uint64_t* path = rec + 3 + pass * depth;
-                for (size_t i = 0; i < depth; i++) {
-                    uint64_t pair[2];
-                    const uint64_t nb = gl_canon(path[i]);
-                    pair[c & 1] = h;
-                    pair[1 - (c & 1)] = nb;
-                    h = host_hash_slice(pair, 2, z0);
-                    c /= 2;
-                }
-                if (h != want_root) return fail(ZKP_E_ARG, "verify Merkle path failed!");
-            }
-            // q_fold = (r + w) e / (2 w) - (r - w) s / (2 w),  w = omega_ds^idx * coset (verifier.rs:96-101)
-            const HGl w = gl_root_of_unity((unsigned)depth).pow_u64(idx) * coset;
-            const HGl rl = HGl::load(&r[l]), e = HGl::load(&rec[1]), s = HGl::load(&rec[2]);
-            const HGl i2w = two_inv * w.inverse();
-            const HGl qf = (rl + w) * e * i2w - (rl - w) * s * i2w;
-            const HGl expect = l + 1 < L ? HGl::load(&p[1]) : cst;  // next layer's evaluation of this query, or const_val
-            if (!(qf == expect)) return fail(ZKP_E_ARG, "folding wrong!");
-            coset = coset * coset;
-        }
-    }
-    return ZKP_OK;
+    return fri_verify_t<FriGlTraits>(proof, words);
 } ZKP_CATCH_INT
 
 // ---- plonk/src/challenge.rs ------------------------------------------------------------------------

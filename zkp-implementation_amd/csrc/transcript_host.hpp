@@ -185,17 +185,38 @@ inline std::string goldilocks_display(uint64_t canonical, bool zero_as_0) {
     return std::to_string(canonical);
 }
 
+// Display of a BLS12-381 Fr element given its canonical value (4 little-endian u64 limbs): base-10^19 chunks
+inline std::string fr_display(const uint64_t canonical[4], bool zero_as_0) {
+    uint64_t t[4] = {canonical[0], canonical[1], canonical[2], canonical[3]};
+    std::string digits;  // least significant first
+    for (;;) {
+        unsigned __int128 rem = 0;
+        bool nonzero = false;
+        for (int i = 3; i >= 0; i--) {
+            const unsigned __int128 cur = rem << 64 | t[i];
+            t[i] = (uint64_t)(cur / 10000000000000000000ull);
+            rem = cur % 10000000000000000000ull;
+            nonzero |= t[i] != 0;
+        }
+        uint64_t r = (uint64_t)rem;
+        for (int k = 0; k < 19 && (nonzero || r); k++, r /= 10) digits.push_back(static_cast<char>('0' + r % 10));
+        if (!nonzero) break;
+    }
+    if (digits.empty()) return zero_as_0 ? "0" : "";
+    return std::string(digits.rbegin(), digits.rend());
+}
+
 // fri/src/fiat_shamir/transcript.rs
 class FriTranscript {
 public:
     explicit FriTranscript(bool zero_as_0) : zero_as_0_(zero_as_0) { digest(0); }  // Transcript::new(F::ZERO)
-    void digest(uint64_t canonical) {  // transcript.rs:64-72
+    void digest(uint64_t canonical) { digest_display(goldilocks_display(canonical, zero_as_0_)); }  // Goldilocks
+    void digest_display(const std::string& s) {  // transcript.rs:64-72, any field: s = Display(message)
         Sha256 h;
         if (has_data_) h.update(data_.data(), 32);
         uint8_t le[8];
         for (int i = 0; i < 8; i++) le[i] = static_cast<uint8_t>(index_ >> (8 * i));
         h.update(le, 8);
-        const std::string s = goldilocks_display(canonical, zero_as_0_);
         h.update(s.data(), s.size());
         data_ = h.finish();
         has_data_ = true;

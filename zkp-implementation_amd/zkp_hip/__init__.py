@@ -82,6 +82,13 @@ _SIGS = {
     "zkp_fri_challenges": ([_VP, _SZ, C.c_uint64, _SZ, _VP, _VP], C.c_int),
     "zkp_fri_prove": ([_VP, _SZ, _SZ, _SZ, C.POINTER(_VP), C.POINTER(_SZ)], C.c_int),
     "zkp_fri_verify": ([_VP, _SZ], C.c_int),
+    "zkp_fri_layer_eval_fr": ([_VP, _SZ, _VP, C.c_uint, _VP], C.c_int),
+    "zkp_fri_fold_fr": ([_VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_fri_merkle_tree_fr": ([_VP, _SZ, _VP], C.c_int),
+    "zkp_fri_merkle_tree_fr_dev": ([_VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_fri_challenges_fr": ([_VP, _SZ, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_fri_prove_fr": ([_VP, _SZ, _SZ, _SZ, C.POINTER(_VP), C.POINTER(_SZ)], C.c_int),
+    "zkp_fri_verify_fr": ([_VP, _SZ], C.c_int),
     "zkp_free": ([_VP], None),
     "zkp_plonk_prove": ([_VP, _VP, _VP], C.c_int),
     "zkp_g2_generator": ([_VP], C.c_int),
@@ -560,6 +567,64 @@ def fri_verify(proof):
     """verify (fri/src/verifier.rs:10-127): True, or raises ZkpError carrying the reference's error string."""
     proof = _np(proof, np.uint64).reshape(-1)
     _chk(lib().zkp_fri_verify(_ptr(proof), proof.size))
+    return True
+
+
+# ----------------------------------------------------------------------------- FRI over Fr: (n, 4) uint64 memory-form arrays
+def fri_layer_eval_fr(coeffs, coset, log_d):
+    """FriLayer::from_poly evaluations over Fr; coset is a Montgomery-form (4,) uint64 array."""
+    coeffs = _np(coeffs, np.uint64, (-1, 4))
+    cs = _np(coset, np.uint64, (4,))
+    out = np.zeros((1 << log_d, 4), dtype=np.uint64)
+    _chk(lib().zkp_fri_layer_eval_fr(_ptr(coeffs), coeffs.shape[0], _ptr(cs), log_d, _ptr(out)))
+    return out
+
+
+def fri_fold_fr(coeffs, r):
+    coeffs = _np(coeffs, np.uint64, (-1, 4))
+    rr = _np(r, np.uint64, (4,))
+    out = np.zeros(((coeffs.shape[0] + 1) // 2, 4), dtype=np.uint64)
+    _chk(lib().zkp_fri_fold_fr(_ptr(coeffs), coeffs.shape[0], _ptr(rr), _ptr(out)))
+    return out
+
+
+def fri_merkle_tree_fr(leaves):
+    """MerkleTree::new over Fr: every level, concatenated, as (zkp_fri_merkle_node_count(n), 4); the root is the last row."""
+    leaves = _np(leaves, np.uint64, (-1, 4))
+    out = np.zeros((fri_merkle_node_count(leaves.shape[0]), 4), dtype=np.uint64)
+    _chk(lib().zkp_fri_merkle_tree_fr(_ptr(leaves), leaves.shape[0], _ptr(out)))
+    return out
+
+
+def fri_merkle_tree_fr_dev(leaves_tensor, n, nodes_tensor, stream=None):
+    _chk(lib().zkp_fri_merkle_tree_fr_dev(_dev_ptr(leaves_tensor, 32 * n), n,
+                                          _dev_ptr(nodes_tensor, 32 * fri_merkle_node_count(n)), _stream_ptr(stream)))
+
+
+def fri_challenges_fr(roots, const_val, num_queries):
+    roots = _np(roots, np.uint64, (-1, 4))
+    cv = _np(const_val, np.uint64, (4,))
+    r_out = np.zeros((roots.shape[0], 4), dtype=np.uint64)
+    q_out = np.zeros(num_queries, dtype=np.uint64)
+    _chk(lib().zkp_fri_challenges_fr(_ptr(roots), roots.shape[0], _ptr(cv), num_queries, _ptr(r_out), _ptr(q_out)))
+    return r_out, q_out
+
+
+def fri_prove_fr(coeffs, blowup_factor, num_queries):
+    """generate_proof over Fr -> flat uint64 proof (layout in include/zkp_hip.h)."""
+    coeffs = _np(coeffs, np.uint64, (-1, 4))
+    p, words = C.c_void_p(), C.c_size_t()
+    _chk(lib().zkp_fri_prove_fr(_ptr(coeffs), coeffs.shape[0], blowup_factor, num_queries, C.byref(p), C.byref(words)))
+    try:
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(words.value,)).copy()
+    finally:
+        lib().zkp_free(p)
+
+
+def fri_verify_fr(proof):
+    """verify over Fr: True, or raises ZkpError carrying the reference's error string."""
+    proof = _np(proof, np.uint64).reshape(-1)
+    _chk(lib().zkp_fri_verify_fr(_ptr(proof), proof.size))
     return True
 
 
