@@ -1,5 +1,7 @@
 """FRI generate_proof timing: python3 tools/fri_bench.py [LOG_D_COEFFS] [BLOWUP] [QUERIES] [--field gl|fr]
-(default Goldilocks; --field fr times the BLS12-381 Fr path: best / median of warm calls, phases, verify, the 2^(LOG_D+1)-leaf tree)"""
+(default Goldilocks; for either field: best / median of five warm calls with profiling off, one profiled call with its phases,
+the SHA-256 of the proof words, verify, and the 2^(LOG_D+1)-leaf Merkle tree)"""
+import hashlib
 import os
 import sys
 import time
@@ -20,71 +22,49 @@ blow = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 nq = int(sys.argv[3]) if len(sys.argv) > 3 else 32
 zkp.init()
 
-
-def bench_fr():
-    rnd = np.random.default_rng(1)
+rnd = np.random.default_rng(1)
+if field == "fr":
+    W, suffix, prove, verify, tree = 4, "_fr", zkp.fri_prove_fr, zkp.fri_verify_fr, zkp.fri_merkle_tree_fr_dev
+    phases = ("fri_merkle", "ntt_fr_pass", "fri_fold", "fri_transcript", "fri_tail", "fri_gather")
     coeffs = rnd.integers(0, 2 ** 63, (1 << ld, 4), dtype=np.uint64)
     coeffs[:, 3] %= np.uint64(0x73eda753299d7d48)  # < r
-    zkp.fri_prove_fr(coeffs, blow, nq)  # warm-up
-    times = []
-    for rep in range(6):
-        zkp.profile_reset()
-        zkp.profile_enable(rep == 5)
-        t0 = time.perf_counter()
-        proof = zkp.fri_prove_fr(coeffs, blow, nq)
-        times.append(time.perf_counter() - t0)
-        zkp.profile_enable(False)
-    ph = {k: zkp.profile_read(k) for k in ("fri_merkle", "ntt_fr_pass", "fri_fold", "fri_transcript", "fri_tail", "fri_gather")}
-    _, mhz, _ = zkp.probe_mad_rate(5)  # shader clock right after the timed calls
-    warm = sorted(times[:5])
-    print(f"fri_prove_fr 2^{ld} coeffs x{blow} q{nq}: best {warm[0] * 1e3:.2f} ms, median {warm[2] * 1e3:.2f} ms (5 warm calls), "
-          f"profiled call {times[5] * 1e3:.2f} ms, proof {proof.size * 8 / 1024:.1f} KiB, clock {mhz:.0f} MHz, phases (ms, records) {ph}")
-    t0 = time.perf_counter()
-    ok = zkp.fri_verify_fr(proof)
-    print("verify_fr", ok, f"{(time.perf_counter() - t0) * 1e3:.2f} ms")
-    n = 1 << (ld + 1)
-    d_leaves = torch.from_numpy(np.ascontiguousarray(rnd.integers(0, 2 ** 63, (n, 4), dtype=np.uint64) >> np.uint64(2)).view(np.int64)).cuda()
-    d_nodes = torch.zeros(zkp.fri_merkle_node_count(n) * 4, dtype=torch.int64, device="cuda")
-    for _ in range(2):
-        zkp.fri_merkle_tree_fr_dev(d_leaves, n, d_nodes)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        zkp.fri_merkle_tree_fr_dev(d_leaves, n, d_nodes)
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    ts.sort()
-    print(f"merkle tree fr 2^{ld + 1} leaves: best {ts[0] * 1e3:.3f} ms, median {ts[2] * 1e3:.3f} ms = "
-          f"{(2 * n - 1) / ts[0] / 1e9:.3f} G hashes/s")
+    leaves = rnd.integers(0, 2 ** 63, (1 << (ld + 1), 4), dtype=np.uint64) >> np.uint64(2)
+else:
+    W, suffix, prove, verify, tree = 1, "", zkp.fri_prove, zkp.fri_verify, zkp.fri_merkle_tree_dev
+    phases = ("fri_merkle", "ntt_gl_pass")  # the driver's own phases are not recorded for this field
+    coeffs = rnd.integers(1, 2 ** 63, 1 << ld, dtype=np.uint64)
+    leaves = rnd.integers(0, 2 ** 62, 1 << (ld + 1), dtype=np.uint64)
 
-
-if field == "fr":
-    bench_fr()
-    sys.exit(0)
-rnd = np.random.default_rng(1)
-coeffs = rnd.integers(1, 2 ** 63, 1 << ld, dtype=np.uint64)
-for rep in range(3):
+prove(coeffs, blow, nq)  # warm-up
+times = []
+for rep in range(6):
     zkp.profile_reset()
-    zkp.profile_enable(True)
+    zkp.profile_enable(rep == 5)
     t0 = time.perf_counter()
-    proof = zkp.fri_prove(coeffs, blow, nq)
-    dt = time.perf_counter() - t0
+    proof = prove(coeffs, blow, nq)
+    times.append(time.perf_counter() - t0)
     zkp.profile_enable(False)
-    ph = {k: zkp.profile_read(k) for k in ("fri_merkle", "ntt_gl_pass")}
-    print(f"fri_prove 2^{ld} coeffs x{blow}: {dt * 1e3:.2f} ms, proof {proof.size * 8 / 1024:.1f} KiB, phases {ph}")
+ph = {k: zkp.profile_read(k) for k in phases}
+_, mhz, _ = zkp.probe_mad_rate(5)  # shader clock right after the timed calls
+warm = sorted(times[:5])
+print(f"fri_prove{suffix} 2^{ld} coeffs x{blow} q{nq}: best {warm[0] * 1e3:.2f} ms, median {warm[2] * 1e3:.2f} ms (5 warm calls), "
+      f"profiled call {times[5] * 1e3:.2f} ms, proof {proof.size * 8 / 1024:.1f} KiB, clock {mhz:.0f} MHz, phases (ms, records) {ph}")
+print(f"proof{suffix} sha256 {hashlib.sha256(np.ascontiguousarray(proof).tobytes()).hexdigest()}")
 t0 = time.perf_counter()
-ok = zkp.fri_verify(proof)
-print("verify", ok, f"{(time.perf_counter() - t0) * 1e3:.2f} ms")
+ok = verify(proof)
+print(f"verify{suffix}", ok, f"{(time.perf_counter() - t0) * 1e3:.2f} ms")
 n = 1 << (ld + 1)
-d_leaves = torch.randint(0, 2 ** 62, (n,), dtype=torch.int64, device="cuda")
-d_nodes = torch.zeros(zkp.fri_merkle_node_count(n), dtype=torch.int64, device="cuda")
+d_leaves = torch.from_numpy(np.ascontiguousarray(leaves).view(np.int64)).cuda()
+d_nodes = torch.zeros(zkp.fri_merkle_node_count(n) * W, dtype=torch.int64, device="cuda")
 for _ in range(2):
-    zkp.fri_merkle_tree_dev(d_leaves, n, d_nodes)
+    tree(d_leaves, n, d_nodes)
 torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(10):
-    zkp.fri_merkle_tree_dev(d_leaves, n, d_nodes)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / 10
-print(f"merkle tree 2^{ld + 1} leaves: {dt * 1e3:.3f} ms = {(2 * n - 1) / dt / 1e9:.2f} G hashes/s")
+ts = []
+for _ in range(5):
+    t0 = time.perf_counter()
+    tree(d_leaves, n, d_nodes)
+    torch.cuda.synchronize()
+    ts.append(time.perf_counter() - t0)
+ts.sort()
+print(f"merkle tree{suffix} 2^{ld + 1} leaves: best {ts[0] * 1e3:.3f} ms, median {ts[2] * 1e3:.3f} ms = "
+      f"{(2 * n - 1) / ts[0] / 1e9:.3f} G hashes/s")

@@ -29,6 +29,7 @@
 #include "plonk.hpp"
 #include "nova.hpp"
 #include "fri.hpp"
+#include "fri_fr.hpp"
 #include "transcript_host.hpp"
 #include "pairing_host.hpp"
 
@@ -178,9 +179,10 @@ struct ProfScope {
     // chain = true: this phase starts where the previous recorded scope on the same stream ended and NOTHING was enqueued in
     // between, so its start is that scope's end event -- one marker per phase boundary instead of two (each marker is a
     // ~5 us bubble on the stream, inside the region bench.py times)
+    // name == nullptr: a phase its caller does not record (fri_host.inc: FriGlTraits::phase)
     ProfScope(const char* name, hipStream_t s, bool chain = false) : st(s), on(false) {
         const int level = g_prof_on.load(std::memory_order_relaxed);
-        on = level == 1 || (level == 2 && std::strcmp(name, "msm_accumulate") == 0);
+        on = name && (level == 1 || (level == 2 && std::strcmp(name, "msm_accumulate") == 0));
         if (!on) return;
         if (level == 2) chain = false;  // the scope before it was not recorded
         rec.name = name;
@@ -1099,7 +1101,8 @@ int create_slot_locked(int device) {
     ZCHK(allow_big_lds(msm_partscatter_kernel<PS_TILE_BIG>));
     ZCHK(allow_big_lds(msm_partscatter_kernel<PS_TILE_MID>));
     ZCHK(allow_big_lds(msm_partscatter_kernel<PS_TILE_SMALL>));
-    ZCHK(allow_big_lds(fri_tail_kernel));
+    ZCHK(allow_big_lds(fri_tail_kernel<FriGl>));
+    ZCHK(allow_big_lds(fri_tail_kernel<FriFr>));
     auto c = std::make_unique<Ctx>();
     c->device = device;
     c->slot = (int)g_rt.slots.size();
@@ -1861,55 +1864,6 @@ int zkp_ntt_fr_layout_dev(const void* d_in, void* d_out, unsigned log_n, size_t 
     return run_ntt<Fr>(reinterpret_cast<const Fr*>(d_in), reinterpret_cast<Fr*>(d_out), log_n, batch, inverse, nullptr, st, &io);
 } ZKP_CATCH_INT
 
-int zkp_fri_layer_eval(const uint64_t* coeffs, size_t d, uint64_t coset, unsigned log_D, uint64_t* out) try {
-    if ((d && !coeffs) || !out) return fail(ZKP_E_ARG, "null argument");
-    if (log_D > 32) return fail(ZKP_E_ARG, "log_D > 32");
-    const size_t D = (size_t)1 << log_D;
-    if (d > D) return fail(ZKP_E_ARG, "more coefficients than domain points");
-    CTX_ENTER(-1);
-    WsOrder ord(nullptr);
-    ZCHK(ctx().tmp.ensure(8 * D));
-    HIPCHK(hipMemsetAsync(ctx().tmp.p, 0, 8 * D, nullptr));
-    if (d) HIPCHK(hipMemcpyAsync(ctx().tmp.p, coeffs, 8 * d, hipMemcpyHostToDevice, nullptr));
-    ZCHK(run_ntt<Gl>(reinterpret_cast<Gl*>(ctx().tmp.p), log_D, 1, 0, &coset, nullptr));
-    HIPCHK(hipMemcpyAsync(out, ctx().tmp.p, 8 * D, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return ZKP_OK;
-} ZKP_CATCH_INT
-
-}  // extern "C"
-
-namespace {
-// out[j] = c[2j] + r * c[2j+1]; r canonical, c Montgomery residues (plain product keeps the residue form)
-__global__ void fri_fold_kernel(const uint64_t* c, uint64_t d, uint64_t r, uint64_t* out) {
-    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (2 * j >= d) return;
-    Gl v{c[2 * j]};
-    if (2 * j + 1 < d) v = v + Gl{r} * Gl{c[2 * j + 1]};
-    out[j] = v.v;
-}
-}  // namespace
-
-extern "C" {
-
-int zkp_fri_fold(const uint64_t* coeffs, size_t d, uint64_t r, uint64_t* out) try {
-    if (d && (!coeffs || !out)) return fail(ZKP_E_ARG, "null argument");
-    if (!d) return ZKP_OK;
-    CTX_ENTER(-1);
-    WsOrder ord(nullptr);
-    const size_t m = (d + 1) / 2;
-    ZCHK(ctx().tmp.ensure(8 * d + 8 * m));
-    uint64_t* dc = reinterpret_cast<uint64_t*>(ctx().tmp.p);
-    HIPCHK(hipMemcpyAsync(dc, coeffs, 8 * d, hipMemcpyHostToDevice, nullptr));
-    HGl rr = HGl::load(&r).from_mont();
-    hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, dc, (uint64_t)d, rr.l[0],
-                       dc + d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dc + d, 8 * m, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return ZKP_OK;
-} ZKP_CATCH_INT
-
 int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, uint64_t* out) try {
     if (la == 0 || lb == 0) return ZKP_OK;  // zero operand => zero polynomial (no coefficients)
     if (!a || !b || !out) return fail(ZKP_E_ARG, "null argument");
@@ -1942,6 +1896,3 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "fri_host.inc"
 #include "verify_host.inc"
 #include "nova_host.inc"
-// FRI over Fr last: its kernels follow every other kernel in the code object
-#include "fri_fr.hpp"
-#include "fri_fr_host.inc"

@@ -209,9 +209,8 @@ inline std::string fr_display(const uint64_t canonical[4], bool zero_as_0) {
 // fri/src/fiat_shamir/transcript.rs
 class FriTranscript {
 public:
-    explicit FriTranscript(bool zero_as_0) : zero_as_0_(zero_as_0) { digest(0); }  // Transcript::new(F::ZERO)
-    void digest(uint64_t canonical) { digest_display(goldilocks_display(canonical, zero_as_0_)); }  // Goldilocks
-    void digest_display(const std::string& s) {  // transcript.rs:64-72, any field: s = Display(message)
+    explicit FriTranscript(bool zero_as_0) { digest_display(zero_as_0 ? "0" : ""); }  // Transcript::new(F::ZERO): Display(0)
+    void digest_display(const std::string& s) {  // transcript.rs:64-72: s = Display(message) of the proof's field
         Sha256 h;
         if (has_data_) h.update(data_.data(), 32);
         uint8_t le[8];
@@ -233,7 +232,7 @@ public:
         return true;
     }
 
-    // hand-over to / from the device-side continuation of the same transcript (csrc/fri.hpp: fri_tail_kernel)
+    // hand-over to / from the device-side continuation of the same transcript (csrc/fri.hpp: fri_transcript_challenge)
     const std::array<uint8_t, 32>& data() const { return data_; }
     uint64_t index() const { return index_; }
     void resume(const std::array<uint8_t, 32>& data, uint64_t index, bool generated) {
@@ -245,7 +244,7 @@ public:
 
 private:
     std::array<uint8_t, 32> data_{};
-    bool has_data_ = false, generated_ = true, zero_as_0_;
+    bool has_data_ = false, generated_ = true;
     uint64_t index_ = 0;
 };
 
