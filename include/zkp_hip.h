@@ -202,6 +202,32 @@ int zkp_g1_fixed_base_mul_dev(const void *d_scalars, size_t n, void *d_out_xy, u
  * canonical a^-1 R out; form 1: the library's internal 14 x 28-bit limbs (+ 2 pad words = 64 B per element), Montgomery radix 2^392,
  * any value below 2p in, a^-1 R below 2p out.  0 maps to 0.  Not part of the hot path. */
 int zkp_selftest_fq_inverse_dev(const void *d_in, size_t n, int form, void *d_out, void *stream);
+/* Self-test hooks for the device field and curve primitives everything above is built from (csrc/selftest.hpp): one lane per case, raw
+ * limbs in and out, no conversion; the tests compare the output words with an exact limb model at the edges of each primitive's operand
+ * contract (tests/test_gpu_field_selftest.py).  Not part of the hot path; the operation numbers are the enums of csrc/selftest.hpp.
+ * Field families: d_in holds n records of 4 operand slots x 16 words (256 B per case), d_out receives n records of 2 result slots x 16
+ * words (128 B per case, unused words zero); an operand fills the first words of its slot.  d_out must not be d_in.
+ *   zkp_selftest_fq28_dev  14 x 28-bit limbs, radix 2^392: the six product forms (0 fq28_mul_inline, 1 fq28_mul_chain, 2 fq28_mul_chain2
+ *                          = two products, 3 sqr, 4 fq28_sqr_chain, 5 fq28_mul2, 6 fq28_mul2_chain), 7 normalise, 8 sub4, 9 sub8, 10 sub16,
+ *                          11 sub8w, 12 neg4, 13 tight_is_zero_mod_p (word 0), 14 fq28_from_sat (12 words in)
+ *   zkp_selftest_fr29_dev  9 x 29-bit limbs, radix 2^261: 0 operator*, 1 fr29_mul2 = two products, 2 fr29_to_canonical (8 words out),
+ *                          3 the memory-form Fr operator* (8 words in and out), 4 sub_tight, 5 sub_wide8, 6 normalise, 7 fr29_pack_tight,
+ *                          8 fr29_from_sat_shl5, 9 fr29_twiddle_from_mont, 10 fr29_from_sat
+ *   zkp_selftest_fp_dev    saturated Montgomery form, field 0 = Fq (12 words), 1 = Fr (8 words): 0 +, 1 -, 2 neg, 3 dbl, 4 operator*
+ *                          (Fq: the out-of-line product), 5 mont_mul
+ *   zkp_selftest_gl_dev    Goldilocks, 2 words: 0 +, 1 -, 2 neg, 3 *, 4 gl_reduce128(lo = slot 0, hi = slot 1)
+ * G1 (zkp_selftest_g1_dev): points are raw limbs, 4 coordinates (X, Y, ZZ, ZZZ; an affine point: x, y) of 16 words.  Operations 0..6
+ * (0 / 1 g1_28_madd plain / asm chains, 2 / 3 g1_28_mmadd likewise, 4 g1_28_add, 5 g1_28_double, 6 g1_28_double_affine) take point i at
+ * byte 256 i of each array, and d_out may be d_a; operations 7..12 (7 / 8 g1_28_add_stream plain / chains, 9 / 10
+ * g1_28_add_stream_inplace, 11 g1_28_add_quad, 12 the same with dst = srcA) take the plane-major layout of the bucket arrays, 16-byte
+ * chunk q of point i at byte 16 (q stride + i), stride >= n; the in-place forms read their first operand from d_out (d_a is not used)
+ * and the quad forms run four lanes per case.  d_flag receives one word per case: the return value of mmadd, result.is_inf() for the
+ * other operations 0..6, zero otherwise. */
+int zkp_selftest_fq28_dev(int op, const void *d_in, size_t n, void *d_out, void *stream);
+int zkp_selftest_fr29_dev(int op, const void *d_in, size_t n, void *d_out, void *stream);
+int zkp_selftest_fp_dev(int field, int op, const void *d_in, size_t n, void *d_out, void *stream);
+int zkp_selftest_gl_dev(int op, const void *d_in, size_t n, void *d_out, void *stream);
+int zkp_selftest_g1_dev(int op, const void *d_a, const void *d_b, size_t n, size_t stride, void *d_out, void *d_flag, void *stream);
 /* [s^i]G for i < n into host memory (kzg/src/srs.rs:48-63: n = circuit_size + 3). */
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t *out_xy);
 

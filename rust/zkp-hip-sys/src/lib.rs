@@ -121,6 +121,11 @@ extern "C" {
     pub fn zkp_g1_mul(base_xy: *const u64, base_is_inf: u8, scalar: *const u64, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_g1_fixed_base_mul_dev(d_scalars: *const c_void, n: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_fq_inverse_dev(d_in: *const c_void, n: usize, form: i32, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_fq28_dev(op: i32, d_in: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_fr29_dev(op: i32, d_in: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_fp_dev(field: i32, op: i32, d_in: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_gl_dev(op: i32, d_in: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_g1_dev(op: i32, d_a: *const c_void, d_b: *const c_void, n: usize, stride: usize, d_out: *mut c_void, d_flag: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_srs_g1(secret: *const u64, n: usize, out_xy: *mut u64) -> i32;
     pub fn zkp_ntt_fr(data: *mut u64, log_n: u32, inverse: i32, coset: *const u64) -> i32;
     pub fn zkp_ntt_fr_dev(d_data: *mut c_void, log_n: u32, batch: usize, inverse: i32, coset: *const u64, stream: *mut c_void) -> i32;

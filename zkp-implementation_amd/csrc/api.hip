@@ -30,6 +30,7 @@
 #include "nova.hpp"
 #include "fri.hpp"
 #include "fri_fr.hpp"
+#include "selftest.hpp"
 #include "transcript_host.hpp"
 #include "pairing_host.hpp"
 
@@ -1754,6 +1755,76 @@ int zkp_selftest_fq_inverse_dev(const void* d_in, size_t n, int form, void* d_ou
     hipLaunchKernelGGL(fq_inverse_selftest_kernel, dim3((unsigned)((n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<uint32_t*>(d_out),
                        (uint64_t)n, form);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+// ---- lane-level self-tests of the field and curve primitives (kernels: csrc/selftest.hip) ----
+namespace {
+unsigned selftest_grid(size_t lanes) { return (unsigned)((lanes + ST_THREADS - 1) / ST_THREADS); }
+int selftest_args(const void* d_in, size_t n, const void* d_out) {
+    if (n && (!d_in || !d_out)) return fail(ZKP_E_ARG, "null argument");
+    if (d_in && d_in == d_out) return fail(ZKP_E_ARG, "d_out must not be d_in");
+    if (n > (size_t)1 << 24) return fail(ZKP_E_SIZE, "a self-test takes at most 2^24 cases");
+    return ZKP_OK;
+}
+}  // namespace
+
+int zkp_selftest_fq28_dev(int op, const void* d_in, size_t n, void* d_out, void* stream) try {
+    ZCHK(selftest_args(d_in, n, d_out));
+    if (op < 0 || op >= ST_FQ28_OPS) return fail(ZKP_E_ARG, "unknown Fq28 self-test operation");
+    CTX_ENTER(-1);
+    if (!n) return ZKP_OK;
+    selftest_fq28_launch(op, selftest_grid(n), reinterpret_cast<hipStream_t>(stream), d_in, d_out, (uint64_t)n);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_selftest_fr29_dev(int op, const void* d_in, size_t n, void* d_out, void* stream) try {
+    ZCHK(selftest_args(d_in, n, d_out));
+    if (op < 0 || op >= ST_FR29_OPS) return fail(ZKP_E_ARG, "unknown Fr29 self-test operation");
+    CTX_ENTER(-1);
+    if (!n) return ZKP_OK;
+    selftest_fr29_launch(op, selftest_grid(n), reinterpret_cast<hipStream_t>(stream), d_in, d_out, (uint64_t)n);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_selftest_fp_dev(int field, int op, const void* d_in, size_t n, void* d_out, void* stream) try {
+    ZCHK(selftest_args(d_in, n, d_out));
+    if (field != 0 && field != 1) return fail(ZKP_E_ARG, "field must be 0 (Fq, 12 words) or 1 (Fr, 8 words)");
+    if (op < 0 || op >= ST_FP_OPS) return fail(ZKP_E_ARG, "unknown Fp self-test operation");
+    CTX_ENTER(-1);
+    if (!n) return ZKP_OK;
+    selftest_fp_launch(field, op, selftest_grid(n), reinterpret_cast<hipStream_t>(stream), d_in, d_out, (uint64_t)n);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_selftest_gl_dev(int op, const void* d_in, size_t n, void* d_out, void* stream) try {
+    ZCHK(selftest_args(d_in, n, d_out));
+    if (op < 0 || op >= ST_GL_OPS) return fail(ZKP_E_ARG, "unknown Goldilocks self-test operation");
+    CTX_ENTER(-1);
+    if (!n) return ZKP_OK;
+    selftest_gl_launch(op, selftest_grid(n), reinterpret_cast<hipStream_t>(stream), d_in, d_out, (uint64_t)n);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_selftest_g1_dev(int op, const void* d_a, const void* d_b, size_t n, size_t stride, void* d_out, void* d_flag, void* stream) try {
+    if (op < 0 || op >= ST_G1_OPS) return fail(ZKP_E_ARG, "unknown G1 self-test operation");
+    const bool in_place = op == ST_G1_ADD_INPLACE || op == ST_G1_ADD_INPLACE_CHAIN || op == ST_G1_ADD_QUAD_INPLACE;
+    const bool planes = op >= ST_G1_ADD_STREAM;
+    if (n && ((!d_a && !in_place) || !d_b || !d_out || !d_flag)) return fail(ZKP_E_ARG, "null argument");
+    if (d_b && d_b == d_out) return fail(ZKP_E_ARG, "d_out must not be d_b");
+    if ((op == ST_G1_ADD_STREAM || op == ST_G1_ADD_STREAM_CHAIN) && d_a == d_out) return fail(ZKP_E_ARG, "the streaming add does not alias: use the in-place operation");
+    if (n > (size_t)1 << 24) return fail(ZKP_E_SIZE, "a self-test takes at most 2^24 cases");
+    if (planes && stride < n) return fail(ZKP_E_ARG, "stride below the number of cases");
+    CTX_ENTER(-1);
+    if (!n) return ZKP_OK;
+    const bool quad = op == ST_G1_ADD_QUAD || op == ST_G1_ADD_QUAD_INPLACE;
+    selftest_g1_launch(op, selftest_grid(quad ? 4 * n : n), reinterpret_cast<hipStream_t>(stream), d_a, d_b, d_out, d_flag, (uint64_t)n,
+                       (uint64_t)stride);
     HIPCHK(hipGetLastError());
     return ZKP_OK;
 } ZKP_CATCH_INT

@@ -63,6 +63,11 @@ _SIGS = {
     "zkp_g1_mul": ([_VP, C.c_uint8, _VP, _VP, _VP], C.c_int),
     "zkp_g1_fixed_base_mul_dev": ([_VP, _SZ, _VP, _U8P, _VP], C.c_int),
     "zkp_selftest_fq_inverse_dev": ([_VP, _SZ, C.c_int, _VP, _VP], C.c_int),
+    "zkp_selftest_fq28_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_selftest_fr29_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_selftest_fp_dev": ([C.c_int, C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_selftest_gl_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_selftest_g1_dev": ([C.c_int, _VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_srs_g1": ([_VP, _SZ, _VP], C.c_int),
     "zkp_ntt_fr": ([_VP, C.c_uint, C.c_int, _VP], C.c_int),
     "zkp_ntt_fr_dev": ([_VP, C.c_uint, _SZ, C.c_int, _VP, _VP], C.c_int),
@@ -354,6 +359,37 @@ def selftest_fq_inverse_dev(in_tensor, n, form, out_tensor, stream=None):
     words = 12 if form == 0 else 16
     _chk(lib().zkp_selftest_fq_inverse_dev(_dev_ptr(in_tensor, 4 * words * n), n, form, _dev_ptr(out_tensor, 4 * words * n),
                                            _stream_ptr(stream)))
+
+
+# operation numbers of the lane-level self-tests (the enums of csrc/selftest.hpp; tests/test_limb_model_cpu.py compares the two)
+SELFTEST_OPS = {
+    "fq28": {"mul_inline": 0, "mul_chain": 1, "mul_chain2": 2, "sqr": 3, "sqr_chain": 4, "mul2": 5, "mul2_chain": 6, "normalise": 7,
+             "sub4": 8, "sub8": 9, "sub16": 10, "sub8w": 11, "neg4": 12, "is_zero": 13, "from_sat": 14},
+    "fr29": {"mul": 0, "mul2": 1, "to_canonical": 2, "fr_mul": 3, "sub_tight": 4, "sub_wide8": 5, "normalise": 6, "pack_tight": 7,
+             "from_sat_shl5": 8, "twiddle": 9, "from_sat": 10},
+    "fp": {"add": 0, "sub": 1, "neg": 2, "dbl": 3, "mul": 4, "mont_mul": 5},
+    "gl": {"add": 0, "sub": 1, "neg": 2, "mul": 3, "reduce128": 4},
+    "g1": {"madd": 0, "madd_chain": 1, "mmadd": 2, "mmadd_chain": 3, "add": 4, "double": 5, "double_affine": 6, "add_stream": 7,
+           "add_stream_chain": 8, "add_inplace": 9, "add_inplace_chain": 10, "add_quad": 11, "add_quad_inplace": 12},
+}
+
+
+def selftest_field_dev(family, op, in_tensor, n, out_tensor, stream=None):
+    """zkp_selftest_{fq28,fr29,fp,gl}_dev: n cases, 64 input words and 32 output words each (int32 tensors).  family: "fq28", "fr29", "gl",
+    "fq" or "fr" (the saturated forms); op: a name of SELFTEST_OPS."""
+    args = (_dev_ptr(in_tensor, 256 * n), n, _dev_ptr(out_tensor, 128 * n), _stream_ptr(stream))
+    if family in ("fq", "fr"):
+        _chk(lib().zkp_selftest_fp_dev(0 if family == "fq" else 1, SELFTEST_OPS["fp"][op], *args))
+    else:
+        _chk(getattr(lib(), f"zkp_selftest_{family}_dev")(SELFTEST_OPS[family][op], *args))
+
+
+def selftest_g1_dev(op, a_tensor, b_tensor, n, stride, out_tensor, flag_tensor, stream=None):
+    """zkp_selftest_g1_dev: the point arrays hold 64 words per point (register forms: n points; plane-major forms: 16 chunks x stride);
+    a_tensor may be None for the in-place forms."""
+    pts = 256 * (stride if SELFTEST_OPS["g1"][op] >= 7 else n)
+    _chk(lib().zkp_selftest_g1_dev(SELFTEST_OPS["g1"][op], _dev_ptr(a_tensor, pts) if a_tensor is not None else None, _dev_ptr(b_tensor, pts),
+                                   n, stride, _dev_ptr(out_tensor, pts), _dev_ptr(flag_tensor, 4 * n), _stream_ptr(stream)))
 
 
 def msm_g1_dev(bases, scalars_tensor, n, stream=None):
