@@ -454,6 +454,35 @@ int zkp_plonk_verify(zkp_plonk_prover *p, const uint64_t g2s_xy[24], const zkp_p
  * 7 tx_compact 8 t (before round 5). */
 int zkp_plonk_get_poly(zkp_plonk_prover *p, int which, uint64_t *out, size_t cap_elems, size_t *len);
 
+/* ---- Circuit::compile (plonk/src/circuit.rs:166-245) on the device: the gate list to a resident prover, and a new witness
+ *      for the same circuit.  The gates of circuit.rs as the caller holds them, struct of arrays, g = `gates` real gates (no
+ *      dummies: pad_circuit adds those, and they are always trailing). ---- */
+typedef struct {
+    size_t gates;          /* g >= 2 */
+    const uint32_t *pos;   /* g x 6: a_col a_row b_col b_row c_col c_row = Position::Pos(col, row), gate.rs */
+    const uint64_t *sel;   /* g x 6 x 4 limbs: q_m q_l q_r q_o q_c pi AS STORED in Gate (pi already negated, gate.rs:53) */
+    const uint64_t *vals;  /* g x 3 x 4 limbs: the a, b, c values of Circuit::vals */
+} zkp_plonk_gates;
+/* n = 2^((g - 1).ilog2() + 1) (pad_circuit, circuit.rs:148-157): g < 2 and log_n > 24 are ZKP_E_ARG, an SRS below n + 3 points
+ * ZKP_E_SIZE, a sharded SRS ZKP_E_ARG.  The nine assignment columns hold the gate's selector or value in row i < g and zero
+ * beyond (get_assignment skips dummies, interpolate zero-pads); sigma_j[i] = K_col w^row for the wire (col, row) of gate i
+ * with K = (1, k1, k2), k1 = 2, k2 = 3 (find_cosets), and K_j w^i in the dummy rows (cal_permutation).  A col above 2 or a
+ * row >= n is ZKP_E_ARG (the reference panics with "Invalid position" or indexes out of bounds), decided before any prover
+ * exists.  The twelve inverse transforms run on the device; the prover is the one zkp_plonk_prover_create makes from the
+ * same twelve coefficient vectors with k1 = 2, k2 = 3. */
+int zkp_plonk_prover_create_from_gates(const zkp_bases *srs, const zkp_plonk_gates *gates, zkp_plonk_prover **out);
+/* Another witness for a prover made by zkp_plonk_prover_create_from_gates (any other prover: ZKP_E_ARG): vals = g x 3 x 4
+ * limbs, pi = g x 4 limbs as stored (nullable: the public inputs stay), gates = the g of creation (else ZKP_E_ARG).
+ * Selectors, wiring and everything computed from them stay; the next proof starts at round 1.  A witness that does not
+ * satisfy its gates is reported by round 3 / zkp_plonk_prove ("No remainder expected"), and a later good one proves again.
+ * _dev: device pointers (16-byte aligned), read on `stream`; the call returns when the device work is done. */
+int zkp_plonk_prover_set_witness(zkp_plonk_prover *p, const uint64_t *vals, const uint64_t *pi, size_t gates);
+int zkp_plonk_prover_set_witness_dev(zkp_plonk_prover *p, const void *d_vals, const void *d_pi, size_t gates, void *stream);
+/* Parity accessor: the n coefficients (zero-padded) of circuit polynomial `which`, 0..11 in the order of
+ * zkp_plonk_prover_create.  `out` receives min(cap_elems, n) coefficients; *len = n. */
+int zkp_plonk_get_circuit_poly(zkp_plonk_prover *p, int which, uint64_t *out, size_t cap_elems, size_t *len);
+int zkp_plonk_prover_info(const zkp_plonk_prover *p, unsigned *log_n, uint64_t k1[4], uint64_t k2[4]);
+
 /* ---- Nova folding (NIFS) over a sparse R1CS: nova/src/nifs/mod.rs, nifs_prover.rs, nifs_verifier.rs, r1cs/mod.rs.
  *      R1CS (r1cs/mod.rs:9-16): A, B, C with `rows` rows over z = (W || x || u), |W| = num_vars, |x| = num_io, so columns
  *      0..num_vars+num_io.  The reference holds dense ragged rows (utils.rs:14-22: an entry beyond a row's length is zero); here each

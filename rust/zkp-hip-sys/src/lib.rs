@@ -29,6 +29,15 @@ pub struct zkp_plonk_proof {
     pub degree: u64,
 }
 
+/// the gates of plonk/src/circuit.rs as struct of arrays (zkp_plonk_prover_create_from_gates)
+#[repr(C)]
+pub struct zkp_plonk_gates {
+    pub gates: usize,     // g >= 2 real gates
+    pub pos: *const u32,  // g x 6: a_col a_row b_col b_row c_col c_row
+    pub sel: *const u64,  // g x 6 x 4 limbs: q_m q_l q_r q_o q_c pi as stored in Gate
+    pub vals: *const u64, // g x 3 x 4 limbs: a, b, c of Circuit::vals
+}
+
 /// gathered / scattered transform layout of zkp_ntt_fr_layout_dev (strides in elements)
 #[repr(C)]
 pub struct zkp_ntt_layout {
@@ -174,6 +183,11 @@ extern "C" {
     pub fn zkp_kzg_aggregate_commitments(commits_xy: *const u64, commits_is_inf: *const u8, n: usize, challenge: *const u64, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_plonk_verify(p: *mut zkp_plonk_prover, g2s_xy: *const u64, proof: *const zkp_plonk_proof, accepted: *mut i32) -> i32;
     pub fn zkp_plonk_get_poly(p: *mut zkp_plonk_prover, which: i32, out: *mut u64, cap_elems: usize, len: *mut usize) -> i32;
+    pub fn zkp_plonk_prover_create_from_gates(srs: *const zkp_bases, gates: *const zkp_plonk_gates, out: *mut *mut zkp_plonk_prover) -> i32;
+    pub fn zkp_plonk_prover_set_witness(p: *mut zkp_plonk_prover, vals: *const u64, pi: *const u64, gates: usize) -> i32;
+    pub fn zkp_plonk_prover_set_witness_dev(p: *mut zkp_plonk_prover, d_vals: *const c_void, d_pi: *const c_void, gates: usize, stream: *mut c_void) -> i32;
+    pub fn zkp_plonk_get_circuit_poly(p: *mut zkp_plonk_prover, which: i32, out: *mut u64, cap_elems: usize, len: *mut usize) -> i32;
+    pub fn zkp_plonk_prover_info(p: *const zkp_plonk_prover, log_n: *mut u32, k1: *mut u64, k2: *mut u64) -> i32;
     pub fn zkp_nova_r1cs_create(srs: *const zkp_bases, rows: usize, num_vars: usize, num_io: usize, a: *const zkp_csr, b: *const zkp_csr, c: *const zkp_csr, out: *mut *mut zkp_nova_r1cs) -> i32;
     pub fn zkp_nova_r1cs_destroy(r: *mut zkp_nova_r1cs);
     pub fn zkp_nova_cross_term_dev(r: *mut zkp_nova_r1cs, d_w1: *const c_void, x1: *const u64, u1: *const u64, d_w2: *const c_void, x2: *const u64, u2: *const u64, d_t: *mut c_void, stream: *mut c_void) -> i32;

@@ -9,7 +9,7 @@ PRIM = {"uint64_t": "u64", "uint8_t": "u8", "int": "i32", "unsigned": "u32", "si
         "double": "f64", "zkp_bases": "zkp_bases", "zkp_plonk_prover": "zkp_plonk_prover",
         "zkp_plonk_transcript": "zkp_plonk_transcript", "zkp_plonk_proof": "zkp_plonk_proof", "zkp_ntt_layout": "zkp_ntt_layout",
         "zkp_ntt_shard_geometry": "zkp_ntt_shard_geometry", "zkp_nova_r1cs": "zkp_nova_r1cs", "zkp_nova_transcript": "zkp_nova_transcript",
-        "zkp_csr": "zkp_csr", "zkp_nova_instance": "zkp_nova_instance", "zkp_nova_proof": "zkp_nova_proof"}
+        "zkp_csr": "zkp_csr", "zkp_plonk_gates": "zkp_plonk_gates", "zkp_nova_instance": "zkp_nova_instance", "zkp_nova_proof": "zkp_nova_proof"}
 RET = {"int": "i32", "void": "()", "size_t": "usize", "const char *": "*const c_char", "const char*": "*const c_char"}
 
 
@@ -68,6 +68,15 @@ pub struct zkp_plonk_proof {
     pub bars: [[u64; 4]; 6],       // bar_a, bar_b, bar_c, bar_s_sigma_1, bar_s_sigma_2, bar_z_w
     pub u: [u64; 4],
     pub degree: u64,
+}
+
+/// the gates of plonk/src/circuit.rs as struct of arrays (zkp_plonk_prover_create_from_gates)
+#[repr(C)]
+pub struct zkp_plonk_gates {
+    pub gates: usize,     // g >= 2 real gates
+    pub pos: *const u32,  // g x 6: a_col a_row b_col b_row c_col c_row
+    pub sel: *const u64,  // g x 6 x 4 limbs: q_m q_l q_r q_o q_c pi as stored in Gate
+    pub vals: *const u64, // g x 3 x 4 limbs: a, b, c of Circuit::vals
 }
 
 /// gathered / scattered transform layout of zkp_ntt_fr_layout_dev (strides in elements)

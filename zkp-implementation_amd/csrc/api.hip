@@ -1964,6 +1964,7 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 
 #include "ntt_sharded.inc"
 #include "plonk_host.inc"
+#include "plonk_compile_host.inc"
 #include "fri_host.inc"
 #include "verify_host.inc"
 #include "nova_host.inc"

@@ -235,6 +235,53 @@ __global__ __launch_bounds__(PK_THREADS) void plonk_gate_check_kernel(const Fr* 
     const unsigned long long m = __ballot(bad);
     if (m && (threadIdx.x & 63) == 0) atomicAdd(violations, (unsigned long long)__builtin_popcountll(m));
 }
+// Circuit::compile's columns (circuit.rs:166-245) from the gate table, one lane per row of the domain: cols = 12 x n evaluation
+// vectors in circuit order (q_m q_l q_r q_o q_c pi f_a f_b f_c s1 s2 s3), the input of the twelve interpolations.
+//   rows i < g:  the gate's selectors and values; sigma_j[i] = K_col w^row for wire j = (col, row), K = (1, 2, 3) (find_cosets)
+//   rows i >= g: pad_circuit's dummy gates -- zero assignment (get_assignment skips them, interpolate zero-pads), sigma_j[i] = K_j w^i
+// w^e = w_hi[e >> h] * w_lo[e & (2^h - 1)] (two host tables of about sqrt(n) entries): one product per wire, and K_col = 2, 3 are
+// additions.  `sel` null restricts the kernel to the witness columns (a new witness for the same circuit): f_a f_b f_c, and pi
+// where `pi` is given (pi_stride elements apart: 6 inside the selector table, 1 in an array of its own).
+// The host has checked every position (col <= 2, row < n); the row is masked all the same, so that no table read can leave its table.
+struct GateColsParams {
+    const uint32_t* pos;   // g x 6: a_col a_row b_col b_row c_col c_row
+    const Fr* sel;         // g x 6: q_m q_l q_r q_o q_c pi (nullable)
+    const Fr* vals;        // g x 3: a b c
+    const Fr* pi;          // nullable
+    uint32_t pi_stride;
+    const Fr* w_lo;        // 2^h entries: w^j
+    const Fr* w_hi;        // n >> h entries: w^(j 2^h)
+    uint32_t h;
+    uint64_t g, n;
+    Fr* cols;              // 12 x n
+};
+ZKP_DEV Fr gate_cols_root(const GateColsParams& p, uint64_t e) {
+    e &= p.n - 1;
+    return p.w_hi[e >> p.h] * p.w_lo[e & ((1u << p.h) - 1)];
+}
+ZKP_DEV Fr gate_cols_coset(const Fr& w, uint32_t col) {  // K_col w
+    const Fr w2 = w + w;
+    return col == 0 ? w : col == 1 ? w2 : w2 + w;
+}
+__global__ __launch_bounds__(PK_THREADS) void plonk_gate_cols_kernel(GateColsParams p) {
+    const uint64_t i = (uint64_t)blockIdx.x * PK_THREADS + threadIdx.x;
+    if (i >= p.n) return;
+    const uint64_t n = p.n;
+    const bool real = i < p.g;
+#pragma unroll
+    for (int j = 0; j < 3; j++) p.cols[(6 + j) * n + i] = real ? p.vals[3 * i + j] : Fr::zero();
+    if (p.pi) p.cols[5 * n + i] = real ? p.pi[(uint64_t)p.pi_stride * i] : Fr::zero();
+    if (!p.sel) return;
+#pragma unroll
+    for (int j = 0; j < 5; j++) p.cols[j * n + i] = real ? p.sel[6 * i + j] : Fr::zero();
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const uint32_t col = real ? p.pos[6 * i + 2 * j] : (uint32_t)j;
+        const uint64_t row = real ? p.pos[6 * i + 2 * j + 1] : i;
+        p.cols[(9 + j) * n + i] = gate_cols_coset(gate_cols_root(p, row), col);
+    }
+}
+
 // acc[i] = nprefix[i] * dsuffix[i] * inv_total
 __global__ __launch_bounds__(PK_THREADS) void plonk_acc_combine_kernel(const Fr* __restrict__ nprefix, const Fr* __restrict__ dsuffix,
                                                                       Fr inv_total, uint64_t n, Fr* __restrict__ acc) {

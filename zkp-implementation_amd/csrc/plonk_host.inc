@@ -42,6 +42,8 @@ struct zkp_plonk_prover {
     unsigned partial_cap = 0;
     TypedBuf<unsigned long long> d_len;
     TypedBuf<Fr> dom_evals;     // the 12 circuit polynomials evaluated on the domain (12 n, circuit order): circuit constants, computed by the first round 2
+                                // (a prover made from gates starts with them: they are the columns its polynomials were interpolated from)
+    uint64_t gates = 0;         // real gates of zkp_plonk_prover_create_from_gates; 0: made from coefficient vectors, no witness rebinding
     // "No remainder expected" (prover.rs:404,431,441), decided exactly on the domain instead of by long division:
     int gate_rows_bad = -1;     // rows of the witness that violate their gate equation (-1: not checked yet; a circuit constant)
     bool perm_closes = false;   // this proof's beta, gamma: prod_i num_i == prod_i den_i, i.e. the accumulator returns to 1 (:431)
@@ -316,22 +318,15 @@ __global__ void fr_fill_kernel(Fr* p, uint64_t n, Fr v) {
     if (i < n) p[i] = v;
 }
 
-}  // namespace
+const char* const kShardedSrsMsg = "SRS is sharded over several devices: a 2^16-gate proof does not shard (SURVEY 8e: replicas only) -- "
+                                   "create the SRS on one slot (zkp_set_device) and run one prover per device";
 
-extern "C" {
-
-int zkp_plonk_prover_create(const zkp_bases* srs, unsigned log_n, const uint64_t* const polys[12], const size_t lens[12],
-                            const uint64_t k1[4], const uint64_t k2[4], zkp_plonk_prover** out) try {
-    if (!srs || !polys || !lens || !k1 || !k2 || !out) return fail(ZKP_E_ARG, "null argument");
-    if (log_n > 24) return fail(ZKP_E_ARG, "log_n > 24");
-    if (!srs->shards.empty())
-        return fail(ZKP_E_ARG, "SRS is sharded over several devices: a 2^16-gate proof does not shard (SURVEY 8e: replicas only) -- "
-                               "create the SRS on one slot (zkp_set_device) and run one prover per device");
-    CTX_ENTER(srs->slot);
-    WsOrder ord(nullptr);
+// A prover of 2^log_n rows over `srs` with every buffer, stream and event it will need and zeroed polynomials; the caller is inside
+// the SRS's slot (CTX_ENTER) and fills `circ`.  (Every HIP failure here reports the bare HIP error text.)
+int prover_alloc(const zkp_bases* srs, unsigned log_n, const HFr& k1, const HFr& k2, std::unique_ptr<zkp_plonk_prover>& p) {
     const uint64_t n = 1ull << log_n;
     if (srs->n < n + 3) return fail(ZKP_E_SIZE, "SRS must hold circuit_size + 3 points (kzg/src/srs.rs:51)");
-    std::unique_ptr<zkp_plonk_prover> p(new (std::nothrow) zkp_plonk_prover());
+    p.reset(new (std::nothrow) zkp_plonk_prover());
     if (!p) return fail(ZKP_E_NOMEM, "host allocation failed");
     p->srs = srs;
     p->device = ctx().device;
@@ -341,9 +336,8 @@ int zkp_plonk_prover_create(const zkp_bases* srs, unsigned log_n, const uint64_t
     while ((1ull << p->log_D) < 3 * n + 7) p->log_D++;  // t has 3n + 6 coefficients (prover.rs:149)
     p->D = 1ull << p->log_D;
     p->cap = n + 8;
-    p->k1 = HFr::load(k1);
-    p->k2 = HFr::load(k2);
-    // (every HIP failure here reports the bare HIP error text)
+    p->k1 = k1;
+    p->k2 = k2;
     HIPCHK_BARE(p->circ.grow(32 * 12 * n));
     HIPCHK_BARE(p->work.grow(32 * 8 * p->cap));
     HIPCHK_BARE(p->t.grow(32 * std::max<uint64_t>(p->D, 2 * p->cap)));
@@ -360,6 +354,23 @@ int zkp_plonk_prover_create(const zkp_bases* srs, unsigned log_n, const uint64_t
     p->h_pin[4 * (size_t)p->partial_cap] = 0;
     HIPCHK_BARE(hipMemset(p->circ, 0, 32 * 12 * n));
     HIPCHK_BARE(hipMemset(p->work, 0, 32 * 8 * p->cap));
+    return ZKP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkp_plonk_prover_create(const zkp_bases* srs, unsigned log_n, const uint64_t* const polys[12], const size_t lens[12],
+                            const uint64_t k1[4], const uint64_t k2[4], zkp_plonk_prover** out) try {
+    if (!srs || !polys || !lens || !k1 || !k2 || !out) return fail(ZKP_E_ARG, "null argument");
+    if (log_n > 24) return fail(ZKP_E_ARG, "log_n > 24");
+    if (!srs->shards.empty()) return fail(ZKP_E_ARG, kShardedSrsMsg);
+    CTX_ENTER(srs->slot);
+    WsOrder ord(nullptr);
+    std::unique_ptr<zkp_plonk_prover> p;
+    ZCHK(prover_alloc(srs, log_n, HFr::load(k1), HFr::load(k2), p));
+    const uint64_t n = p->n;
     for (int i = 0; i < 12; i++) {
         if (lens[i] > n) return fail(ZKP_E_ARG, "circuit polynomial longer than n");
         if (lens[i]) HIPCHK_BARE(hipMemcpy(p->circuit(i), polys[i], 32 * lens[i], hipMemcpyHostToDevice));

@@ -116,6 +116,11 @@ _SIGS = {
     "zkp_plonk_round4": ([_VP, _VP, _VP], C.c_int),
     "zkp_plonk_round5": ([_VP, _VP, _VP, _VP], C.c_int),
     "zkp_plonk_get_poly": ([_VP, C.c_int, _VP, _SZ, C.POINTER(C.c_size_t)], C.c_int),
+    "zkp_plonk_prover_create_from_gates": ([_VP, _VP, C.POINTER(_VP)], C.c_int),
+    "zkp_plonk_prover_set_witness": ([_VP, _VP, _VP, _SZ], C.c_int),
+    "zkp_plonk_prover_set_witness_dev": ([_VP, _VP, _VP, _SZ, _VP], C.c_int),
+    "zkp_plonk_get_circuit_poly": ([_VP, C.c_int, _VP, _SZ, C.POINTER(C.c_size_t)], C.c_int),
+    "zkp_plonk_prover_info": ([_VP, C.POINTER(C.c_uint), _VP, _VP], C.c_int),
     "zkp_kzg_commit": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_kzg_open": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_nova_r1cs_create": ([_VP, _SZ, _SZ, _SZ, _VP, _VP, _VP, C.POINTER(_VP)], C.c_int),
@@ -818,6 +823,69 @@ class _PlonkProof(C.Structure):  # zkp_plonk_proof in include/zkp_hip.h
                 ("u", C.c_uint64 * 4), ("degree", C.c_uint64)]
 
 
+class _PlonkGates(C.Structure):  # zkp_plonk_gates in include/zkp_hip.h
+    _fields_ = [("gates", C.c_size_t), ("pos", C.c_void_p), ("sel", C.c_void_p), ("vals", C.c_void_p)]
+
+
+_FR_MOD = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+
+
+def _fr_mont_rows(values):
+    """ints -> (len, 4) uint64 Montgomery limbs (the memory form of the ABI); a circuit repeats few selector values, so each distinct
+    value is converted once."""
+    seen = {}
+    out = np.empty((len(values), 4), dtype=np.uint64)
+    for i, v in enumerate(values):
+        row = seen.get(v)
+        if row is None:
+            m = (v % _FR_MOD << 256) % _FR_MOD
+            row = seen[v] = [(m >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]
+        out[i] = row
+    return out
+
+
+class PlonkCircuit:
+    """Circuit of plonk/src/circuit.rs: gates over (wire column, row, value) triples, with the selector rules of gate.rs:38-94
+    (the stored pi is negated; a constant gate has q_l = 1 and q_c = -constant).  Holds plain integers; gate_table() packs them
+    for zkp_plonk_prover_create_from_gates, compile() replaces Circuit::compile."""
+
+    def __init__(self):
+        self.pos = []   # per gate: a_col a_row b_col b_row c_col c_row
+        self.sel = []   # per gate: q_m q_l q_r q_o q_c pi (as stored)
+        self.vals = []  # per gate: a b c
+
+    def __len__(self):
+        return len(self.pos)
+
+    def _add(self, a, b, c, q_m, q_l, q_r, q_o, q_c, pi):
+        self.pos.append((a[0], a[1], b[0], b[1], c[0], c[1]))
+        self.sel.append((q_m, q_l, q_r, q_o, q_c % _FR_MOD, (-pi) % _FR_MOD))
+        self.vals.append((a[2] % _FR_MOD, b[2] % _FR_MOD, c[2] % _FR_MOD))
+
+    def add_addition_gate(self, a, b, c, pi=0):        # gate.rs:38-55
+        self._add(a, b, c, 0, 1, 1, _FR_MOD - 1, 0, pi)
+
+    def add_multiplication_gate(self, a, b, c, pi=0):  # gate.rs:57-74
+        self._add(a, b, c, 1, 0, 0, _FR_MOD - 1, 0, pi)
+
+    def add_constant_gate(self, a, b, c, pi=0, constant=None):
+        """gate.rs:76-94; Circuit::add_constant_gate takes the constant from a's value (circuit.rs:73-79), Gate::new_constant_gate
+        any constant."""
+        self._add(a, b, c, 0, 1, 0, 0, -(a[2] if constant is None else constant), pi)
+
+    def gate_table(self):
+        """-> pos (g, 6) uint32, sel (g, 6, 4) uint64, vals (g, 3, 4) uint64: the arrays of zkp_plonk_gates."""
+        g = len(self.pos)
+        pos = np.array(self.pos, dtype=np.uint32).reshape(g, 6)
+        sel = _fr_mont_rows([v for row in self.sel for v in row]).reshape(g, 6, 4)
+        vals = _fr_mont_rows([v for row in self.vals for v in row]).reshape(g, 3, 4)
+        return pos, sel, vals
+
+    def compile(self, srs_bases):
+        """Circuit::compile (circuit.rs:166-245) on the device -> PlonkProver."""
+        return PlonkProver.from_gates(srs_bases, *self.gate_table())
+
+
 class PlonkProver:
     """Round-by-round face of generate_proof (plonk/src/prover.rs:61-293); blinders and challenges are inputs."""
 
@@ -831,6 +899,45 @@ class PlonkProver:
         self._h = C.c_void_p()
         self.n = 1 << log_n
         _chk(lib().zkp_plonk_prover_create(srs_bases._h, log_n, ptrs, lens, _ptr(k1), _ptr(k2), C.byref(self._h)))
+
+    @classmethod
+    def from_gates(cls, srs_bases, pos, sel, vals):
+        """zkp_plonk_prover_create_from_gates: pos (g, 6) uint32, sel (g, 6, 4), vals (g, 3, 4) uint64 (PlonkCircuit.gate_table())."""
+        pos = _np(pos, np.uint32, (-1, 6))
+        g = pos.shape[0]
+        sel, vals = _np(sel, np.uint64, (g, 6, 4)), _np(vals, np.uint64, (g, 3, 4))
+        gt = _PlonkGates(g, pos.ctypes.data, sel.ctypes.data, vals.ctypes.data)
+        self = cls.__new__(cls)
+        self._bases = srs_bases  # keep alive
+        self._h = C.c_void_p()
+        _chk(lib().zkp_plonk_prover_create_from_gates(srs_bases._h, C.byref(gt), C.byref(self._h)))
+        self.gates = g
+        self.n = 1 << self.info()[0]
+        return self
+
+    def set_witness(self, vals, pi=None):
+        """Another witness for the circuit of from_gates: vals (g, 3, 4) uint64, pi (g, 4) as stored (None: unchanged)."""
+        vals = _np(vals, np.uint64, (-1, 3, 4))
+        pi = _np(pi, np.uint64, (vals.shape[0], 4)) if pi is not None else None
+        _chk(lib().zkp_plonk_prover_set_witness(self._h, _ptr(vals), _ptr(pi), vals.shape[0]))
+
+    def set_witness_dev(self, vals, gates, pi=None, stream=None):
+        """set_witness from torch CUDA tensors of 12 * gates (and 4 * gates) 64-bit words, read on `stream` (None: torch's current)."""
+        _chk(lib().zkp_plonk_prover_set_witness_dev(self._h, _dev_ptr(vals, 96 * gates), _dev_ptr(pi, 32 * gates) if pi is not None else None,
+                                                    gates, _stream_ptr(stream)))
+
+    def circuit_poly(self, name):
+        """The n coefficients (zero-padded) of one of CIRCUIT_POLYS as the prover holds it."""
+        out = np.zeros((self.n, 4), dtype=np.uint64)
+        ln = C.c_size_t(0)
+        _chk(lib().zkp_plonk_get_circuit_poly(self._h, CIRCUIT_POLYS.index(name), _ptr(out), self.n, C.byref(ln)))
+        return out
+
+    def info(self):
+        """-> (log_n, k1, k2)."""
+        log_n, k1, k2 = C.c_uint(0), np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+        _chk(lib().zkp_plonk_prover_info(self._h, C.byref(log_n), _ptr(k1), _ptr(k2)))
+        return int(log_n.value), k1, k2
 
     def prove(self, blinders):
         """generate_proof (plonk/src/prover.rs:61-293) with the reference's transcript; blinders = b1..b9 (9, 4)."""
