@@ -10,10 +10,6 @@
 #include "msm_plan.hpp"
 using namespace zkp;
 
-static const char* const kKnobs[] = {"ZKP_MSM_C", "ZKP_MSM_RANGE_LOG", "ZKP_MSM_FIRST_PCT", "ZKP_MSM_NCHUNK", "ZKP_SORT_LO_BITS",
-                                     "ZKP_MSM_NO_OVERLAP", "ZKP_MSM_SPLIT_LOG", "ZKP_MSM_FEED_RANGES", "ZKP_MSM_FEED_FIRST_PCT",
-                                     "ZKP_MSM_FEED_SECOND_PCT"};
-
 // slice offsets of bases expanded for window_bits w (zkp_g1_bases_precompute): equal slices of w bits when they tile 256
 // exactly, otherwise floor / ceil(256 / planes) bits
 static void expand(uint32_t w, uint32_t* planes, uint32_t* cmax, uint16_t* off) {
@@ -57,7 +53,7 @@ static const char* broken(const MsmPlan& p, const uint16_t* pre_off, uint64_t n,
     const MsmGeom& g = p.g;
     const size_t W = g.nwin, nb = g.nb;
     uint64_t sum = 0, longest = 0, cap = g.shared ? (p.nwin1 <= 12 ? 1ull << 24 : 1ull << 23) : n;
-    if (const int v = msm_env_int("ZKP_MSM_RANGE_LOG", 10, 30, 0)) cap = 1ull << v;
+    if (const long long v = knob_int(KNOB_MSM_RANGE_LOG)) cap = 1ull << v;
     else if (feed) cap = std::min<uint64_t>(cap, 1ull << msm_feed_ranges(n).range_log);
     for (uint64_t l : p.lens) {
         if (l == 0 || l > cap) return "a range is empty or longer than the cap";
@@ -66,7 +62,7 @@ static const char* broken(const MsmPlan& p, const uint16_t* pre_off, uint64_t n,
     }
     if (sum != n) return "the ranges do not add up to n";
     if (longest != p.range || g.ns != p.range) return "range is not the longest range";
-    if (p.overlap != (p.lens.size() > 1 && g.shared && !getenv("ZKP_MSM_NO_OVERLAP")) || p.nbuf != (p.overlap ? 2u : 1u)) return "overlap";
+    if (p.overlap != (p.lens.size() > 1 && g.shared && !knob_flag(KNOB_MSM_NO_OVERLAP)) || p.nbuf != (p.overlap ? 2u : 1u)) return "overlap";
     if (g.nwin != (g.shared ? count : count * p.nwin1) || g.n != (g.shared ? p.nwin1 * p.range : n)) return "windows / entries";
     for (uint32_t s = 0; s <= p.nwin1; s++)
         if (g.off[s] != (g.shared ? pre_off[s] : s * g.c)) return "slice offsets";
@@ -101,7 +97,7 @@ int main(int argc, char** argv) {
             printf("unreadable line: %s\n", line.c_str());
             return 2;
         }
-        for (const char* k : kKnobs) unsetenv(k);
+        for (int k = 0; k < KNOB_MSM_PLAN_END; k++) unsetenv(kKnobs[k].name);  // the knobs plan_msm and msm_feed_ranges read (knobs.hpp)
         if (strcmp(env, "-") != 0) {
             std::stringstream ss(env);
             for (std::string kv; std::getline(ss, kv, ';');) setenv(kv.substr(0, kv.find('=')).c_str(), kv.substr(kv.find('=') + 1).c_str(), 1);

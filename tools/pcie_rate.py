@@ -34,5 +34,5 @@ print(f"plain pageable H2D of the {32 * n / 2**20:.0f} MiB of scalars: {t_copy*1
 zkp.profile_reset(); zkp.profile_enable(True)
 for _ in range(5): zkp.msm_g1(bases, h)
 zkp.profile_enable(False)
-print("phases per MSM (host scalars, ZKP_MSM_FEED_RANGES=%s):" % os.environ.get("ZKP_MSM_FEED_RANGES", "4"),
+print("phases per MSM (host scalars, ZKP_MSM_FEED_RANGES=%s):" % os.environ.get("ZKP_MSM_FEED_RANGES", "unset"),
       {k: round(zkp.profile_read(k)[0] / 5, 3) for k in ("msm_digits", "msm_sort", "msm_accumulate", "msm_bucket_reduce", "msm_tail_host")})

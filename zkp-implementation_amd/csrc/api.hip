@@ -496,11 +496,7 @@ int get_radix_table(int log_r, int inverse, const typename NttOps<F>::W** out, h
 // without on one box (profiles/r02_m_ntt_twiddle_matrix.md): 2^18 -2 %, 2^21..2^23 -4 %, 2^24 -2.7 %, fifteen 2^18 -4.5 %; 2^25 and
 // 2^26 gain 1 % for 1 and 2 GiB per direction, which is not worth the memory
 static unsigned pass0_matrix_max_log() {
-    static const unsigned v = [] {
-        const char* e = getenv("ZKP_NTT_TW_MATRIX_MAX_LOG");
-        return e ? (unsigned)std::min(30, std::max(0, atoi(e))) : 24u;
-    }();
-    return v;
+    return (unsigned)knob_int(KNOB_NTT_TW_MATRIX_MAX_LOG);
 }
 
 template <class F>
@@ -517,7 +513,7 @@ int get_plan(unsigned log_n, int inverse, bool allow_wide, NttPlan<F>** out, hip
         // wide (radix-2^9, two-column) passes where they save a whole pass: 2^25 5.84 -> 4.42 ms, 2^26 11.47 -> 9.09 ms, 2^27 22.6 -> 19.3 ms,
         // fifteen 2^18 transforms (PLONK round 3) 2.11 -> 1.98 ms (profiles/r02_l_ntt_wide_pass.md).  Not for a lone small transform:
         // 2^17 would be 128 tiles on 256 CUs (0.047 against 0.042 ms): the caller allows it from 2^19 elements per launch.
-        if (pl.passes > 1 && allow_wide && !getenv("ZKP_NTT_NO_WIDE_PASS")) {
+        if (pl.passes > 1 && allow_wide && !knob_flag(KNOB_NTT_NO_WIDE_PASS)) {
             for (int maxr = NttOps<F>::MAX_PASS_LOG + 1; maxr <= NttOps<F>::WIDE_PASS_LOG; maxr++) {  // the narrowest radix that saves a pass
                 // radix 2^10 (single-column tiles, 32-byte runs) only while the data is cache-resident: 2^19 0.102 -> 0.092 ms, 2^20
                 // 0.173 -> 0.165 ms, but 2^28 45.1 -> 48.3 ms (profiles/r02_l_ntt_wide_pass.md)
@@ -937,22 +933,9 @@ int ensure_fixed_base_table(hipStream_t st) {
         for (int d = 1; d < ND; d++) pts[(size_t)w * ND + d] = pts[(size_t)w * ND + d - 1].add(base);
         base = pts[(size_t)w * ND + ND - 1].add(base);
     }
-    // batch-normalise: one inversion for all ZZZ (Montgomery's trick); none of these points is the identity
-    std::vector<HFq> pref(pts.size());
-    HFq acc = HFq::one();
-    for (size_t i = 0; i < pts.size(); i++) {
-        pref[i] = acc;
-        acc = acc * pts[i].zzz;
-    }
-    HFq inv = acc.inverse();
     std::vector<uint64_t> tab(pts.size() * 12);
-    for (size_t i = pts.size(); i-- > 0;) {
-        HFq zi3 = inv * pref[i];
-        inv = inv * pts[i].zzz;
-        HFq zi2 = (zi3 * pts[i].zz).sqr();
-        (pts[i].x * zi2).store(&tab[i * 12]);
-        (pts[i].y * zi3).store(&tab[i * 12 + 6]);
-    }
+    std::vector<uint8_t> inf(pts.size());  // (none of these points is the identity)
+    batch_to_affine(pts.data(), pts.size(), tab.data(), inf.data());
     ZCHK(ctx().fb_table.ensure(tab.size() * 8));
     HIPCHK(hipMemcpyAsync(ctx().fb_table.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -1300,7 +1283,7 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool check_only = fals
     SliceOffsets so;
     std::memset(&so, 0, sizeof so);
     uint32_t cmax = window_bits;
-    static const uint32_t balance_from = getenv("ZKP_MSM_BALANCE_FROM") ? (uint32_t)atoi(getenv("ZKP_MSM_BALANCE_FROM")) : 1u;  // tuning aid
+    const uint32_t balance_from = (uint32_t)knob_int(KNOB_MSM_BALANCE_FROM);  // tuning aid
     if (planes * window_bits - 256 < balance_from) {
         for (uint32_t s = 0; s <= planes; s++) so.off[s] = (uint16_t)(s * window_bits);
     } else {
@@ -1314,8 +1297,7 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool check_only = fals
         const size_t need = 128 * (size_t)planes * b->n;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
-        size_t budget = free_b ? free_b : ~(size_t)0;
-        if (const char* env = getenv("ZKP_SRS_EXPAND_MAX_BYTES")) budget = std::min<size_t>(budget, (size_t)strtoull(env, nullptr, 10));
+        const size_t budget = std::min<size_t>(free_b ? free_b : ~(size_t)0, (size_t)knob_int(KNOB_SRS_EXPAND_MAX_BYTES));
         auto too_large = [&](const char* why) {
             return fail(ZKP_E_NOMEM, "SRS expansion does not fit (" + std::string(why) + "): " + std::to_string(planes) + " planes x " +
                                          std::to_string(b->n) + " points x 128 B = " + std::to_string(need) + " bytes, " +
@@ -1517,24 +1499,29 @@ int msm_host_scalars(const zkp_bases* bases, const uint64_t* scalars, size_t n, 
     return msm_partial(bases, d_sc, n, st, r);
 }
 
-// the same over a handle that may be sharded: every device takes the scalars of its chunk (uploaded by its own worker thread
-// over its own PCIe link) and runs the whole Pippenger on it; the per-device partial sums (192 B each) come back to the host
-// with each device's result anyway, so the exchange of SURVEY 8e is a host-side EC add of `devices` points
+// One MSM over the chunks of a sharded handle: body(i, lo, len, &part) runs chunk i's share [lo, lo + len) of the n terms on that
+// chunk's worker (for_each_shard); a chunk at or past n and an empty chunk are skipped.  The per-device partial sums (192 B each) come
+// back to the host with each device's result anyway, so the exchange of SURVEY 8e is a host-side EC add of `devices` points, in chunk order
+int msm_over_shards(const zkp_bases* bases, size_t n, const std::function<int(size_t, size_t, size_t, HXyzz*)>& body, HXyzz* r) {
+    std::vector<HXyzz> part(bases->shards.size(), HXyzz::infinity());
+    ZCHK(for_each_shard(bases, [&](size_t i) {
+        const size_t lo = bases->shard_off[i], have = bases->shards[i]->n;
+        if (lo >= n || !have) return (int)ZKP_OK;
+        return body(i, lo, std::min(have, n - lo), &part[i]);
+    }));
+    *r = HXyzz::infinity();
+    for (const HXyzz& p : part) *r = r->add(p);
+    return ZKP_OK;
+}
+
+// msm_host_scalars over a handle that may be sharded: every device takes the scalars of its chunk (uploaded by its own worker thread
+// over its own PCIe link) and runs the whole Pippenger on it
 int msm_host_scalars_any(const zkp_bases* bases, const uint64_t* scalars, size_t n, HXyzz* r) {
     if (bases->shards.empty()) return msm_host_scalars(bases, scalars, n, r);
     if (n > bases->n) return fail(ZKP_E_SIZE, "more scalars than bases (kzg/src/scheme.rs:86)");
-    const size_t k = bases->shards.size();
-    std::vector<HXyzz> part(k, HXyzz::infinity());
-    ZCHK(for_each_shard(bases, [&](size_t i) {
-        const size_t lo = bases->shard_off[i];
-        if (lo >= n) return (int)ZKP_OK;
-        const size_t len = std::min(bases->shards[i]->n, n - lo);
-        return msm_host_scalars(bases->shards[i].get(), scalars + 4 * lo, len, &part[i]);
-    }));
-    HXyzz acc = HXyzz::infinity();
-    for (size_t i = 0; i < k; i++) acc = acc.add(part[i]);
-    *r = acc;
-    return ZKP_OK;
+    return msm_over_shards(bases, n, [&](size_t i, size_t lo, size_t len, HXyzz* part) {
+        return msm_host_scalars(bases->shards[i].get(), scalars + 4 * lo, len, part);
+    }, r);
 }
 
 }  // namespace
@@ -1611,23 +1598,17 @@ int zkp_msm_g1_sharded_dev_after(const zkp_bases* bases, const void* const* d_sc
             ZCHK(msm_partial(bases, reinterpret_cast<const Fr*>(d_scalars[0]), n, st, &acc));
         }
     } else {
-        const size_t k = bases->shards.size();
-        for (size_t i = 0; i < k; i++)
+        for (size_t i = 0; i < bases->shards.size(); i++)
             if (bases->shard_off[i] < n && bases->shards[i]->n && !d_scalars[i]) return fail(ZKP_E_ARG, "null scalar pointer for a chunk in use");
-        std::vector<HXyzz> part(k, HXyzz::infinity());
-        ZCHK(for_each_shard(bases, [&](size_t i) {
-            const size_t lo = bases->shard_off[i];
+        ZCHK(msm_over_shards(bases, n, [&](size_t i, size_t, size_t len, HXyzz* part) {
             const zkp_bases* sh = bases->shards[i].get();
-            if (lo >= n || !sh->n) return (int)ZKP_OK;
-            const size_t len = std::min(sh->n, n - lo);
             CTX_ENTER(sh->slot);
             // d_scalars[i] may come from a copy or kernel still in flight on another stream of this device (a resident tensor made
             // by .to(device) a moment ago): the slot's stream is non-blocking and would not wait for it
             ZCHK(order_after_producer(ctx().stream, ready_events ? ready_events[i] : nullptr));
             WsOrder ord(ctx().stream);
-            return msm_partial(sh, reinterpret_cast<const Fr*>(d_scalars[i]), len, ctx().stream, &part[i]);
-        }));
-        for (size_t i = 0; i < k; i++) acc = acc.add(part[i]);
+            return msm_partial(sh, reinterpret_cast<const Fr*>(d_scalars[i]), len, ctx().stream, part);
+        }, &acc));
     }
     acc.to_affine(out_xy, out_is_inf);
     return ZKP_OK;
@@ -1655,29 +1636,7 @@ int zkp_msm_g1_batch_dev(const zkp_bases* bases, const void* const* d_scalars, s
     std::vector<HXyzz> r(count);
     ZCHK(msm_partial_batch(bases, reinterpret_cast<const Fr* const*>(d_scalars), count, n, reinterpret_cast<hipStream_t>(stream),
                            r.data()));
-    // affine results with ONE field inversion for the whole batch (Montgomery's trick over the finite ZZZ): a Fermat inversion
-    // is ~23 us of host time, and a PLONK proof makes nine commitments in four batches
-    std::vector<HFq> prefix(count);
-    HFq run = HFq::one();
-    for (size_t m = 0; m < count; m++) {
-        prefix[m] = run;
-        if (!r[m].is_inf()) run = run * r[m].zzz;
-    }
-    HFq inv = run.inverse();
-    for (size_t m = count; m-- > 0;) {
-        if (r[m].is_inf()) {
-            std::memset(out_xy + 12 * m, 0, 96);
-            out_is_inf[m] = 1;
-            continue;
-        }
-        const HFq zi3 = inv * prefix[m];  // 1 / ZZZ_m
-        inv = inv * r[m].zzz;
-        HFq zi2 = zi3 * r[m].zz;          // ZZ / ZZZ = 1 / Z, squared below = 1 / ZZ
-        zi2 = zi2.sqr();
-        (r[m].x * zi2).store(out_xy + 12 * m);
-        (r[m].y * zi3).store(out_xy + 12 * m + 6);
-        out_is_inf[m] = 0;
-    }
+    batch_to_affine(r.data(), count, out_xy, out_is_inf);  // one field inversion for the batch: a PLONK proof makes nine commitments in four batches
     return ZKP_OK;
 } ZKP_CATCH_INT
 

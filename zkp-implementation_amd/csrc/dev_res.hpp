@@ -1,4 +1,5 @@
-// Owning handles of the HIP resources the host side holds: device buffers, pinned host buffers, streams and events.  Each type is
+// Owning handles of the HIP resources the host side holds: device buffers, pinned host buffers, streams and events, and the polled
+// wait on a stream (poll_or_sync, at the end).  Each type is
 // move-only and releases its resource in its destructor with `(void)hip...`.  The destructors never synchronise and never switch
 // device: an owner that may still have work in flight, or that lives on another device, drains it and makes its device current
 // first (~Ctx, zkp_plonk_prover_destroy, zkp_g1_bases_destroy).  Kernels and launch sites receive the raw handles (.p, .get(),
@@ -6,7 +7,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstddef>
+#include <cstdint>
 #include <string>
 #include <utility>
 
@@ -134,3 +137,22 @@ template <class T, class Buf = DevBuf> struct TypedBuf : Buf {  // the same, hol
     T* get() const { return static_cast<T*>(this->p); }
     operator T*() const { return get(); }
 };
+
+// Wait for the work on `st` whose end a kernel announces in pinned host memory (the MSM's result flags, the PLONK prover's sequence
+// number): the stream wait costs 30-60 us of wake-up (profiles/r05_k), so the host spins on done() instead -- a pause between two
+// looks, the clock every 1024 spins.  After POLL_TIMEOUT without the announcement (a kernel that faulted never writes it), or at
+// once when `poll` is false, the stream wait.  From the return on the kernels' writes to pinned memory are visible to the host:
+// done() reads with acquire loads.
+constexpr std::chrono::seconds POLL_TIMEOUT(2);
+template <class Done>
+int poll_or_sync(bool poll, hipStream_t st, Done done) {
+    if (poll) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint64_t spins = 0;; __builtin_ia32_pause()) {
+            if (done()) return ZKP_OK;
+            if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > POLL_TIMEOUT) break;
+        }
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    return e == hipSuccess ? ZKP_OK : hip_fail(e, "hipStreamSynchronize(st): ");
+}

@@ -12,10 +12,7 @@
 
 namespace {
 
-bool fri_zero_as_0() {
-    const char* e = getenv("ZKP_FRI_ZERO_AS_0");
-    return e && e[0] == '1';
-}
+bool fri_zero_as_0() { return knob_flag(KNOB_FRI_ZERO_AS_0); }
 
 size_t merkle_depth(size_t n) {
     size_t d = 0;
@@ -120,10 +117,8 @@ struct FriFrTraits {
     // tail kernel.  ZKP_FRI_FR_TAIL_LOG (0 .. FriFr::TAIL_LOG) overrides the default for measurements: 0 sends every layer through
     // the large-layer launches.
     static unsigned tail_log() {
-        const char* e = getenv("ZKP_FRI_FR_TAIL_LOG");
-        if (!e || !*e) return 9;
-        const long v = strtol(e, nullptr, 10);
-        return v < 0 ? 0u : v > FriFr::TAIL_LOG ? (unsigned)FriFr::TAIL_LOG : (unsigned)v;
+        static_assert(kKnobs[KNOB_FRI_FR_TAIL_LOG].hi == FriFr::TAIL_LOG, "knobs.hpp: the tail kernel's capacity");
+        return (unsigned)knob_int(KNOB_FRI_FR_TAIL_LOG);
     }
     static const char* phase(const char* name) { return name; }
     // fri_fr_merkle_levels_kernel: one input per lane, up to 8 more levels through LDS

@@ -207,7 +207,7 @@ struct MsmPass {
         MSM_TRACE(st, ridx, "combine");
         // buckets += parts, pairwise: split_log steps; a step with many adds runs one lane per add, a small one four (latency): msm.hpp
         const uint64_t cap = (uint64_t)g.nwin * g.nb;
-        static const uint64_t lane_from = getenv("ZKP_FOLD_LANE_MIN") ? strtoull(getenv("ZKP_FOLD_LANE_MIN"), nullptr, 10) : FOLD_LANE_MIN_ADDS;
+        const uint64_t lane_from = (uint64_t)knob_int(KNOB_FOLD_LANE_MIN);
         for (uint32_t t = 0; t < g.split_log; t++) {
             const unsigned pairs = 1u << (g.split_log - 1 - t), per = cap * pairs >= lane_from ? MSM_THREADS : MSM_THREADS / 4;  // adds per workgroup
             hipLaunchKernelGGL(per == MSM_THREADS ? msm_fold_parts_lane_kernel : msm_fold_parts_kernel, dim3((unsigned)((cap + per - 1) / per), pairs),
@@ -219,9 +219,9 @@ struct MsmPass {
     // that writes the c result points and the flag word of every bucket set to pinned host memory
     int reduce() {
         // tuning aids (A/B runs): workgroup size and count of the last-levels launch, and the per-array pair count from which it takes over
-        static const uint32_t tail_threads = getenv("ZKP_PYR_TAIL_THREADS") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_THREADS")) : PYR_TAIL_THREADS;
-        static const uint32_t tail_blocks = getenv("ZKP_PYR_TAIL_BLOCKS") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_BLOCKS")) : PYR_TAIL_BLOCKS;
-        static const uint32_t tail_half = getenv("ZKP_PYR_TAIL_HALF") ? (uint32_t)atoi(getenv("ZKP_PYR_TAIL_HALF")) : 64u;
+        static_assert(kKnobs[KNOB_PYR_TAIL_THREADS].dflt == PYR_TAIL_THREADS && kKnobs[KNOB_PYR_TAIL_BLOCKS].dflt == PYR_TAIL_BLOCKS, "knobs.hpp");
+        const uint32_t tail_threads = (uint32_t)knob_int(KNOB_PYR_TAIL_THREADS), tail_blocks = (uint32_t)knob_int(KNOB_PYR_TAIL_BLOCKS);
+        const uint32_t tail_half = (uint32_t)knob_int(KNOB_PYR_TAIL_HALF);
         if (tail_threads < 64 || tail_threads > 512 || (tail_threads & 63) || !tail_blocks || tail_blocks > 256 || !tail_half)
             return fail(ZKP_E_ARG, "ZKP_PYR_TAIL_THREADS must be a multiple of 64 up to 512, ZKP_PYR_TAIL_BLOCKS 1..256, ZKP_PYR_TAIL_HALF >= 1");
         for (size_t w = 0; w < W; w++) __atomic_store_n(result_flags + w, MSM_FLAG_PENDING, __ATOMIC_RELEASE);  // (the previous MSM's results were read before it returned)
@@ -247,7 +247,7 @@ struct MsmPass {
             while (tb > 1 && (uint64_t)tb * g.nwin * (tail_threads / 64) > max_waves) tb >>= 1;
             // test hook (tests/test_gpu_parity.py): ask the barrier for one arrival more than there are workgroups, with a short
             // time-out -- the path a workgroup that never became resident would take: MSM_TAIL_TIMEOUT flag, ZKP_E_DEVICE
-            const bool starve = getenv("ZKP_TEST_TAIL_STARVE") != nullptr;
+            const bool starve = knob_flag(KNOB_TEST_TAIL_STARVE);
             hipLaunchKernelGGL(msm_pyramid_tail_kernel, dim3(tb, g.nwin), dim3(tail_threads), 0, st, pyr[0], pyr[1], odd[0], odd[1], level_tail,
                                g.c, g.nb, cx.result.get(), result_out, result_flags, starve ? tb + 1 : tb, starve ? (1u << 12) : PYR_TAIL_SPIN_LIMIT);
         } else {  // every level already ran as its own launch: only the gathering is left
@@ -259,20 +259,13 @@ struct MsmPass {
     }
 };
 
-// Up to 2^24 entries per bucket set the host polls the result flags: the stream wait costs 30-60 us of wake-up per MSM (profiles/r05_k).
-// A kernel that never writes its flag (a fault) is caught by the stream wait the poll falls back to after two seconds.
+// Up to 2^24 entries per bucket set the host polls the result flags instead of waiting for the stream (poll_or_sync, dev_res.hpp)
 int wait_msm_result(const MsmGeom& g, const uint32_t* flags, hipStream_t st) {
-    bool seen = false;
-    if (g.n <= (1ull << 24) && !getenv("ZKP_MSM_NO_POLL")) {
-        const auto t_poll0 = std::chrono::steady_clock::now();
-        for (uint64_t spins = 0;; __builtin_ia32_pause()) {
-            bool all = true;
-            for (size_t w = 0; w < g.nwin && all; w++) all = (__atomic_load_n(flags + w, __ATOMIC_ACQUIRE) & MSM_FLAG_PENDING) == 0;
-            if ((seen = all)) break;
-            if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t_poll0 > std::chrono::seconds(2)) break;
-        }
-    }
-    if (!seen) HIPCHK(hipStreamSynchronize(st));  // the kernels' writes to the pinned buffer are visible to the host from here on
+    ZCHK(poll_or_sync(g.n <= (1ull << 24) && !knob_flag(KNOB_MSM_NO_POLL), st, [&] {
+        for (size_t w = 0; w < g.nwin; w++)
+            if (__atomic_load_n(flags + w, __ATOMIC_ACQUIRE) & MSM_FLAG_PENDING) return false;
+        return true;
+    }));
     for (size_t w = 0; w < g.nwin; w++)
         if (flags[w] & MSM_TAIL_TIMEOUT)
             return fail(ZKP_E_DEVICE, "bucket reduction: the workgroups of the last levels did not all become resident (device shared "
@@ -342,7 +335,7 @@ int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t
             if (chk[4 * k]) fprintf(stderr, "ZKP_MSM_CHECK class %d: %u violations, first (%u, %u)\n", k, chk[4 * k], chk[4 * k + 1], chk[4 * k + 2]);
     }
 #endif
-    if (count > 1 && !getenv("ZKP_POOL_NO_WARM")) host_pool().warm(std::chrono::microseconds(3000));  // the tails below run on the pool: wake it now
+    if (count > 1 && !knob_flag(KNOB_POOL_NO_WARM)) host_pool().warm(std::chrono::microseconds(3000));  // the tails below run on the pool: wake it now
     ZCHK(wait_msm_result(pass.g, pass.result_flags, st));
     msm_host_tail(reinterpret_cast<const uint32_t*>(pass.result_out), count, p.g.shared ? 1u : p.nwin1, p.g.c, out);  // (the pool's threads are in no context)
     return ZKP_OK;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/zkp_hip.h"
+#include "knobs.hpp"
 
 namespace zkp {
 
@@ -49,17 +50,12 @@ constexpr uint32_t PYR_BAR_STRIDE = 32;  // words between the barrier counters o
 // bucket lanes / bucket quads below which a bucket's run is split: enough for TWO generations of workgroups, so that the dispatcher
 // evens out the longest runs (PLONK 2^16: 3.83 -> 3.75 ms per proof, round 5)
 constexpr uint64_t SPLIT_FILL_LANES = 6 * 1024 * 64, SPLIT_FILL_QUADS = 2 * 1024 * 64 / 4 * 2;
-constexpr uint64_t FOLD_LANE_MIN_ADDS = 1ull << 15;  // adds in one fold launch from which one lane per add is used (profiles/r05_m_fold_lane.md)
 constexpr uint32_t MSM_MAX_SPLIT_LOG = 2;  // eight parts measured no better than four (2^16 single 0.535 against 0.529 ms, batches worse)
-
-inline int msm_env_int(const char* name, int lo, int hi, int dflt) {  // a tuning knob in [lo, hi], read on every call
-    const int v = getenv(name) ? atoi(getenv(name)) : dflt;
-    return v >= lo && v <= hi ? v : dflt;
-}
+static_assert(kKnobs[KNOB_MSM_SPLIT_LOG].hi == MSM_MAX_SPLIT_LOG, "ZKP_MSM_SPLIT_LOG's range");
 
 // Window width: only widths dividing 256 leave no sparse top window (others 4-9x slower, profiles/r01_window_sweep.txt); below 8 bits
 // a scalar has more than 32 windows (MsmGeom::off holds 36 offsets).
-inline unsigned pick_window_bits(size_t n) { return (unsigned)msm_env_int("ZKP_MSM_C", 8, 16, n >= 2048 ? 16 : 8); }
+inline unsigned pick_window_bits(size_t n) { return (unsigned)knob_int(KNOB_MSM_C, n >= 2048 ? 16 : 8); }
 
 // The shape of the bases an MSM runs over (zkp_bases): pre_c != 0 means pre_planes expanded planes, plane s = 2^pre_off[s] * P
 struct MsmBases { uint64_t n; uint32_t pre_c, pre_planes; const uint16_t* pre_off; };
@@ -75,10 +71,10 @@ inline MsmFeedRanges msm_feed_ranges(uint64_t n) {
     MsmFeedRanges f;
     uint64_t parts = 2;
     unsigned first_pct = n >= (1u << 21) ? 10 : 25;
-    const int ranges = msm_env_int("ZKP_MSM_FEED_RANGES", 1, 64, 0);  // equal ranges, as rounds 2-3 (tuning aid)
+    const int ranges = (int)knob_int(KNOB_MSM_FEED_RANGES);  // equal ranges, as rounds 2-3 (tuning aid)
     if (ranges) { parts = (uint64_t)ranges; first_pct = 0; }
-    first_pct = (unsigned)msm_env_int("ZKP_MSM_FEED_FIRST_PCT", 0, 90, (int)first_pct);  // share of the first range (0 = equal ranges)
-    const unsigned second_pct = (unsigned)msm_env_int("ZKP_MSM_FEED_SECOND_PCT", 0, 80, n >= (1u << 21) ? 30 : 0);  // a second short range
+    first_pct = (unsigned)knob_int(KNOB_MSM_FEED_FIRST_PCT, first_pct);  // share of the first range (0 = equal ranges)
+    const unsigned second_pct = (unsigned)knob_int(KNOB_MSM_FEED_SECOND_PCT, n >= (1u << 21) ? 30 : 0);  // a second short range
     if (first_pct) {
         f.first_len = std::max<uint64_t>(1024, (n * first_pct / 100) & ~(uint64_t)1023);
         if (second_pct) f.second_len = std::max<uint64_t>(1024, (n * second_pct / 100) & ~(uint64_t)1023);
@@ -105,7 +101,7 @@ struct MsmPlan {
     const char* error;          // the message of a refusal (plan_msm's return value != ZKP_OK)
 };
 
-// Everything msm_partial_batch decides before it touches the device.  Reads the ZKP_MSM_* / ZKP_SORT_LO_BITS tuning knobs.
+// Everything msm_partial_batch decides before it touches the device.  Reads the knobs of knobs.hpp before KNOB_MSM_PLAN_END.
 inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeedRanges* feed, MsmPlan* p) {
     auto refuse = [p](int code, const char* msg) { p->error = msg; return code; };
     p->lens.clear();
@@ -129,10 +125,10 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     if (shared) {
         const uint64_t max_range = bases.pre_planes <= 12 ? 1ull << 24 : 1ull << 23;
         uint64_t cap = feed ? std::min<uint64_t>(max_range, 1ull << feed->range_log) : max_range;
-        if (const int v = msm_env_int("ZKP_MSM_RANGE_LOG", 10, 30, 0)) cap = 1ull << v;
+        if (const long long v = knob_int(KNOB_MSM_RANGE_LOG)) cap = 1ull << v;
         uint64_t want_first = feed ? feed->first_len : 0;
         if (!feed && count == 1) {  // tuning aid (resident scalars): a short first range whose sort is the exposed one
-            const int v = msm_env_int("ZKP_MSM_FIRST_PCT", 1, 90, 0);
+            const long long v = knob_int(KNOB_MSM_FIRST_PCT);
             if (v) want_first = std::max<uint64_t>(1024, ((uint64_t)n * v / 100) & ~(uint64_t)1023);
         }
         uint64_t done = 0;  // short ranges first (they obey the range limit like the others), then the rest in equal ranges of at most `cap`
@@ -156,7 +152,7 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     g.interleave = (g.nwin > 1 && g.n <= (1ull << 22)) ? 1u : 0u;  // measured: +5 % at 2^22, 0 at 2^23, -5 % at 2^24
     const uint64_t entries = g.n;
     g.nchunk = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(1, (512 + g.nwin - 1) / g.nwin), (entries + 4095) / 4096);
-    if (const int v = msm_env_int("ZKP_MSM_NCHUNK", 1, 4096, 0)) g.nchunk = (uint32_t)std::min<uint64_t>((uint64_t)v, entries);
+    if (const long long v = knob_int(KNOB_MSM_NCHUNK)) g.nchunk = (uint32_t)std::min<uint64_t>((uint64_t)v, entries);
     g.chunk = (entries + g.nchunk - 1) / g.nchunk;
     // a bucket is oversized above 4x the average run; its pieces are no longer than an average run (they execute next to
     // the ordinary lanes, so a longer piece would become the critical path)
@@ -165,12 +161,12 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     SortGeom& sg = p->sg;
     // 2^19 buckets: 1024 partitions x 512 bins; 21..24-bit windows: 1024 bins per partition (measured, round 2)
     sg.lo_bits = std::min<uint32_t>(g.c >= 21 ? 10 : g.c >= 20 ? 9 : 8, g.c - 1);
-    if (const int lo = msm_env_int("ZKP_SORT_LO_BITS", 6, 10, 0); lo && (uint32_t)lo < g.c) sg.lo_bits = (uint32_t)lo;  // tuning aid
+    if (const long long lo = knob_int(KNOB_SORT_LO_BITS); lo && (uint32_t)lo < g.c) sg.lo_bits = (uint32_t)lo;  // tuning aid
     sg.nhi = g.nb >> sg.lo_bits;
     if (sg.nhi > SORT_MAX_PART) return refuse(ZKP_E_ARG, "window width above 24 bits is not supported by the sort");
     const size_t W = g.nwin, nb = g.nb, c = g.c;
     // Several scalar ranges: the (memory-bound) sort of range r+1 runs under the (issue-bound) accumulate of range r, on its own buffers
-    p->overlap = shared && range < n && !getenv("ZKP_MSM_NO_OVERLAP");
+    p->overlap = shared && range < n && !knob_flag(KNOB_MSM_NO_OVERLAP);
     const size_t nbuf = p->nbuf = p->overlap ? 2 : 1;
     // oversized-bucket bookkeeping (msm_order): at most n / LIMIT oversized buckets and n / PIECE + that many pieces
     p->over_cap = (uint32_t)std::min<uint64_t>(entries / 128 + 1, (uint64_t)nb);  // also bounds the saturated bin
@@ -182,7 +178,7 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     const uint64_t want_units = (uint64_t)g.n * g.nwin <= (1ull << 20) ? SPLIT_FILL_QUADS : SPLIT_FILL_LANES;
     if (range >= n) {
         while (g.split_log < MSM_MAX_SPLIT_LOG && (units << g.split_log) < want_units) g.split_log++;
-        g.split_log = (uint32_t)msm_env_int("ZKP_MSM_SPLIT_LOG", 0, (int)MSM_MAX_SPLIT_LOG, (int)g.split_log);  // tuning aid
+        g.split_log = (uint32_t)knob_int(KNOB_MSM_SPLIT_LOG, g.split_log);  // tuning aid
     }
     p->bytes = MsmSizes{4 * W * entries, nbuf * 4 * W * entries, 4 * W * ((size_t)g.nchunk * sg.nhi + 2 * sg.nhi + 1 + 512),
                         8 * W * entries, nbuf * 4 * W * (nb + 2), nbuf * 4 * W * nb, nbuf * p->over_bytes,

@@ -461,10 +461,7 @@ size_t runtime_slots() {
 }  // namespace
 
 bool ntt_should_shard(unsigned log_n) {
-    static const unsigned min_log = [] {
-        const char* e = getenv("ZKP_NTT_SHARD_MIN_LOG");
-        return e ? (unsigned)std::max(4, atoi(e)) : 24u;
-    }();
+    const unsigned min_log = (unsigned)knob_int(KNOB_NTT_SHARD_MIN_LOG);
     const size_t W = runtime_slots();
     ShardGeom g;
     return W > 1 && !(W & (W - 1)) && log_n >= min_log && shard_geometry(log_n, W, 0, &g) == ZKP_OK;

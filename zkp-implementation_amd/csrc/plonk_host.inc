@@ -100,8 +100,6 @@ int blind_polys(zkp_plonk_prover* p, int count, Fr* const* dst, const Fr* const*
     return ZKP_OK;
 }
 
-void batch_to_affine(const HXyzz* pts, size_t count, uint64_t* out_xy, uint8_t* out_inf);
-
 int commit_dev(const zkp_plonk_prover* p, const Fr* coeffs, uint64_t len, hipStream_t st, uint64_t out_xy[12], uint8_t* out_inf) {
     if (len > p->srs->n) return fail(ZKP_E_SIZE, "SRS shorter than the polynomial (kzg/src/scheme.rs:86)");
     HXyzz r;
@@ -152,10 +150,9 @@ struct EvalReq { const Fr* c; uint64_t len; HFr z; HFr* out; };
 // Wait for everything enqueued on `st`.  A proof has four small read-backs on its critical path (the accumulator's three totals, the
 // quotient's length, two sets of evaluations) and the runtime's stream wait costs 30-60 us of wake-up latency each time: a one-thread
 // kernel writes a sequence number into pinned memory behind the read-back and the host polls it (as the MSM does with its result
-// flags, profiles/r05_k); after two seconds, or without a pinned buffer (zkp_kzg_open's borrowed scratch), the stream wait.
+// flags: poll_or_sync, dev_res.hpp); without a pinned buffer (zkp_kzg_open's borrowed scratch), the stream wait.
 int wait_stream(const PlonkScratch& s, hipStream_t st) {
-    static const bool no_poll = getenv("ZKP_PLONK_NO_POLL") != nullptr;
-    if (!s.h_pin || no_poll) {
+    if (!s.h_pin || knob_flag(KNOB_PLONK_NO_POLL)) {
         HIPCHK(hipStreamSynchronize(st));
         return ZKP_OK;
     }
@@ -163,14 +160,7 @@ int wait_stream(const PlonkScratch& s, hipStream_t st) {
     const unsigned long long seq = ++*s.poll_seq;
     hipLaunchKernelGGL(stream_signal_kernel, dim3(1), dim3(1), 0, st, flag, seq);
     HIPCHK(hipGetLastError());
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint64_t spins = 0;;) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return ZKP_OK;
-        if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-        __builtin_ia32_pause();
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    return ZKP_OK;
+    return poll_or_sync(true, st, [=] { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq; });
 }
 
 int eval_many_dev(const PlonkScratch& s, const std::vector<EvalReq>& reqs, hipStream_t st) {
@@ -831,26 +821,13 @@ int build_para_table(zkp_plonk_prover* p) {
         }
         for (int k = 0; k < 4; k++) base = base.dbl();
     }
-    // normalise the table to affine (one inversion for all 960 entries) so that commit_para adds with the mixed formula
+    // normalise the table to affine (one inversion for all 960 entries) so that commit_para adds with the mixed formula; multiples
+    // d * 16^w * G0 with 0 < d * 16^w < r are never the identity
     const size_t cnt = p->para_table.size();
-    std::vector<HFq> prefix(cnt);
-    HFq run = HFq::one();
-    for (size_t i = 0; i < cnt; i++) {  // multiples d * 16^w * G0 with 0 < d * 16^w < r are never the identity
-        prefix[i] = run;
-        run = run * p->para_table[i].zzz;
-    }
-    HFq inv = run.inverse();
-    for (size_t i = cnt; i-- > 0;) {
-        HXyzz& e = p->para_table[i];
-        const HFq zi3 = inv * prefix[i];
-        inv = inv * e.zzz;
-        HFq zi2 = zi3 * e.zz;
-        zi2 = zi2.sqr();
-        e.x = e.x * zi2;
-        e.y = e.y * zi3;
-        e.zz = HFq::one();
-        e.zzz = HFq::one();
-    }
+    std::vector<uint64_t> xy(12 * cnt);
+    std::vector<uint8_t> inf(cnt);
+    batch_to_affine(p->para_table.data(), cnt, xy.data(), inf.data());
+    for (size_t i = 0; i < cnt; i++) p->para_table[i] = HXyzz::from_affine(&xy[12 * i], false);
     return ZKP_OK;
 }
 
@@ -866,32 +843,6 @@ HXyzz commit_para_xyzz(const zkp_plonk_prover* p, const HFr& para) {
 
 void commit_para(const zkp_plonk_prover* p, const HFr& para, uint64_t out_xy[12], uint8_t* out_inf) {
     commit_para_xyzz(p, para).to_affine(out_xy, out_inf);
-}
-
-// affine coordinates of `count` points with ONE field inversion (Montgomery's trick over the finite ZZZ; a Fermat inversion is
-// ~23 us of host time and the transcript of a proof needs six commit_para points at once)
-void batch_to_affine(const HXyzz* pts, size_t count, uint64_t* out_xy /* count x 12 */, uint8_t* out_inf) {
-    std::vector<HFq> prefix(count);
-    HFq run = HFq::one();
-    for (size_t i = 0; i < count; i++) {
-        prefix[i] = run;
-        if (!pts[i].is_inf()) run = run * pts[i].zzz;
-    }
-    HFq inv = run.inverse();
-    for (size_t i = count; i-- > 0;) {
-        if (pts[i].is_inf()) {
-            std::memset(out_xy + 12 * i, 0, 96);
-            out_inf[i] = 1;
-            continue;
-        }
-        const HFq zi3 = inv * prefix[i];
-        inv = inv * pts[i].zzz;
-        HFq zi2 = zi3 * pts[i].zz;
-        zi2 = zi2.sqr();
-        (pts[i].x * zi2).store(out_xy + 12 * i);
-        (pts[i].y * zi3).store(out_xy + 12 * i + 6);
-        out_inf[i] = 0;
-    }
 }
 
 }  // namespace
