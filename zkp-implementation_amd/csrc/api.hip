@@ -19,6 +19,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/zkp_hip.h"
@@ -212,66 +213,10 @@ void prof_host(const char* name, double ms) {
     prof_records().push_back(std::move(r));
 }
 
-// ----------------------------------------------------------------------------------------------------
-// host <-> device field views
-// ----------------------------------------------------------------------------------------------------
-template <class F> struct HostField;
-template <> struct HostField<Fr> {
-    typedef HFr H;
-    static Fr dev(const HFr& x) { Fr r; std::memcpy(r.l, x.l, 32); return r; }  // Montgomery on both sides
-    // twiddle form of the kernels (fr29.hpp): w * 2^261 mod r sliced into 29-bit limbs
-    static Fr29 tw(const HFr& x) {
-        HFr y = x;
-        for (int i = 0; i < 5; i++) y = y.dbl();
-        Fr29 r;
-        for (int i = 0; i < 9; i++) {
-            const int bit = 29 * i, w = bit >> 6, sh = bit & 63;
-            unsigned __int128 v = y.l[w];
-            if (w + 1 < 4) v |= (unsigned __int128)y.l[w + 1] << 64;
-            r.l[i] = (uint32_t)(v >> sh) & MASK29;
-        }
-        return r;
-    }
-    static HFr root(unsigned log_n) { return fr_root_of_unity(log_n); }
-    static constexpr int ID = 0;
-};
-template <> struct HostField<Gl> {
-    typedef HGl H;
-    static Gl dev(const HGl& x) { return Gl{x.from_mont().l[0]}; }  // device twiddles are canonical (ff.hpp)
-    static Gl tw(const HGl& x) { return dev(x); }
-    static HGl root(unsigned log_n) { return gl_root_of_unity(log_n); }
-    static constexpr int ID = 1;
-};
+enum { CLK_MSM_ACCUMULATE = 0, CLK_MAD_PROBE = 1, CLK_NTT_FR = 2, CLK_NTT_GL = 3, CLK_COUNT = 4 };
+static const char* const kClkNames[CLK_COUNT] = {"msm_accumulate", "mad_probe", "ntt_fr_pass", "ntt_gl_pass"};
 
-template <class F>
-struct NttPlan {
-    unsigned log_n = 0;
-    int passes = 0;
-    int r[4] = {0, 0, 0, 0};
-    const typename NttOps<F>::W* tw[4] = {nullptr, nullptr, nullptr, nullptr};
-    TypedBuf<typename NttOps<F>::W> inter_lo, inter_hi;
-    // inverse plans: inter_lo times 1/n.  Pass 0 multiplies every element by one inter-pass twiddle anyway, so reading it from
-    // this table applies the 1/n of the inverse transform for free (no scaling product at the store of the last pass)
-    TypedBuf<typename NttOps<F>::W> inter_lo_ninv;
-    uint32_t h = 0;
-    // passes 1 .. P-2 work on sub-problems of size M_p = n >> (r_0 + .. + r_{p-1}); up to 2^17 their inter-pass twiddles
-    // omega_{M_p}^e come from a direct table (one load, no product of a low and a high factor)
-    TypedBuf<typename NttOps<F>::W> direct[4];
-    // pass 0's inter-pass twiddles as a matrix shaped like the data (NttOps::PASS0_MATRIX); [1] = times 1/n.  Built on first use.
-    TypedBuf<F> tw_matrix[2];
-    typename HostField<F>::H n_inv;
-};
-
-template <class F>
-struct CosetCache {
-    bool valid = false;
-    unsigned log_n = 0;
-    int inverse = 0;
-    uint64_t key[4] = {0, 0, 0, 0};
-    uint64_t ckey[4] = {0, 0, 0, 0};  // the constant factor c of the table c * g^e
-    TypedBuf<typename NttOps<F>::W> lo, hi;  // grow-only
-    uint32_t h = 0;
-};
+#include "ntt_host.inc"  // HostField, NttState, run_ntt, run_ntt_axis0, get_coset_tables: the single-device NTT driver
 
 // One context per device SLOT.  zkp_init(device) makes a single slot; zkp_init_devices() one per listed HIP device (the same
 // device may be listed more than once: two slots on one GPU have separate workspaces and streams, which is how a 1-GPU box
@@ -297,18 +242,10 @@ struct Ctx {
     bool ws_pending = false;
     std::vector<ProfRec> prof;
     hipStream_t prof_last = nullptr;
-    // NTT
-    std::map<std::pair<int, int>, DevBuf> radix_tw[2];  // [field] (log_r, inverse) -> table
-    std::map<std::pair<unsigned, int>, NttPlan<Fr>> plans_fr;
-    std::map<std::pair<unsigned, int>, NttPlan<Gl>> plans_gl;
-    // a few (size, direction, coset) tables per field: a PLONK proof alternates forward and inverse transforms on the 4n
-    // coset, and a single entry was rebuilt four times per proof (115 us of pow_table launches)
-    static constexpr int COSET_WAYS = 8;
-    CosetCache<Fr> coset_fr[COSET_WAYS];
-    CosetCache<Gl> coset_gl[COSET_WAYS];
-    unsigned coset_victim[2] = {0, 0};
+    // NTT (ntt_host.inc)
+    NttState<Fr> ntt_fr;
+    NttState<Gl> ntt_gl;
     DevBuf ntt_scratch;
-    std::map<std::pair<unsigned, int>, DevBuf> axis0_tw[2];  // [field] (log_len, inverse) -> omega_len^e, e < len (run_ntt_axis0)
     // MSM
     DevBuf scalars, over;
     TypedBuf<uint32_t> digits, sorted, counts, start, perm, result;
@@ -337,8 +274,6 @@ struct Ctx {
         (void)hipDeviceSynchronize();
     }
 };
-enum { CLK_MSM_ACCUMULATE = 0, CLK_MAD_PROBE = 1, CLK_NTT_FR = 2, CLK_NTT_GL = 3, CLK_COUNT = 4 };
-static const char* const kClkNames[CLK_COUNT] = {"msm_accumulate", "mad_probe", "ntt_fr_pass", "ntt_gl_pass"};
 
 struct Runtime {
     std::mutex mu;              // guards `slots` (creation / shutdown); never held while a context works
@@ -363,6 +298,8 @@ thread_local Ctx* t_cur = nullptr;  // the context of the entry this thread is i
 Ctx& ctx() { return *t_cur; }
 std::vector<ProfRec>& prof_records() { return ctx().prof; }
 hipStream_t& prof_last_stream() { return ctx().prof_last; }
+template <class F> NttState<F>& ntt_state() { if constexpr (std::is_same<F, Fr>::value) return ctx().ntt_fr; else return ctx().ntt_gl; }
+DevBuf& ntt_scratch() { return ctx().ntt_scratch; }
 
 int create_slot_locked(int device);  // below zkp_init
 
@@ -430,449 +367,6 @@ template <class K>
 int allow_big_lds(K kernel) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                160 * 1024));
-    return ZKP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// NTT driver
-// ----------------------------------------------------------------------------------------------------
-template <class F>
-std::map<std::pair<unsigned, int>, NttPlan<F>>& plan_map();
-template <> std::map<std::pair<unsigned, int>, NttPlan<Fr>>& plan_map<Fr>() { return ctx().plans_fr; }
-template <> std::map<std::pair<unsigned, int>, NttPlan<Gl>>& plan_map<Gl>() { return ctx().plans_gl; }
-template <class F> CosetCache<F>* coset_cache();
-template <> CosetCache<Fr>* coset_cache<Fr>() { return ctx().coset_fr; }
-template <> CosetCache<Gl>* coset_cache<Gl>() { return ctx().coset_gl; }
-
-template <class F>
-int make_pow_table(const typename HostField<F>::H& base, const typename HostField<F>::H& c, uint32_t shift,
-                   uint32_t count, typename NttOps<F>::W* out, hipStream_t st) {
-    hipLaunchKernelGGL(pow_table_kernel<F>, dim3((count + 255) / 256), dim3(256), 0, st, HostField<F>::dev(base),
-                       HostField<F>::dev(c), shift, count, out);
-    HIPCHK(hipGetLastError());
-    return ZKP_OK;
-}
-
-// A cached table of w^e, e < count, shared by later calls on any stream: filled and drained before the caller publishes it.  On a
-// failure st is drained too before the table is freed, since its fill kernel may still be queued.
-template <class F>
-int build_pow_table(const typename HostField<F>::H& w, uint32_t count, DevBuf* out, hipStream_t st) {
-    typedef typename NttOps<F>::W W;
-    DevBuf tab;
-    ZCHK(tab.ensure(sizeof(W) * count));
-    int rc = make_pow_table<F>(w, HostField<F>::H::one(), 0, count, static_cast<W*>(tab.p), st);
-    if (rc == ZKP_OK) {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize(st): ");
-    }
-    if (rc != ZKP_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    *out = std::move(tab);
-    return ZKP_OK;
-}
-
-template <class F>
-int get_radix_table(int log_r, int inverse, const typename NttOps<F>::W** out, hipStream_t st) {
-    typedef typename HostField<F>::H H;
-    typedef typename NttOps<F>::W W;
-    auto& m = ctx().radix_tw[HostField<F>::ID];
-    auto key = std::make_pair(log_r, inverse);
-    auto it = m.find(key);
-    if (it == m.end()) {
-        uint32_t count = log_r ? (1u << (log_r - 1)) : 1u;
-        H w = HostField<F>::root((unsigned)log_r);
-        if (inverse) w = w.inverse();
-        DevBuf tab;
-        ZCHK(build_pow_table<F>(w, count, &tab, st));
-        it = m.emplace(key, std::move(tab)).first;
-    }
-    *out = static_cast<const W*>(it->second.p);
-    return ZKP_OK;
-}
-
-// largest transform whose pass-0 twiddles are kept as a matrix (32 B per element per direction: 512 MiB at 2^24).  Measured with and
-// without on one box (profiles/r02_m_ntt_twiddle_matrix.md): 2^18 -2 %, 2^21..2^23 -4 %, 2^24 -2.7 %, fifteen 2^18 -4.5 %; 2^25 and
-// 2^26 gain 1 % for 1 and 2 GiB per direction, which is not worth the memory
-static unsigned pass0_matrix_max_log() {
-    return (unsigned)knob_int(KNOB_NTT_TW_MATRIX_MAX_LOG);
-}
-
-template <class F>
-int get_plan(unsigned log_n, int inverse, bool allow_wide, NttPlan<F>** out, hipStream_t st) {
-    typedef typename HostField<F>::H H;
-    typedef typename NttOps<F>::W W;
-    auto& m = plan_map<F>();
-    auto key = std::make_pair(log_n, inverse | (allow_wide ? 2 : 0));
-    auto it = m.find(key);
-    if (it == m.end()) {
-        NttPlan<F> pl;
-        pl.log_n = log_n;
-        pl.passes = (int)log_n <= NttOps<F>::MAX_TILE_LOG ? 1 : (int)((log_n + NttOps<F>::MAX_PASS_LOG - 1) / NttOps<F>::MAX_PASS_LOG);
-        // wide (radix-2^9, two-column) passes where they save a whole pass: 2^25 5.84 -> 4.42 ms, 2^26 11.47 -> 9.09 ms, 2^27 22.6 -> 19.3 ms,
-        // fifteen 2^18 transforms (PLONK round 3) 2.11 -> 1.98 ms (profiles/r02_l_ntt_wide_pass.md).  Not for a lone small transform:
-        // 2^17 would be 128 tiles on 256 CUs (0.047 against 0.042 ms): the caller allows it from 2^19 elements per launch.
-        if (pl.passes > 1 && allow_wide && !knob_flag(KNOB_NTT_NO_WIDE_PASS)) {
-            for (int maxr = NttOps<F>::MAX_PASS_LOG + 1; maxr <= NttOps<F>::WIDE_PASS_LOG; maxr++) {  // the narrowest radix that saves a pass
-                // radix 2^10 (single-column tiles, 32-byte runs) only while the data is cache-resident: 2^19 0.102 -> 0.092 ms, 2^20
-                // 0.173 -> 0.165 ms, but 2^28 45.1 -> 48.3 ms (profiles/r02_l_ntt_wide_pass.md)
-                if ((int)log_n > NttOps<F>::wide_max_log_n(maxr)) break;
-                const int wide = (int)((log_n + maxr - 1) / maxr);
-                if (wide < pl.passes) pl.passes = wide;
-            }
-        }
-        int base = (int)log_n / pl.passes, rem = (int)log_n % pl.passes;
-        for (int p = 0; p < pl.passes; p++) pl.r[p] = base + (p < rem ? 1 : 0);
-        for (int p = 0; p < pl.passes; p++) ZCHK(get_radix_table<F>(pl.r[p], inverse, &pl.tw[p], st));
-        H w = HostField<F>::root(log_n);
-        if (inverse) w = w.inverse();
-        H two = H::from_u64(2), ninv = H::one(), half = two.inverse();
-        for (unsigned i = 0; i < log_n; i++) ninv = ninv * half;
-        pl.n_inv = ninv;
-        if (pl.passes > 1) {
-            pl.h = (log_n + 1) / 2;
-            uint32_t nlo = 1u << pl.h, nhi = 1u << (log_n - pl.h);
-            // a plan that fails half-way is not cached, and `pl` gives back what it had allocated: the kernels filling the
-            // tables may still be queued on st, so drain it first
-            auto build = [&]() -> int {
-                ZCHK(pl.inter_lo.ensure(sizeof(W) * nlo));
-                ZCHK(pl.inter_hi.ensure(sizeof(W) * nhi));
-                ZCHK(make_pow_table<F>(w, H::one(), 0, nlo, pl.inter_lo.get(), st));
-                ZCHK(make_pow_table<F>(w, H::one(), pl.h, nhi, pl.inter_hi.get(), st));
-                if (inverse) {
-                    ZCHK(pl.inter_lo_ninv.ensure(sizeof(W) * nlo));
-                    ZCHK(make_pow_table<F>(w, ninv, 0, nlo, pl.inter_lo_ninv.get(), st));
-                }
-                unsigned outer = pl.r[0];
-                for (int p = 1; p + 1 < pl.passes; p++) {
-                    const unsigned log_m = log_n - outer;
-                    if (log_m <= 17) {
-                        ZCHK(pl.direct[p].ensure(sizeof(W) << log_m));
-                        ZCHK(make_pow_table<F>(w, H::one(), outer, 1u << log_m, pl.direct[p].get(), st));  // w^(e << outer) = omega_M^e
-                    }
-                    outer += pl.r[p];
-                }
-                HIPCHK(hipStreamSynchronize(st));
-                return ZKP_OK;
-            };
-            if (const int rc = build(); rc != ZKP_OK) {
-                (void)hipStreamSynchronize(st);
-                (void)hipGetLastError();
-                return rc;
-            }
-        }
-        it = m.emplace(key, std::move(pl)).first;
-    }
-    *out = &it->second;
-    return ZKP_OK;
-}
-
-// two-level table of c * g^idx, idx < 2^log_n
-template <class F>
-int get_coset_tables(unsigned log_n, int inverse, const uint64_t* coset, const typename HostField<F>::H& c,
-                     PowTab<F>* out, hipStream_t st) {
-    typedef typename HostField<F>::H H;
-    typedef typename NttOps<F>::W W;
-    constexpr int NL = sizeof(H) / 8;
-    CosetCache<F>* ways = coset_cache<F>();
-    uint64_t key[4] = {0, 0, 0, 0}, ckey[4] = {0, 0, 0, 0};
-    std::memcpy(key, coset, 8 * NL);
-    std::memcpy(ckey, c.l, 8 * NL);
-    int way = -1;
-    for (int i = 0; i < Ctx::COSET_WAYS && way < 0; i++)
-        if (ways[i].valid && ways[i].log_n == log_n && ways[i].inverse == inverse && std::memcmp(ways[i].key, key, sizeof key) == 0 &&
-            std::memcmp(ways[i].ckey, ckey, sizeof ckey) == 0)
-            way = i;
-    const bool hit = way >= 0;
-    if (!hit) {  // an unused entry, else round-robin (tables still in use by enqueued kernels are rewritten in stream order)
-        for (int i = 0; i < Ctx::COSET_WAYS && way < 0; i++)
-            if (!ways[i].valid) way = i;
-        if (way < 0) way = (int)(ctx().coset_victim[HostField<F>::ID]++ % Ctx::COSET_WAYS);
-    }
-    CosetCache<F>& cc = ways[way];
-    if (!hit) {
-        cc.valid = false;
-        uint32_t h = (log_n + 1) / 2;
-        uint32_t nlo = 1u << h, nhi = 1u << (log_n - h);
-        // a failing ensure leaves an empty (invalid, capacity 0) entry behind, never a dangling pointer with a stale capacity
-        ZCHK(cc.lo.ensure(sizeof(W) * nlo));
-        ZCHK(cc.hi.ensure(sizeof(W) * nhi));
-        H g = H::load(coset);
-        if (inverse) g = g.inverse();
-        ZCHK(make_pow_table<F>(g, c, 0, nlo, cc.lo.get(), st));
-        ZCHK(make_pow_table<F>(g, H::one(), h, nhi, cc.hi.get(), st));
-        cc.h = h;
-        cc.log_n = log_n;
-        cc.inverse = inverse;
-        std::memcpy(cc.key, key, sizeof key);
-        std::memcpy(cc.ckey, ckey, sizeof ckey);
-        cc.valid = true;
-    }
-    out->lo = cc.lo.get();
-    out->hi = cc.hi.get();
-    out->h = cc.h;
-    return ZKP_OK;
-}
-
-template <class F>
-ScaleSpec<F> no_scale() {
-    ScaleSpec<F> s;
-    std::memset(&s, 0, sizeof s);
-    s.mode = SCALE_NONE;
-    return s;
-}
-
-// Optional extras of a batched transform (the local pieces of the multi-GPU four-step NTT, zkp_hip/dist.py)
-struct NttIo {
-    const NttRemap* in_remap = nullptr;   // gathered input: logical element e of transform b at ntt_phys(...)
-    const NttRemap* out_remap = nullptr;  // scattered output (same mapping on the natural output index)
-    unsigned tw_log_n = 0;                // != 0: output k of transform b is multiplied by omega_{2^tw_log_n}^(+-(tw_row0 + b) k)
-    uint64_t tw_row0 = 0;
-};
-
-template <class F>
-int run_ntt(const F* d_in, F* d_data, unsigned log_n, size_t batch, int inverse, const uint64_t* coset, hipStream_t st,
-            const NttIo* io = nullptr) {
-    typedef typename HostField<F>::H H;
-    if (log_n > 32) return fail(ZKP_E_ARG, "log_n > 32 (two-adicity of the field)");
-    if (batch == 0 || log_n == 0) return ZKP_OK;  // size-1 transform is the identity (n^-1 = coset^0 = 1)
-    if (batch > 65535) return fail(ZKP_E_ARG, "batch > 65535");
-    inverse = inverse ? 1 : 0;
-    NttPlan<F>* pl = nullptr;
-    ZCHK(get_plan<F>(log_n, inverse, ((uint64_t)batch << log_n) >= (1ull << 19), &pl, st));
-    const uint64_t n = 1ull << log_n;
-    ScaleSpec<F> pre = no_scale<F>(), post = no_scale<F>();
-    const bool four_step_tw = io && io->tw_log_n != 0;
-    if (four_step_tw) {
-        if (coset) return fail(ZKP_E_ARG, "a coset and a four-step twiddle cannot be combined");
-        if (io->tw_log_n > 32 || ((io->tw_row0 + batch - 1) * (n - 1)) >> io->tw_log_n)
-            return fail(ZKP_E_ARG, "four-step twiddle exponent (row0 + batch - 1) * (n - 1) must stay below 2^tw_log_n");
-        post.mode = SCALE_POW_ROW;
-        post.row0 = io->tw_row0;
-        const H w = HostField<F>::root(io->tw_log_n);  // get_coset_tables inverts the base itself when inverse != 0
-        ZCHK(get_coset_tables<F>(io->tw_log_n, inverse, w.l, inverse ? pl->n_inv : H::one(), &post.t, st));  // 1/n rides along
-    } else if (coset) {
-        if (!inverse) {
-            pre.mode = SCALE_POW;
-            ZCHK(get_coset_tables<F>(log_n, 0, coset, H::one(), &pre.t, st));
-        } else {
-            post.mode = SCALE_POW;
-            ZCHK(get_coset_tables<F>(log_n, 1, coset, pl->n_inv, &post.t, st));
-        }
-    } else if (inverse && pl->passes == 1) {
-        post.mode = SCALE_CONST;
-        post.c = HostField<F>::tw(pl->n_inv);
-    }
-    const bool ninv_in_pass0 = inverse && !coset && !four_step_tw && pl->passes > 1;  // 1/n rides on pass 0's inter-pass twiddles
-    constexpr int LOG_T = NttOps<F>::LOG_T;
-    typedef typename NttOps<F>::E E;
-    typedef typename NttOps<F>::W W;
-    const int P = pl->passes;
-    const F* cur_in = d_in;
-    F* work = d_data;
-    NttRemap no_remap;
-    std::memset(&no_remap, 0, sizeof no_remap);
-    if (P > 1) {
-        ZCHK(ctx().ntt_scratch.ensure(sizeof(F) * n * batch));
-        work = reinterpret_cast<F*>(ctx().ntt_scratch.p);
-    }
-    unsigned log_outer = 0;
-    for (int p = 0; p + 1 < P; p++) {
-        NttStridedParams<F> sp;
-        std::memset(&sp, 0, sizeof sp);
-        sp.in = cur_in;
-        sp.out = work;
-        sp.tw = pl->tw[p];
-        sp.n = n;
-        sp.inner = n >> (log_outer + pl->r[p]);
-        sp.log_r = pl->r[p];
-        if (pl->direct[p].p) {
-            sp.tw_stride_log = 0;
-            sp.inter.lo = pl->direct[p].get();
-            sp.inter.hi = pl->direct[p].get();  // never read: every exponent is below 2^h
-            sp.inter.h = log_n - log_outer;
-        } else {
-            sp.tw_stride_log = log_outer;
-            sp.inter.lo = ((p == 0 && ninv_in_pass0) ? pl->inter_lo_ninv : pl->inter_lo).get();
-            sp.inter.hi = pl->inter_hi.get();
-            sp.inter.h = pl->h;
-        }
-        if (p == 0 && NttOps<F>::PASS0_MATRIX && log_n <= pass0_matrix_max_log()) {
-            TypedBuf<F>& mat = pl->tw_matrix[ninv_in_pass0 ? 1 : 0];
-            if (!mat.p) {  // (the two-level tables set above are what the matrix is made from)
-                // An optimisation, 32 B per element held until zkp_shutdown (512 MiB per direction at 2^24): when the device has
-                // no room for it the transform keeps the two-level tables (one more product per element) instead of failing
-                // The plan is cached: the matrix is published in it only once it is filled -- a failed fill must not leave a
-                // non-null table of garbage behind for every later transform of this size
-                TypedBuf<F> fresh;
-                if (hipMalloc(&fresh.p, sizeof(F) * n) != hipSuccess) {  // (not ensure: that would set the error message of a call that succeeds)
-                    (void)hipGetLastError();
-                } else {
-                    hipLaunchKernelGGL(twiddle_matrix_kernel<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sp.inter, (uint64_t)n,
-                                       (uint64_t)sp.inner, fresh.get());
-                    hipError_t fe = hipGetLastError();
-                    if (fe == hipSuccess) fe = hipStreamSynchronize(st);  // shared by later calls on any stream
-                    if (fe != hipSuccess) return fail(ZKP_E_DEVICE, std::string("twiddle matrix: ") + hipGetErrorString(fe));
-                    fresh.cap = sizeof(F) * n;
-                    mat = std::move(fresh);
-                }
-            }
-            sp.tw_matrix = mat.get();
-        }
-        sp.pre = p == 0 ? pre : no_scale<F>();
-        sp.clk = clk_record(HostField<F>::ID == 0 ? CLK_NTT_FR : CLK_NTT_GL);
-        sp.remap = (p == 0 && io && io->in_remap) ? *io->in_remap : no_remap;
-        const size_t R = 1ull << pl->r[p];
-        const int log_t = NttOps<F>::log_t_of(pl->r[p]);
-        const size_t lds = sizeof(E) * (R << log_t) + sizeof(W) * (R / 2);
-        const uint64_t tiles = (n >> pl->r[p]) >> log_t;
-        {
-            ProfScope ps(HostField<F>::ID == 0 ? "ntt_fr_pass" : "ntt_gl_pass", st, p > 0);  // passes of one transform are adjacent
-            const dim3 grid((unsigned)tiles, (unsigned)batch), block(NttOps<F>::THREADS);
-            constexpr int T0 = NttOps<F>::LOG_T;  // tile widths: T0 (radix <= MAX_PASS_LOG) and, where the field has wide passes, T0 - 1, T0 - 2
-            constexpr bool WIDE = NttOps<F>::WIDE_PASS_LOG > NttOps<F>::MAX_PASS_LOG;
-            if (!WIDE || log_t == T0)
-                hipLaunchKernelGGL((ntt_pass_strided<F, T0>), grid, block, lds, st, sp);
-            else if (log_t == T0 - 1)
-                hipLaunchKernelGGL((ntt_pass_strided<F, (WIDE ? T0 - 1 : T0)>), grid, block, lds, st, sp);
-            else
-                hipLaunchKernelGGL((ntt_pass_strided<F, (WIDE ? T0 - 2 : T0)>), grid, block, lds, st, sp);
-        }
-        HIPCHK(hipGetLastError());
-        cur_in = work;
-        log_outer += pl->r[p];
-    }
-    NttLastParams<F> lp;
-    std::memset(&lp, 0, sizeof lp);
-    lp.in = cur_in;
-    lp.out = d_data;
-    lp.tw = pl->tw[P - 1];
-    lp.n = n;
-    lp.log_r = pl->r[P - 1];
-    lp.log_r0 = P > 1 ? pl->r[0] : 0;
-    lp.log_m = 0;
-    for (int p = 1; p + 1 < P; p++) lp.log_m += pl->r[p];
-    lp.log_r1 = P == 4 ? pl->r[1] : lp.log_m;
-    lp.t_log = std::min<uint32_t>((uint32_t)NttOps<F>::log_t_of((int)lp.log_r), lp.log_r0);
-    lp.pre = P == 1 ? pre : no_scale<F>();
-    lp.post = post;
-    lp.remap = (P == 1 && io && io->in_remap) ? *io->in_remap : no_remap;
-    lp.out_remap = (io && io->out_remap) ? *io->out_remap : no_remap;
-    lp.clk = clk_record(HostField<F>::ID == 0 ? CLK_NTT_FR : CLK_NTT_GL);
-    {
-        const size_t R = 1ull << lp.log_r, T = 1ull << lp.t_log;
-        const size_t stride = T > 1 ? T + NttOps<F>::PAD : 1;
-        const size_t lds = sizeof(E) * (R * stride) + sizeof(W) * (R / 2);
-        const uint64_t tiles = (1ull << (lp.log_r0 - lp.t_log)) << lp.log_m;
-        ProfScope ps(HostField<F>::ID == 0 ? "ntt_fr_pass" : "ntt_gl_pass", st, P > 1);
-        hipLaunchKernelGGL(ntt_pass_last<F>, dim3((unsigned)tiles, (unsigned)batch), dim3(NttOps<F>::THREADS), lds, st, lp);
-        HIPCHK(hipGetLastError());
-    }
-    return ZKP_OK;
-}
-
-template <class F>
-int run_ntt(F* d_data, unsigned log_n, size_t batch, int inverse, const uint64_t* coset, hipStream_t st) {
-    return run_ntt<F>(d_data, d_data, log_n, batch, inverse, coset, st, nullptr);
-}
-
-// Transforms of length 2^log_len along axis 0 of a row-major matrix [2^log_len][cols] (the columns are the contiguous
-// direction), natural order in and out, every output (k, b) multiplied by omega_{2^tw_log_n}^(+-(col0 + b) k) when
-// tw_log_n != 0 and by 1/2^log_len when inverse.  One or two strided passes (ntt_pass_strided): the second one stores the rows
-// in natural order and applies the twiddle, so the matrix is read and written exactly once per pass and never transposed.
-// This is the column half of the multi-GPU four-step transform: the all-to-all delivers [all rows][my columns].
-template <class F>
-int run_ntt_axis0(const F* d_in, F* d_out, unsigned log_len, size_t cols, int inverse, unsigned tw_log_n, uint64_t col0,
-                  hipStream_t st) {
-    typedef typename HostField<F>::H H;
-    typedef typename NttOps<F>::E E;
-    typedef typename NttOps<F>::W W;
-    constexpr int LOG_T = NttOps<F>::LOG_T;
-    constexpr int MAXR = NttOps<F>::MAX_PASS_LOG;
-    if (log_len == 0 || log_len > 2 * (unsigned)MAXR) return fail(ZKP_E_ARG, "axis-0 transform length out of range");
-    if (cols == 0 || (cols & (cols - 1)) || cols < (1u << LOG_T)) return fail(ZKP_E_ARG, "cols must be a power of two >= 4");
-    inverse = inverse ? 1 : 0;
-    const uint64_t L = 1ull << log_len, total = L * cols;
-    unsigned col_bits = 0;
-    while ((1ull << col_bits) < cols) col_bits++;
-    if (tw_log_n > 32 || (tw_log_n && (((col0 + cols - 1) * (L - 1)) >> tw_log_n)))
-        return fail(ZKP_E_ARG, "four-step twiddle exponent (col0 + cols - 1) * (len - 1) must stay below 2^tw_log_n");
-    const int P = log_len <= (unsigned)MAXR ? 1 : 2;
-    const int r0 = P == 1 ? (int)log_len : (int)(log_len + 1) / 2, r1 = (int)log_len - r0;
-    // final factor table: c * base^e with c = 1/len for the inverse; base = the N-th root (or 1: a constant table)
-    H ninv = H::one();
-    if (inverse) {
-        const H half = H::from_u64(2).inverse();
-        for (unsigned i = 0; i < log_len; i++) ninv = ninv * half;
-    }
-    PowTab<F> fin;
-    {
-        const H base = tw_log_n ? HostField<F>::root(tw_log_n) : H::one();
-        ZCHK(get_coset_tables<F>(tw_log_n ? tw_log_n : log_len, inverse, base.l, ninv, &fin, st));
-    }
-    NttStridedParams<F> sp;
-    std::memset(&sp, 0, sizeof sp);
-    sp.n = total;
-    sp.pre = no_scale<F>();
-    sp.col_bits = col_bits;
-    sp.clk = clk_record(HostField<F>::ID == 0 ? CLK_NTT_FR : CLK_NTT_GL);
-    auto launch = [&](int log_r) {
-        const size_t R = 1ull << log_r;
-        const size_t lds = sizeof(E) * (R << LOG_T) + sizeof(W) * (R / 2);
-        const uint64_t tiles = (total >> log_r) >> LOG_T;
-        ProfScope ps(HostField<F>::ID == 0 ? "ntt_fr_pass" : "ntt_gl_pass", st);
-        hipLaunchKernelGGL((ntt_pass_strided<F, NttOps<F>::LOG_T>), dim3((unsigned)tiles, 1), dim3(NttOps<F>::THREADS), lds, st, sp);
-    };
-    if (P == 1) {
-        ZCHK(get_radix_table<F>(r0, inverse, &sp.tw, st));
-        sp.in = d_in;
-        sp.out = d_out;
-        sp.inner = cols;
-        sp.log_r = (uint32_t)r0;
-        sp.axis0_last = 1;
-        sp.tw_on = tw_log_n ? 1u : 0u;
-        sp.outer_count = 1;
-        sp.col0 = col0;
-        sp.inter = fin;
-        launch(r0);
-    } else {
-        // inter-pass twiddles omega_len^(k0 * d1): a direct table of `len` entries per (length, direction)
-        auto key = std::make_pair(log_len, inverse);
-        auto& cache = ctx().axis0_tw[HostField<F>::ID];
-        auto it = cache.find(key);
-        if (it == cache.end()) {
-            H w = HostField<F>::root(log_len);
-            if (inverse) w = w.inverse();
-            DevBuf tab;
-            ZCHK(build_pow_table<F>(w, (uint32_t)L, &tab, st));
-            it = cache.emplace(key, std::move(tab)).first;
-        }
-        ZCHK(ctx().ntt_scratch.ensure(sizeof(F) * total));
-        F* work = reinterpret_cast<F*>(ctx().ntt_scratch.p);
-        ZCHK(get_radix_table<F>(r0, inverse, &sp.tw, st));
-        sp.in = d_in;
-        sp.out = work;
-        sp.inner = (uint64_t)cols << r1;
-        sp.log_r = (uint32_t)r0;
-        sp.tw_stride_log = 0;
-        sp.inter.lo = static_cast<const W*>(it->second.p);
-        sp.inter.hi = sp.inter.lo;  // never read: every exponent is below 2^h
-        sp.inter.h = log_len;
-        launch(r0);
-        ZCHK(get_radix_table<F>(r1, inverse, &sp.tw, st));
-        sp.in = work;
-        sp.out = d_out;
-        sp.inner = cols;
-        sp.log_r = (uint32_t)r1;
-        sp.axis0_last = 1;
-        sp.tw_on = tw_log_n ? 1u : 0u;
-        sp.outer_count = 1ull << r0;
-        sp.col0 = col0;
-        sp.inter = fin;
-        launch(r1);
-    }
-    HIPCHK(hipGetLastError());
     return ZKP_OK;
 }
 

@@ -19,41 +19,19 @@
 #pragma once
 #include "ff.hpp"
 #include "fr29.hpp"
+#include "ntt_plan.hpp"
 
 namespace zkp {
 
 enum { SCALE_NONE = 0, SCALE_CONST = 1, SCALE_POW = 2, SCALE_POW_ROW = 3 };
 
-template <class F> struct NttOps;
-#ifndef ZKP_GL_LOG_T
-#define ZKP_GL_LOG_T 4
-#endif
-#ifndef ZKP_GL_THREADS
-#define ZKP_GL_THREADS 512
-#endif
-#ifndef ZKP_GL_MAX_PASS_LOG
-#define ZKP_GL_MAX_PASS_LOG 9
-#endif
-template <> struct NttOps<Fr> {
+template <class F> struct NttOps;  // the plan constants (MAX_PASS_LOG, LOG_T, THREADS, PAD, ...) come from ntt_plan.hpp
+template <> struct NttOps<Fr> : NttFrConsts {
     typedef Fr29 E;
     typedef Fr29 W;
-    static constexpr int MAX_PASS_LOG = 8;   // radix of one pass of a multi-pass transform (2^9: 72 KiB tiles, one workgroup
-                                             // per CU -- 2^26 in three passes measured 12.8 ms against 10.9 ms in four)
-    static constexpr int THREADS = 256;      // workgroup size of the pass kernels
-    static constexpr int LOG_T = 2;          // 4 x 32 B = 128 B runs (one cache line); 1024-element tiles = 36 KiB of
-                                             // LDS, so 4 workgroups (4 waves/SIMD) fit a CU: the kernel is issue-bound
-    static constexpr int MAX_TILE_LOG = 11;  // single-pass limit: 2048 elements x 36 B = 72 KiB of LDS
-    // A radix-2^9 pass with tiles of TWO columns (64-byte runs, the same 36 KiB of LDS and one element-quad per thread as a radix-2^8
-    // pass with four columns) where it saves a whole pass: 2^17 and 2^18 in two passes, 2^25 .. 2^27 in three.
-    // ... and a radix-2^10 pass with single-column tiles (32-byte runs) likewise: 2^19 and 2^20 in two passes, 2^28 .. 2^30 in three.
-    static constexpr int WIDE_PASS_LOG = 10;
-    static ZKP_HD int log_t_of(int log_r) { return log_r <= MAX_PASS_LOG ? LOG_T : log_r == 9 ? 1 : 0; }
-    // largest transform a wide radix is used for: 2^9 always, 2^10 (32-byte runs) only while the data is cache-resident
-    static ZKP_HD int wide_max_log_n(int log_r) { return log_r <= 9 ? 64 : 20; }
     static constexpr int K = 2;              // stages per register round: 1024-element tiles / 4 = one item per thread
                                              // (K = 3 with a mid-round normalise leaves half the threads idle: measured 20 % slower)
     static constexpr bool MIDFIX = false;    // a third lazy stage would need re-normalised limbs (fr29.hpp)
-    static constexpr int PAD = 0;            // 36-byte elements already spread over the LDS banks
     static constexpr bool LAST_LOAD_LDS_ORDER = true;  // see ntt_pass_last
     static ZKP_DEV E load(const Fr& x) { return fr29_from_sat(x); }
     static ZKP_DEV Fr store(const E& x) { return fr29_to_canonical(x); }
@@ -75,32 +53,14 @@ template <> struct NttOps<Fr> {
         u = u + t;
     }
     static ZKP_DEV W to_tw(const Fr& mont) { return fr29_twiddle_from_mont(mont); }
-    // Pass 0 of a multi-pass transform reads its inter-pass twiddles omega_N^(k_0 i) from a matrix shaped like the data ([k_0][i],
-    // one coalesced 32-byte load per element) instead of forming each one as the product of a low and a high table entry: one field
-    // product less per element (13.5 -> 12.5 at 2^24, 10 -> 9 at 2^18) for 32 B per element of extra reads in an issue-bound kernel.
-    static constexpr bool PASS0_MATRIX = true;
     static ZKP_DEV Fr tw_pack(const W& w) { return fr29_to_canonical(w); }
     static ZKP_DEV W tw_unpack(const Fr& x) { return fr29_from_sat(x); }
 };
-template <> struct NttOps<Gl> {
+template <> struct NttOps<Gl> : NttGlConsts {
     typedef Gl E;
     typedef Gl W;
-    // 16 x 8 B = 128 B runs; radix <= 2^9 so that 2^26 takes three passes (64 KiB tiles); 512 threads keep enough loads
-    // in flight per tile.  Measured 2^20 / 2^24 / 2^26: (T 32, radix 2^8, 256 threads) 0.068 / 0.567 / 2.04 ms,
-    // (16, 2^8, 512) 0.045 / 0.417 / 2.18, (16, 2^9, 512) 0.045 / 0.430 / 1.82, (16, 2^9, 1024) 0.048 / 0.451 / 1.75.
-    static constexpr int LOG_T = ZKP_GL_LOG_T;
-    static constexpr int MAX_PASS_LOG = ZKP_GL_MAX_PASS_LOG;
-    static constexpr int THREADS = ZKP_GL_THREADS;
-    static constexpr int MAX_TILE_LOG = 13;  // 8192 elements = 64 KiB
-    // no wider radices for Goldilocks: radix 2^10 / 2^11 with 8 / 4-column tiles (two passes instead of three for 2^19 .. 2^22)
-    // measured slower at every size (2^19 0.033 -> 0.060 ms, 2^22 0.112 -> 0.129 ms: the padded last-pass tile grows to 73 / 82 KiB
-    // and the runs shrink to 64 / 32 bytes; profiles/r02_l_ntt_wide_pass.md)
-    static constexpr int WIDE_PASS_LOG = MAX_PASS_LOG;
-    static ZKP_HD int log_t_of(int) { return LOG_T; }
-    static ZKP_HD int wide_max_log_n(int) { return 0; }
     static constexpr int K = 3;
     static constexpr bool MIDFIX = false;
-    static constexpr int PAD = 1;            // +1 element per row keeps the transposing LDS writes conflict-light
     static constexpr bool LAST_LOAD_LDS_ORDER = false;
     static ZKP_DEV E load(const Gl& x) { return x; }
     static ZKP_DEV Gl store(const E& x) { return x; }
@@ -118,10 +78,11 @@ template <> struct NttOps<Gl> {
         u = u + t;
     }
     static ZKP_DEV W to_tw(const Gl& canon) { return canon; }
-    static constexpr bool PASS0_MATRIX = false;  // memory-bound: a product is cheaper than 8 more bytes per element
     static ZKP_DEV Gl tw_pack(const W& w) { return w; }
     static ZKP_DEV W tw_unpack(const Gl& x) { return x; }
 };
+
+static_assert(sizeof(Fr29) == NttFrConsts::ELEM_BYTES && sizeof(Fr29) == NttFrConsts::TW_BYTES && sizeof(Gl) == NttGlConsts::ELEM_BYTES, "ntt_plan.hpp");
 
 // value(e) = lo[e & (2^h - 1)] * hi[e >> h]  -- two-level table of powers of one base
 template <class F>
