@@ -128,11 +128,34 @@ int zkp_g1_bases_create_dev(const void *d_xy, const uint8_t *d_is_inf, size_t n,
  * uses the shared bucket set (2^10 terms: 0.28 ms against 0.85 ms per-window, whose host-side window combination alone is
  * 0.4 ms).  For a sharded handle every chunk is expanded on its own device, all chunks alike (automatic width: that of the largest
  * chunk) and all-or-nothing: every device is asked for room before any chunk allocates, so a ZKP_E_NOMEM refusal leaves the whole
- * handle unexpanded and a later call with another width is accepted. */
+ * handle unexpanded and a later call with another width is accepted.
+ * zkp_g1_bases_precompute_glv below stores about half as many planes for the same MSM results: choose it when the footprint or the
+ * one-off expansion time matters (a 2^26 or 2^27 SRS, an SRS expanded per KzgScheme::new); this entry stays the default. */
 int zkp_g1_bases_precompute(zkp_bases *b, unsigned window_bits);
+/* zkp_g1_bases_precompute for the endomorphism-split MSM: ceil(129 / window_bits) planes instead of ceil(256 / window_bits);
+ * results of every MSM / KZG / PLONK / Nova entry over the handle are unchanged (same group element).
+ * BLS12-381 G1 has phi(x, y) = (beta x, y) = [lambda](x, y) with lambda = z^2 - 1 of 128 bits.  A scalar k < r is split on the device
+ * into k = k1 + lambda k2 (k2 = k div lambda; both halves at most lambda + 1 < 0.674 * 2^128, csrc/glv.hpp), the two halves are run as
+ * two scalar vectors over the same planes with one bucket set each, and the host returns V1 + phi(V2).  The planes therefore only
+ * cover 129 bits: 22 bits -> 6 planes of 21/22 bits instead of 12, 20 -> 7 of 18/19 (2^18 buckets per set) instead of 13, 16 -> 9
+ * of 14/15, 12 -> 11 of 11/12.  Saves: half the expansion memory (2^26 points at 22 bits: 51.5 GB instead of 103 GB; a 2^27 SRS fits
+ * one device) and half the expansion work.  Costs: two bucket sets -- two bucket reductions and two host tails -- per MSM, 2 x planes
+ * insertions per scalar (12 at 22 bits as before, 14 instead of 13 at 20), and a batch (zkp_msm_g1_batch_dev) of at most 32 MSMs
+ * instead of 64 (ZKP_E_ARG above).  Measured on one MI355X: expansion 15.9 instead of 33.9 ms at 2^20 points and 242
+ * instead of 511 ms at 2^24; a warm MSM 2.97 instead of 2.39 ms at 2^20, 9.4 instead of 8.6 ms at 2^22, 31.8 instead of 31.2 ms at 2^24.  Same arguments, automatic widths and refusals as zkp_g1_bases_precompute (ZKP_E_NOMEM with the
+ * sizes, ZKP_SRS_EXPAND_MAX_BYTES, all-or-nothing over the chunks of a sharded handle).  A handle is expanded one way: asking for the
+ * other mode on an expanded handle is ZKP_E_ARG, like another width; the same mode and width again is ZKP_OK. */
+int zkp_g1_bases_precompute_glv(zkp_bases *b, unsigned window_bits);
 size_t zkp_g1_bases_len(const zkp_bases *b);
 /* How the bases are expanded: *window_bits = the width asked for (0 = not expanded), *slices = insertions per scalar. */
 int zkp_g1_bases_info(const zkp_bases *b, unsigned *window_bits, unsigned *slices);
+/* The expansion in full: planes stored per point, glv = 1 for zkp_g1_bases_precompute_glv planes (slices = 2 x planes then, else
+ * planes), the widest slice in bits (2^(widest - 1) buckets per set).  All zero when the bases are not expanded. */
+typedef struct {
+    unsigned window_bits, slices, planes, glv, widest_slice_bits;
+    size_t bytes;   /* device bytes of the planes, summed over shards */
+} zkp_bases_expansion;
+int zkp_g1_bases_expansion(const zkp_bases *b, zkp_bases_expansion *out);
 void zkp_g1_bases_destroy(zkp_bases *b);
 
 /* ---- MSM: replaces the body of KzgScheme::evaluate_in_s, kzg/src/scheme.rs:84-96 (reached from commit :49,
@@ -228,6 +251,10 @@ int zkp_selftest_fr29_dev(int op, const void *d_in, size_t n, void *d_out, void 
 int zkp_selftest_fp_dev(int field, int op, const void *d_in, size_t n, void *d_out, void *stream);
 int zkp_selftest_gl_dev(int op, const void *d_in, size_t n, void *d_out, void *stream);
 int zkp_selftest_g1_dev(int op, const void *d_a, const void *d_b, size_t n, size_t stride, void *d_out, void *d_flag, void *stream);
+/* The scalar split of the endomorphism-split MSM (glv_split of csrc/glv.hpp, the function the digit recoding calls), one lane per case:
+ * d_scalars holds n Fr in memory form (Montgomery, 8 words), d_out receives 8 words per case, k1 = k mod lambda then k2 = k div lambda,
+ * canonical, low word first. */
+int zkp_selftest_glv_split_dev(const void *d_scalars, size_t n, void *d_out, void *stream);
 /* [s^i]G for i < n into host memory (kzg/src/srs.rs:48-63: n = circuit_size + 3). */
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t *out_xy);
 

@@ -19,6 +19,17 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_nova_r1cs { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
 
+/// how a bases handle is expanded (zkp_g1_bases_expansion); all zero when it is not
+#[repr(C)]
+pub struct zkp_bases_expansion {
+    pub window_bits: u32,
+    pub slices: u32,      // insertions per scalar: 2 x planes for endomorphism-split planes
+    pub planes: u32,
+    pub glv: u32,         // 1: zkp_g1_bases_precompute_glv
+    pub widest_slice_bits: u32,
+    pub bytes: usize,     // device bytes of the planes, summed over shards
+}
+
 /// struct Proof of plonk/src/prover.rs:23-41 in ABI form
 #[repr(C)]
 pub struct zkp_plonk_proof {
@@ -112,8 +123,10 @@ extern "C" {
     pub fn zkp_g1_bases_create(xy: *const u64, is_inf: *const u8, n: usize, out: *mut *mut zkp_bases) -> i32;
     pub fn zkp_g1_bases_create_dev(d_xy: *const c_void, d_is_inf: *const u8, n: usize, stream: *mut c_void, out: *mut *mut zkp_bases) -> i32;
     pub fn zkp_g1_bases_precompute(b: *mut zkp_bases, window_bits: u32) -> i32;
+    pub fn zkp_g1_bases_precompute_glv(b: *mut zkp_bases, window_bits: u32) -> i32;
     pub fn zkp_g1_bases_len(b: *const zkp_bases) -> usize;
     pub fn zkp_g1_bases_info(b: *const zkp_bases, window_bits: *mut u32, slices: *mut u32) -> i32;
+    pub fn zkp_g1_bases_expansion(b: *const zkp_bases, out: *mut zkp_bases_expansion) -> i32;
     pub fn zkp_g1_bases_destroy(b: *mut zkp_bases);
     pub fn zkp_msm_g1(bases: *const zkp_bases, scalars: *const u64, n: usize, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_msm_g1_dev(bases: *const zkp_bases, d_scalars: *const c_void, n: usize, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
@@ -135,6 +148,7 @@ extern "C" {
     pub fn zkp_selftest_fp_dev(field: i32, op: i32, d_in: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_gl_dev(op: i32, d_in: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_g1_dev(op: i32, d_a: *const c_void, d_b: *const c_void, n: usize, stride: usize, d_out: *mut c_void, d_flag: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_glv_split_dev(d_scalars: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_srs_g1(secret: *const u64, n: usize, out_xy: *mut u64) -> i32;
     pub fn zkp_ntt_fr(data: *mut u64, log_n: u32, inverse: i32, coset: *const u64) -> i32;
     pub fn zkp_ntt_fr_dev(d_data: *mut c_void, log_n: u32, batch: usize, inverse: i32, coset: *const u64, stream: *mut c_void) -> i32;

@@ -9,7 +9,8 @@ PRIM = {"uint64_t": "u64", "uint8_t": "u8", "int": "i32", "unsigned": "u32", "si
         "double": "f64", "zkp_bases": "zkp_bases", "zkp_plonk_prover": "zkp_plonk_prover",
         "zkp_plonk_transcript": "zkp_plonk_transcript", "zkp_plonk_proof": "zkp_plonk_proof", "zkp_ntt_layout": "zkp_ntt_layout",
         "zkp_ntt_shard_geometry": "zkp_ntt_shard_geometry", "zkp_nova_r1cs": "zkp_nova_r1cs", "zkp_nova_transcript": "zkp_nova_transcript",
-        "zkp_csr": "zkp_csr", "zkp_plonk_gates": "zkp_plonk_gates", "zkp_nova_instance": "zkp_nova_instance", "zkp_nova_proof": "zkp_nova_proof"}
+        "zkp_csr": "zkp_csr", "zkp_plonk_gates": "zkp_plonk_gates", "zkp_nova_instance": "zkp_nova_instance", "zkp_nova_proof": "zkp_nova_proof",
+        "zkp_bases_expansion": "zkp_bases_expansion"}
 RET = {"int": "i32", "void": "()", "size_t": "usize", "const char *": "*const c_char", "const char*": "*const c_char"}
 
 
@@ -59,6 +60,17 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_plonk_transcript { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_r1cs { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
+
+/// how a bases handle is expanded (zkp_g1_bases_expansion); all zero when it is not
+#[repr(C)]
+pub struct zkp_bases_expansion {
+    pub window_bits: u32,
+    pub slices: u32,      // insertions per scalar: 2 x planes for endomorphism-split planes
+    pub planes: u32,
+    pub glv: u32,         // 1: zkp_g1_bases_precompute_glv
+    pub widest_slice_bits: u32,
+    pub bytes: usize,     // device bytes of the planes, summed over shards
+}
 
 /// struct Proof of plonk/src/prover.rs:23-41 in ABI form
 #[repr(C)]

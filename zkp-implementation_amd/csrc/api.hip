@@ -406,6 +406,7 @@ struct zkp_bases {
     uint32_t pre_planes = 0;
     uint32_t pre_req = 0;      // window_bits the expansion was requested with
     uint16_t pre_off[36] = {0};
+    uint32_t pre_glv = 0;      // 1: the planes cover the 129 bits of a scalar half (zkp_g1_bases_precompute_glv): two bucket sets per MSM
 };
 
 namespace {
@@ -747,7 +748,11 @@ unsigned auto_window_bits(size_t n) {
 
 // check_only: stop after the argument and budget checks, before anything is allocated (the sharded entry asks every chunk's device
 // first, so that a refusal leaves the whole handle unexpanded instead of a mixture)
-int precompute_single(zkp_bases* b, unsigned window_bits, bool check_only = false) {
+// glv: planes for the endomorphism-split MSM (glv.hpp) -- ceil(129 / window_bits) of them instead of ceil(256 / window_bits)
+int precompute_single(zkp_bases* b, unsigned window_bits, bool glv, bool check_only = false) {
+    if (b->pre_c && (b->pre_glv != 0) != glv)
+        return fail(ZKP_E_ARG, b->pre_glv ? "bases already expanded for the endomorphism-split MSM (zkp_g1_bases_precompute_glv)"
+                                          : "bases already expanded for whole scalars (zkp_g1_bases_precompute)");
     if (window_bits == 0) {  // automatic
         // Up to 2^18 points the MSM is a chain of latencies, not of throughput: 16-bit windows (16 slices, 2^15 buckets, 14 reduction
         // levels) with the run of a bucket split over 2 or 4 lanes (msm.hpp, split_run) beat the 18..20 bits of round 1, whose 2^17..2^19
@@ -767,27 +772,15 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool check_only = fals
     hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
     WsOrder ord(st);
     if (!b->n) return ZKP_OK;
-    // Slices of a scalar: ceil(256 / window_bits) of them.  When that many windows of window_bits overshoot the 256 bits, the top
-    // window is short by that many bits and its 2^-k of the buckets collect 2^k times the points of the others; the 256 bits are
-    // then split into slices of floor/ceil(256 / planes) bits instead (18 -> 15 slices of 17/18 bits, 19 -> 14 of 18/19, 20 -> 13
-    // of 19/20).  Round 3: from ANY overshoot on (rounds 1-2: from 8 bits) -- at 20 bits the 4-bit overshoot left 2^14 buckets
-    // with ~90 entries against 26 on average at 2^20 points, and those 256 waves, dispatched first, were still walking their
-    // runs alone when the rest of the machine had finished (profiles/r03_j_balanced_slices.md).
-    const uint32_t planes = 256 / window_bits + (256 % window_bits ? 1 : 0);
+    // Slices of a scalar (or of a scalar half): msm_slice_offsets, msm_plan.hpp
+    const MsmSlices sl = msm_slice_offsets(glv ? GlvParams::COVER_BITS : 256, window_bits, (uint32_t)knob_int(KNOB_MSM_BALANCE_FROM));  // (tuning aid)
+    const uint32_t planes = sl.planes, cmax = sl.widest;
     SliceOffsets so;
-    std::memset(&so, 0, sizeof so);
-    uint32_t cmax = window_bits;
-    const uint32_t balance_from = (uint32_t)knob_int(KNOB_MSM_BALANCE_FROM);  // tuning aid
-    if (planes * window_bits - 256 < balance_from) {
-        for (uint32_t s = 0; s <= planes; s++) so.off[s] = (uint16_t)(s * window_bits);
-    } else {
-        const uint32_t base = 256 / planes, rem = 256 % planes;
-        cmax = base + (rem ? 1 : 0);
-        for (uint32_t s = 0; s < planes; s++) so.off[s + 1] = (uint16_t)(so.off[s] + base + (s < rem ? 1 : 0));
-    }
+    static_assert(sizeof so.off == sizeof sl.off, "SliceOffsets");
+    std::memcpy(so.off, sl.off, sizeof so.off);
     DevBuf p;
     {   // The expansion is `planes` x the SRS (13 x at 20 bits, 12 x at 22: 103 GB for 2^26 points, and a 2^27 SRS no longer fits one
-        // device).  Say so with the numbers instead of a bare allocation failure; the handle stays usable unexpanded (per-window MSM).
+        // device; split planes: 7 x and 6 x).  Say so with the numbers instead of a bare allocation failure; the handle stays usable unexpanded (per-window MSM).
         const size_t need = 128 * (size_t)planes * b->n;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
@@ -823,6 +816,7 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool check_only = fals
     b->pre_c = cmax;
     b->pre_req = window_bits;
     b->pre_planes = planes;
+    b->pre_glv = glv ? 1u : 0u;
     std::memcpy(b->pre_off, so.off, sizeof so.off);
     return ZKP_OK;
 }
@@ -839,7 +833,7 @@ int unexpand_single(zkp_bases* b) {
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(ZKP_E_DEVICE, hipGetErrorString(e));
     b->d_xy = std::move(p);
-    b->pre_c = b->pre_req = b->pre_planes = 0;
+    b->pre_c = b->pre_req = b->pre_planes = b->pre_glv = 0;
     return ZKP_OK;
 }
 
@@ -918,22 +912,24 @@ int zkp_g1_bases_create_dev(const void* d_xy, const uint8_t* d_is_inf, size_t n,
     return ZKP_OK;
 } ZKP_CATCH_INT
 
-int zkp_g1_bases_precompute(zkp_bases* b, unsigned window_bits) try {
+static int precompute_any(zkp_bases* b, unsigned window_bits, bool glv) {
     if (!b) return fail(ZKP_E_ARG, "null argument");
-    if (b->shards.empty()) return precompute_single(b, window_bits);
+    if (b->shards.empty()) return precompute_single(b, window_bits, glv);
     // A sharded handle is expanded all-or-nothing and every chunk alike (zkp_g1_bases_info reports chunk 0 for all of them): the
     // automatic width comes from the largest chunk, every chunk's device is asked for room BEFORE any of them allocates, and a
     // failure half way rolls the finished chunks back to the plain points.
     size_t nmax = 0, expanded = 0;
     for (const auto& sh : b->shards) nmax = std::max(nmax, sh->n), expanded += sh->pre_c ? 1 : 0;
+    for (const auto& sh : b->shards)  // (the other mode: refused before the automatic width can say "nothing to do")
+        if (sh->pre_c && (sh->pre_glv != 0) != glv) return precompute_single(sh.get(), window_bits, glv, true);
     if (window_bits == 0) {
         if (expanded == b->shards.size() || !(window_bits = auto_window_bits(nmax))) return ZKP_OK;
         if (expanded) window_bits = b->shards[0]->pre_req ? b->shards[0]->pre_req : window_bits;
     }
-    ZCHK(for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i].get(), window_bits, true); }));
+    ZCHK(for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i].get(), window_bits, glv, true); }));
     std::vector<uint8_t> was(b->shards.size());
     for (size_t i = 0; i < b->shards.size(); i++) was[i] = b->shards[i]->pre_c ? 1 : 0;
-    const int rc = for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i].get(), window_bits); });  // every chunk on its own device
+    const int rc = for_each_shard(b, [&](size_t i) { return precompute_single(b->shards[i].get(), window_bits, glv); });  // every chunk on its own device
     if (rc != ZKP_OK) {
         const std::string why = zkp_last_error();
         bool mixed = false;
@@ -942,6 +938,26 @@ int zkp_g1_bases_precompute(zkp_bases* b, unsigned window_bits) try {
         return fail(rc, why + (mixed ? " -- and a finished chunk could not be rolled back: the handle is expanded in part (still usable)"
                                      : " -- every chunk is back to the plain points"));
     }
+    return ZKP_OK;
+}
+
+int zkp_g1_bases_precompute(zkp_bases* b, unsigned window_bits) try { return precompute_any(b, window_bits, false); } ZKP_CATCH_INT
+
+int zkp_g1_bases_precompute_glv(zkp_bases* b, unsigned window_bits) try { return precompute_any(b, window_bits, true); } ZKP_CATCH_INT
+
+int zkp_g1_bases_expansion(const zkp_bases* b, zkp_bases_expansion* out) try {
+    if (!b || !out) return fail(ZKP_E_ARG, "null argument");
+    const zkp_bases* s = b->shards.empty() ? b : b->shards[0].get();  // every chunk of a sharded handle is expanded alike
+    if (!s) return fail(ZKP_E_ARG, "empty handle");
+    *out = zkp_bases_expansion{};
+    if (!s->pre_c) return ZKP_OK;  // unexpanded: all zero
+    out->window_bits = s->pre_req;
+    out->planes = s->pre_planes;
+    out->glv = s->pre_glv;
+    out->slices = s->pre_planes * (s->pre_glv ? 2u : 1u);
+    out->widest_slice_bits = s->pre_c;
+    if (b->shards.empty()) out->bytes = 128 * (size_t)s->pre_planes * s->n;
+    for (const auto& sh : b->shards) out->bytes += sh->pre_c ? 128 * (size_t)sh->pre_planes * sh->n : 0;
     return ZKP_OK;
 } ZKP_CATCH_INT
 
@@ -952,7 +968,7 @@ int zkp_g1_bases_info(const zkp_bases* b, unsigned* window_bits, unsigned* slice
     const zkp_bases* s = b->shards.empty() ? b : b->shards[0].get();  // every chunk of a sharded handle is expanded alike
     if (!s) return fail(ZKP_E_ARG, "empty handle");
     *window_bits = s->pre_req;
-    *slices = s->pre_c ? s->pre_planes : 0;
+    *slices = s->pre_c ? s->pre_planes * (s->pre_glv ? 2u : 1u) : 0;  // insertions per scalar
     return ZKP_OK;
 } ZKP_CATCH_INT
 
@@ -1278,6 +1294,15 @@ int zkp_selftest_g1_dev(int op, const void* d_a, const void* d_b, size_t n, size
     const bool quad = op == ST_G1_ADD_QUAD || op == ST_G1_ADD_QUAD_INPLACE;
     selftest_g1_launch(op, selftest_grid(quad ? 4 * n : n), reinterpret_cast<hipStream_t>(stream), d_a, d_b, d_out, d_flag, (uint64_t)n,
                        (uint64_t)stride);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_selftest_glv_split_dev(const void* d_scalars, size_t n, void* d_out, void* stream) try {
+    ZCHK(selftest_args(d_scalars, n, d_out));
+    CTX_ENTER(-1);
+    if (!n) return ZKP_OK;
+    selftest_glv_split_launch(selftest_grid(n), reinterpret_cast<hipStream_t>(stream), d_scalars, d_out, (uint64_t)n);
     HIPCHK(hipGetLastError());
     return ZKP_OK;
 } ZKP_CATCH_INT

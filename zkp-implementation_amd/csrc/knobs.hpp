@@ -48,7 +48,7 @@ constexpr KnobRow kKnobs[KNOB_COUNT] = {
     {KNOB_MSM_FEED_SECOND_PCT, "ZKP_MSM_FEED_SECOND_PCT", KNOB_TUNING, KNOB_INT, 0, 80, KNOB_COMPUTED,
      "share of a second short host-fed range (30 from 2^21 terms, else none): profiles/r05_o_range_handover.md"},
     {KNOB_MSM_RANGE_LOG, "ZKP_MSM_RANGE_LOG", KNOB_TUNING, KNOB_INT, 10, 30, 0,
-     "scalar ranges of at most 2^v terms in shared-bucket mode (0: 2^24, or 2^23 above 12 planes): "
+     "scalar ranges of at most 2^v terms in shared-bucket mode (0: 2^24, or 2^23 above 12 insertions per scalar): "
      "profiles/r02_a_accumulate_prefetch_and_range_sweep.md"},
     {KNOB_MSM_FIRST_PCT, "ZKP_MSM_FIRST_PCT", KNOB_TUNING, KNOB_INT, 1, 90, 0,
      "resident scalars, single MSM: a short first range of this share (0: none): profiles/r05_o_range_handover.md"},

@@ -18,6 +18,7 @@
 #include "g1_28.hpp"
 #include "fq28_inv.hpp"
 #include "msm_plan.hpp"  // MsmGeom, SortGeom and the limits the host plan shares with the kernels
+#include "glv.hpp"       // glv_split: the scalar halves of the endomorphism-split mode
 
 namespace zkp {
 
@@ -25,9 +26,9 @@ constexpr int MSM_THREADS = 256;
 constexpr int ACC_THREADS = 256;  // workgroup size of msm_accumulate (64 and 128 measure the same)
 // The kernels below take MsmGeom and SortGeom (msm_plan.hpp) by value: their layout is part of this file's kernels, pinned here
 #define ZKP_AT(f, o) offsetof(MsmGeom, f) == o
-static_assert(sizeof(MsmGeom) == 152 && ZKP_AT(c, 0) && ZKP_AT(nwin, 4) && ZKP_AT(nb, 8) && ZKP_AT(nchunk, 12) && ZKP_AT(n, 16) && ZKP_AT(chunk, 24) &&
+static_assert(sizeof(MsmGeom) == 160 && ZKP_AT(c, 0) && ZKP_AT(nwin, 4) && ZKP_AT(nb, 8) && ZKP_AT(nchunk, 12) && ZKP_AT(n, 16) && ZKP_AT(chunk, 24) &&
               ZKP_AT(ns, 32) && ZKP_AT(plane_stride, 40) && ZKP_AT(nslice, 48) && ZKP_AT(shared, 52) && ZKP_AT(run_limit, 56) && ZKP_AT(piece, 60) &&
-              ZKP_AT(resume, 64) && ZKP_AT(off, 68) && ZKP_AT(interleave, 140) && ZKP_AT(split_log, 144) && ZKP_AT(more, 148), "MsmGeom layout");
+              ZKP_AT(resume, 64) && ZKP_AT(off, 68) && ZKP_AT(interleave, 140) && ZKP_AT(split_log, 144) && ZKP_AT(more, 148) && ZKP_AT(glv, 152), "MsmGeom layout");
 #undef ZKP_AT
 static_assert(sizeof(SortGeom) == 8 && offsetof(SortGeom, lo_bits) == 0 && offsetof(SortGeom, nhi) == 4, "SortGeom layout");
 
@@ -50,13 +51,10 @@ ZKP_DEV bool msm_check_fail(int cls, uint32_t v0, uint32_t v1) {
 struct DigitSources {
     const Fr* scalars[MSM_MAX_BATCH];  // one scalar vector per MSM of the batch (blockIdx.y), already offset to this range
 };
-__global__ __launch_bounds__(MSM_THREADS) void msm_digits_kernel(DigitSources src, const uint8_t* __restrict__ base_inf, MsmGeom g,
-                                                                uint32_t nwin1, uint32_t* __restrict__ digits) {
-    const uint64_t i = (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
-    if (i >= g.ns) return;
-    const uint32_t win_off = blockIdx.y * nwin1;  // digits laid out [msm][slice][scalar]
-    Fr k = from_mont(src.scalars[blockIdx.y][i]);
-    const bool skip = base_inf != nullptr && base_inf[i] != 0;  // infinity base contributes nothing
+// The signed digits of one canonical value (8 words; a scalar half of the split mode: the upper four zero) into digit group `group`
+ZKP_DEV void msm_recode(const uint32_t (&k)[8], bool skip, const MsmGeom& g, uint32_t nwin1, uint32_t group, uint64_t i,
+                        uint32_t* __restrict__ digits) {
+    const uint32_t win_off = group * nwin1;  // digits laid out [group][slice][scalar]
     uint32_t carry = 0;
     for (uint32_t w = 0; w < nwin1; w++) {  // nwin1 = g.nslice windows of this scalar vector
         const uint32_t lo = g.off[w], width = (uint32_t)g.off[w + 1] - lo;
@@ -64,8 +62,8 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_digits_kernel(DigitSources sr
         uint64_t v = 0;
 #pragma unroll
         for (int q = 0; q < 8; q++) {  // static indexing keeps the limbs in registers
-            if (q == (int)limb) v |= (uint64_t)k.l[q];
-            if (q == (int)limb + 1) v |= (uint64_t)k.l[q] << 32;
+            if (q == (int)limb) v |= (uint64_t)k[q];
+            if (q == (int)limb + 1) v |= (uint64_t)k[q] << 32;
         }
         uint32_t u = ((uint32_t)(v >> sh) & ((1u << width) - 1)) + carry;
         uint32_t enc;
@@ -78,6 +76,27 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_digits_kernel(DigitSources sr
         }
         digits[(uint64_t)(win_off + w) * g.ns + i] = skip ? 0u : enc;
     }
+}
+__global__ __launch_bounds__(MSM_THREADS) void msm_digits_kernel(DigitSources src, const uint8_t* __restrict__ base_inf, MsmGeom g,
+                                                                uint32_t nwin1, uint32_t* __restrict__ digits) {
+    const uint64_t i = (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= g.ns) return;
+    Fr k = from_mont(src.scalars[blockIdx.y][i]);
+    const bool skip = base_inf != nullptr && base_inf[i] != 0;  // infinity base contributes nothing
+    msm_recode(k.l, skip, g, nwin1, blockIdx.y, i, digits);  // digit group = msm
+}
+// Endomorphism-split planes (g.glv): k = k1 + lambda k2 (glv.hpp); k1 goes to digit group 2 m, k2 to group 2 m + 1, both with the
+// same slice offsets (which cover 129 bits: no carry leaves the top slice of a half) and the same carry rule
+__global__ __launch_bounds__(MSM_THREADS) void msm_digits_glv_kernel(DigitSources src, const uint8_t* __restrict__ base_inf, MsmGeom g,
+                                                                    uint32_t nwin1, uint32_t* __restrict__ digits) {
+    const uint64_t i = (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= g.ns) return;
+    const Fr k = from_mont(src.scalars[blockIdx.y][i]);
+    const bool skip = base_inf != nullptr && base_inf[i] != 0;  // infinity base contributes nothing, in either group
+    const GlvHalves h = glv_split(k.l);
+    const uint32_t k1[8] = {h.k1[0], h.k1[1], h.k1[2], h.k1[3], 0, 0, 0, 0}, k2[8] = {h.k2[0], h.k2[1], h.k2[2], h.k2[3], 0, 0, 0, 0};
+    msm_recode(k1, skip, g, nwin1, 2 * blockIdx.y, i, digits);
+    msm_recode(k2, skip, g, nwin1, 2 * blockIdx.y + 1, i, digits);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -157,9 +157,9 @@ struct MsmPass {
         const SortGeom& sg = p.sg;
         {
             ProfScope ps("msm_digits", sst);
-            DigitSources ds;  // digits laid out [msm][slice][scalar]: a shared-mode sort window is one msm
+            DigitSources ds;  // digits laid out [msm][slice][scalar]: a shared-mode sort window is one msm (split planes: one half of one)
             for (size_t m = 0; m < count; m++) ds.scalars[m] = scalars[m] + off;
-            hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)((g.ns + MSM_THREADS - 1) / MSM_THREADS), (unsigned)count), dim3(MSM_THREADS), 0,
+            hipLaunchKernelGGL(g.glv ? msm_digits_glv_kernel : msm_digits_kernel, dim3((unsigned)((g.ns + MSM_THREADS - 1) / MSM_THREADS), (unsigned)count), dim3(MSM_THREADS), 0,
                                sst, ds, bases->d_inf.p ? bases->d_inf.get() + off : nullptr, g, p.nwin1, cx.digits.get());
             MSM_TRACE(sst, ridx, "digits");
         }
@@ -275,10 +275,17 @@ int wait_msm_result(const MsmGeom& g, const uint32_t* flags, hipStream_t st) {
 
 // Serial tail on the host.  Per bucket set: V = S + sum_l 2^l U_l.  Per-window mode: total = sum_w 2^(c w) V_w, and every (w, l)
 // lands on its own bit position c w + l, so ONE Horner chain over the positions does it with c W doublings.  Shared mode: the
-// expanded bases already carry the 2^(c w) factors, total = V of the single bucket set.
-void msm_host_tail(const uint32_t* host_res, size_t count, uint32_t wins_per_msm, uint32_t c, HXyzz* out) {
+// expanded bases already carry the 2^(c w) factors, total = V of the single bucket set.  Endomorphism-split planes (glv): an MSM has
+// two bucket sets, total = V_1 + phi(V_2) with phi(X, Y, ZZ, ZZZ) = (beta X, Y, ZZ, ZZZ) -- the identity (ZZ = 0) stays the identity,
+// and V_1 = +-phi(V_2) is the general add's doubling / cancelling case.
+HXyzz glv_phi(HXyzz v) {
+    static const HFq beta = HFq::load(GlvParams::BETA).to_mont();
+    v.x = v.x * beta;
+    return v;
+}
+void msm_host_tail(const uint32_t* host_res, size_t count, uint32_t wins_per_msm, uint32_t c, bool glv, HXyzz* out) {
     const auto t_tail0 = std::chrono::steady_clock::now();
-    auto tail = [&](size_t m) {
+    auto tail_set = [&](size_t m) {
         const uint32_t* res = host_res + m * wins_per_msm * c * 64;  // 64 words / point
         HXyzz total = HXyzz::infinity();
         for (int pos = (int)(wins_per_msm * c) - 1; pos >= 0; pos--) {
@@ -288,8 +295,9 @@ void msm_host_tail(const uint32_t* host_res, size_t count, uint32_t wins_per_msm
             if (l <= (int)c - 2) total = total.add(xyzz_from_internal(rw + (size_t)(1 + l) * 64));
             if (l == 0) total = total.add(xyzz_from_internal(rw));
         }
-        out[m] = total;
+        return total;
     };
+    auto tail = [&](size_t m) { out[m] = glv ? tail_set(2 * m).add(glv_phi(tail_set(2 * m + 1))) : tail_set(m); };
     if (count == 1)
         tail(0);
     else  // the tails of a batch are independent serial chains: spread over the resident host workers
@@ -300,11 +308,12 @@ void msm_host_tail(const uint32_t* host_res, size_t count, uint32_t wins_per_msm
 // out[m] = sum_i scalars[m][i] * bases[i] as extended-Jacobian points (host), for `count` scalar vectors of the same length over
 // the same bases.  The vectors are stacked as extra windows of ONE pass through the kernels, so that a batch of small MSMs (the
 // 3 + 1 + 3 + 2 commitments of a PLONK proof) fills the GPU and pays the latency-bound bucket reduction once.  With expanded bases
-// (zkp_g1_bases_precompute) all windows of a scalar share one bucket set.
+// (zkp_g1_bases_precompute) all windows of a scalar share one bucket set; with endomorphism-split planes
+// (zkp_g1_bases_precompute_glv) every scalar vector is a batch of two over the same planes and out[m] = V_1 + phi(V_2).
 int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t count, size_t n, hipStream_t st, HXyzz* out,
                       const MsmFeed* feed = nullptr) {
     MsmPlan p;
-    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off}, count, n, feed ? &feed->ranges : nullptr, &p))
+    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, feed ? &feed->ranges : nullptr, &p))
         return fail(rc, p.error);
     if (p.lens.empty()) {
         for (size_t m = 0; m < count; m++) out[m] = HXyzz::infinity();
@@ -337,7 +346,7 @@ int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t
 #endif
     if (count > 1 && !knob_flag(KNOB_POOL_NO_WARM)) host_pool().warm(std::chrono::microseconds(3000));  // the tails below run on the pool: wake it now
     ZCHK(wait_msm_result(pass.g, pass.result_flags, st));
-    msm_host_tail(reinterpret_cast<const uint32_t*>(pass.result_out), count, p.g.shared ? 1u : p.nwin1, p.g.c, out);  // (the pool's threads are in no context)
+    msm_host_tail(reinterpret_cast<const uint32_t*>(pass.result_out), count, p.g.shared ? 1u : p.nwin1, p.g.c, p.g.glv != 0, out);  // (the pool's threads are in no context)
     return ZKP_OK;
 }
 

@@ -35,6 +35,7 @@ struct MsmGeom {
     uint32_t interleave; // 1: msm_accumulate walks the bucket sets interleaved (see there)
     uint32_t split_log;  // 2^split_log lanes (quads) share a bucket's run, one contiguous part each (small problems, see msm_accumulate)
     uint32_t more;       // 1: another scalar range follows: the bucket sums go to the hand-over array (msm_accumulate_body), not to `buckets`
+    uint32_t glv;        // 1: endomorphism-split planes: MSM m owns bucket sets 2m (k mod lambda) and 2m + 1 (k div lambda), see glv.hpp
 };
 
 // Counting sort geometry (msm.hpp): bucket ids are 1..nb; (b - 1) = hi * 2^lo_bits + lo.
@@ -57,8 +58,37 @@ static_assert(kKnobs[KNOB_MSM_SPLIT_LOG].hi == MSM_MAX_SPLIT_LOG, "ZKP_MSM_SPLIT
 // a scalar has more than 32 windows (MsmGeom::off holds 36 offsets).
 inline unsigned pick_window_bits(size_t n) { return (unsigned)knob_int(KNOB_MSM_C, n >= 2048 ? 16 : 8); }
 
-// The shape of the bases an MSM runs over (zkp_bases): pre_c != 0 means pre_planes expanded planes, plane s = 2^pre_off[s] * P
-struct MsmBases { uint64_t n; uint32_t pre_c, pre_planes; const uint16_t* pre_off; };
+// The shape of the bases an MSM runs over (zkp_bases): pre_c != 0 means pre_planes expanded planes, plane s = 2^pre_off[s] * P;
+// glv != 0: the planes cover the 129 bits of a scalar half only (zkp_g1_bases_precompute_glv)
+struct MsmBases { uint64_t n; uint32_t pre_c, pre_planes; const uint16_t* pre_off; uint32_t glv = 0; };
+
+// Slices of an expansion (zkp_g1_bases_precompute*): ceil(cover / window_bits) planes over `cover` bits -- 256 for whole scalars, 129
+// for the halves of the endomorphism split (both at most lambda + 1 < 0.674 * 2^128: with 128 bits the top signed digit would carry
+// out and msm_digits drops that carry; with 129 the top slice stays below half its range, as r < 2^255 keeps it for 256).  When that
+// many windows of window_bits overshoot the cover, the top window is short by that many bits and its 2^-k of the buckets collect 2^k
+// times the points of the others; from `balance_from` bits of overshoot on (ZKP_MSM_BALANCE_FROM, default: any) the cover is split
+// into slices of floor/ceil(cover / planes) bits instead (256 bits: 18 -> 15 slices of 17/18 bits, 19 -> 14 of 18/19, 20 -> 13 of
+// 19/20; 129 bits: 22 -> 6 of 21/22, 20 -> 7 of 18/19).  Round 3: from ANY overshoot on (rounds 1-2: from 8 bits) -- at 20 bits the
+// 4-bit overshoot left 2^14 buckets with ~90 entries against 26 on average at 2^20 points, and those 256 waves, dispatched first,
+// were still walking their runs alone when the rest of the machine had finished (profiles/r03_j_balanced_slices.md).
+struct MsmSlices {
+    uint32_t planes, widest;  // widest slice in bits: 2^(widest - 1) buckets
+    uint16_t off[36];         // plane s holds 2^off[s] * P; off[planes] >= cover
+};
+inline MsmSlices msm_slice_offsets(uint32_t cover, uint32_t window_bits, uint32_t balance_from) {
+    MsmSlices s{};
+    s.planes = cover / window_bits + (cover % window_bits ? 1 : 0);
+    s.widest = window_bits;
+    if (s.planes > 35) return s;  // (window_bits below 8: refused by the callers)
+    if (s.planes * window_bits - cover < balance_from) {
+        for (uint32_t k = 0; k <= s.planes; k++) s.off[k] = (uint16_t)(k * window_bits);
+    } else {
+        const uint32_t base = cover / s.planes, rem = cover % s.planes;
+        s.widest = base + (rem ? 1 : 0);
+        for (uint32_t k = 0; k < s.planes; k++) s.off[k + 1] = (uint16_t)(s.off[k] + base + (k < rem ? 1 : 0));
+    }
+    return s;
+}
 
 // Host-fed scalars (zkp_msm_g1, shared-bucket mode): ranges of at most 2^range_log scalars; first_len != 0: a short first range (its
 // upload is the exposed one), second_len != 0: then a second short one, then the rest
@@ -111,6 +141,11 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     if (count > (size_t)MSM_MAX_BATCH) return refuse(ZKP_E_ARG, "batch of more than 64 MSMs");
     // expanded bases: always the shared bucket set (even 2^10 terms: 0.35 vs 0.85 ms on the per-window path)
     const bool shared = bases.pre_c != 0;
+    // endomorphism-split planes: every MSM is a batch of two over the same planes (k mod lambda, k div lambda), one bucket set each
+    const bool glv = shared && bases.glv != 0;
+    const uint32_t sets = glv ? 2 : 1;
+    if (sets * count > (size_t)MSM_MAX_BATCH)
+        return refuse(ZKP_E_ARG, "batch of more than 32 MSMs over endomorphism-split bases (two bucket sets per MSM, 64 per pass)");
     MsmGeom& g = p->g = MsmGeom{};
     g.c = shared ? bases.pre_c : pick_window_bits(n);
     const uint32_t nwin1 = shared ? bases.pre_planes : 256 / g.c + (256 % g.c ? 1 : 0);
@@ -119,11 +154,15 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     if (nwin1 + 1 > 36) return refuse(ZKP_E_ARG, "more than 35 windows per scalar");
     for (uint32_t s = 0; s <= nwin1; s++) g.off[s] = shared ? bases.pre_off[s] : (uint16_t)(s * g.c);
     g.shared = shared ? 1u : 0u;
+    g.glv = glv ? 1u : 0u;
     // Shared mode walks the scalars in ranges: random 128-byte reads over more than ~26 GB of planes fall off a translation cliff
     // (profiles/r01_f_shared_buckets.md, profiles/r02_j_sort_under_accumulate.md).  Later ranges add into the same buckets.
     std::vector<uint64_t>& lens = p->lens;
     if (shared) {
-        const uint64_t max_range = bases.pre_planes <= 12 ? 1ull << 24 : 1ull << 23;
+        // The cap goes by insertions per scalar (split planes: two per plane), not by planes: 12 x 2^24 entries is what the
+        // workspaces and the sort were measured with, and a split pass of 2 x 6 x 2^24 has exactly that many.  Its planes are half
+        // as large (13 GB at 2^24), so the translation cliff is no nearer than in plain mode; longer split ranges are unmeasured.
+        const uint64_t max_range = sets * bases.pre_planes <= 12 ? 1ull << 24 : 1ull << 23;
         uint64_t cap = feed ? std::min<uint64_t>(max_range, 1ull << feed->range_log) : max_range;
         if (const long long v = knob_int(KNOB_MSM_RANGE_LOG)) cap = 1ull << v;
         uint64_t want_first = feed ? feed->first_len : 0;
@@ -145,7 +184,7 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     const uint64_t range = p->range = *std::max_element(lens.begin(), lens.end());
     g.ns = range;
     g.plane_stride = bases.n;
-    g.nwin = shared ? (uint32_t)count : nwin1 * (uint32_t)count;  // sort windows = bucket sets
+    g.nwin = shared ? sets * (uint32_t)count : nwin1 * (uint32_t)count;  // sort windows = bucket sets
     g.n = shared ? (uint64_t)nwin1 * range : n;                   // entries per sort window
     if (g.n >= (1ull << 31)) return refuse(ZKP_E_ARG, "windows x scalars >= 2^31 with expanded bases");
     g.nb = 1u << (g.c - 1);

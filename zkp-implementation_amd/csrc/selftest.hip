@@ -3,6 +3,7 @@
 
 #include "fr29.hpp"
 #include "g1_28.hpp"
+#include "glv.hpp"
 
 namespace zkp {
 
@@ -180,6 +181,18 @@ __global__ __launch_bounds__(ST_THREADS) void selftest_g1_kernel(const uint4* pa
     }
 }
 
+__global__ __launch_bounds__(ST_THREADS) void selftest_glv_split_kernel(const Fr* __restrict__ in, uint32_t* __restrict__ out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const Fr k = from_mont(Fr::load(in + i));
+    const GlvHalves h = glv_split(k.l);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        out[8 * i + j] = h.k1[j];
+        out[8 * i + 4 + j] = h.k2[j];
+    }
+}
+
 // the operation number picks the instantiation
 namespace {
 template <int OP = 0>
@@ -246,6 +259,11 @@ bool selftest_gl_launch(int op, unsigned blocks, hipStream_t s, const void* in, 
 bool selftest_g1_launch(int op, unsigned blocks, hipStream_t s, const void* a, const void* b, void* out, void* flag, uint64_t n, uint64_t stride) {
     return launch_g1(op, dim3(blocks), s, reinterpret_cast<const uint4*>(a), reinterpret_cast<const uint4*>(b), reinterpret_cast<uint4*>(out),
                      reinterpret_cast<uint32_t*>(flag), n, stride);
+}
+
+void selftest_glv_split_launch(unsigned blocks, hipStream_t s, const void* in, void* out, uint64_t n) {
+    hipLaunchKernelGGL(selftest_glv_split_kernel, dim3(blocks), dim3(ST_THREADS), 0, s, reinterpret_cast<const Fr*>(in),
+                       reinterpret_cast<uint32_t*>(out), n);
 }
 
 }  // namespace zkp

@@ -79,5 +79,7 @@ bool selftest_fr29_launch(int op, unsigned blocks, hipStream_t s, const void* in
 bool selftest_fp_launch(int field, int op, unsigned blocks, hipStream_t s, const void* in, void* out, uint64_t n);
 bool selftest_gl_launch(int op, unsigned blocks, hipStream_t s, const void* in, void* out, uint64_t n);
 bool selftest_g1_launch(int op, unsigned blocks, hipStream_t s, const void* a, const void* b, void* out, void* flag, uint64_t n, uint64_t stride);
+// glv_split (glv.hpp) of n Fr in memory form: 8 words per case, k1 then k2
+void selftest_glv_split_launch(unsigned blocks, hipStream_t s, const void* in, void* out, uint64_t n);
 
 }  // namespace zkp

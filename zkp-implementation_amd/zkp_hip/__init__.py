@@ -48,7 +48,9 @@ _SIGS = {
     "zkp_g1_bases_create_dev": ([_VP, _U8P, _SZ, _VP, C.POINTER(_VP)], C.c_int),
     "zkp_g1_bases_precompute": ([_VP, C.c_uint], C.c_int),
     "zkp_g1_bases_len": ([_VP], _SZ),
+    "zkp_g1_bases_precompute_glv": ([_VP, C.c_uint], C.c_int),
     "zkp_g1_bases_info": ([_VP, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], C.c_int),
+    "zkp_g1_bases_expansion": ([_VP, _VP], C.c_int),
     "zkp_g1_bases_destroy": ([_VP], None),
     "zkp_msm_g1": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
@@ -68,6 +70,7 @@ _SIGS = {
     "zkp_selftest_fp_dev": ([C.c_int, C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_gl_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_g1_dev": ([C.c_int, _VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
+    "zkp_selftest_glv_split_dev": ([_VP, _SZ, _VP, _VP], C.c_int),
     "zkp_srs_g1": ([_VP, _SZ, _VP], C.c_int),
     "zkp_ntt_fr": ([_VP, C.c_uint, C.c_int, _VP], C.c_int),
     "zkp_ntt_fr_dev": ([_VP, C.c_uint, _SZ, C.c_int, _VP, _VP], C.c_int),
@@ -265,6 +268,11 @@ def _dev_ptr(t, min_bytes):
 
 
 # ----------------------------------------------------------------------------- bases / MSM
+class _BasesExpansion(C.Structure):  # zkp_bases_expansion in include/zkp_hip.h
+    _fields_ = [("window_bits", C.c_uint), ("slices", C.c_uint), ("planes", C.c_uint), ("glv", C.c_uint), ("widest_slice_bits", C.c_uint),
+                ("bytes", C.c_size_t)]
+
+
 class G1Bases:
     """Base points resident in HBM (the SRS of kzg/src/srs.rs:14-21, uploaded once)."""
 
@@ -286,10 +294,17 @@ class G1Bases:
         _chk(lib().zkp_g1_bases_create_dev(_dev_ptr(xy_tensor, 96 * n), inf, n, _stream_ptr(stream), C.byref(h)))
         return cls(h)
 
-    def precompute(self, window_bits=20):
-        """Expand to the multiples 2^(window_bits s) P (shared-bucket MSM, see include/zkp_hip.h)."""
-        _chk(lib().zkp_g1_bases_precompute(self._h, window_bits))
+    def precompute(self, window_bits=20, glv=False):
+        """Expand to the multiples 2^(window_bits s) P (shared-bucket MSM, see include/zkp_hip.h).  glv: the endomorphism-split
+        expansion (zkp_g1_bases_precompute_glv), about half as many planes for the same results."""
+        _chk((lib().zkp_g1_bases_precompute_glv if glv else lib().zkp_g1_bases_precompute)(self._h, window_bits))
         return self
+
+    def expansion(self):
+        """zkp_g1_bases_expansion -> dict(window_bits, slices, planes, glv, widest_slice_bits, bytes); all zero when not expanded."""
+        e = _BasesExpansion()
+        _chk(lib().zkp_g1_bases_expansion(self._h, C.byref(e)))
+        return {name: int(getattr(e, name)) for name, _ in _BasesExpansion._fields_}
 
     def shards(self):
         """[(slot, hip_device, offset, length)] of the chunks of this handle (one entry for a single-slot handle)."""
@@ -387,6 +402,11 @@ def selftest_field_dev(family, op, in_tensor, n, out_tensor, stream=None):
         _chk(lib().zkp_selftest_fp_dev(0 if family == "fq" else 1, SELFTEST_OPS["fp"][op], *args))
     else:
         _chk(getattr(lib(), f"zkp_selftest_{family}_dev")(SELFTEST_OPS[family][op], *args))
+
+
+def selftest_glv_split_dev(scalars_tensor, n, out_tensor, stream=None):
+    """zkp_selftest_glv_split_dev: n Fr in memory form (32 B each) -> 8 words per case (k mod lambda, k div lambda)."""
+    _chk(lib().zkp_selftest_glv_split_dev(_dev_ptr(scalars_tensor, 32 * n), n, _dev_ptr(out_tensor, 32 * n), _stream_ptr(stream)))
 
 
 def selftest_g1_dev(op, a_tensor, b_tensor, n, stride, out_tensor, flag_tensor, stream=None):
