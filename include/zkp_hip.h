@@ -144,7 +144,9 @@ int zkp_g1_bases_precompute(zkp_bases *b, unsigned window_bits);
  * instead of 64 (ZKP_E_ARG above).  Measured on one MI355X: expansion 15.9 instead of 33.9 ms at 2^20 points and 242
  * instead of 511 ms at 2^24; a warm MSM 2.97 instead of 2.39 ms at 2^20, 9.4 instead of 8.6 ms at 2^22, 31.8 instead of 31.2 ms at 2^24.  Same arguments, automatic widths and refusals as zkp_g1_bases_precompute (ZKP_E_NOMEM with the
  * sizes, ZKP_SRS_EXPAND_MAX_BYTES, all-or-nothing over the chunks of a sharded handle).  A handle is expanded one way: asking for the
- * other mode on an expanded handle is ZKP_E_ARG, like another width; the same mode and width again is ZKP_OK. */
+ * other mode on an expanded handle is ZKP_E_ARG, like another width; the same mode and width again is ZKP_OK.
+ * phi(P) = [lambda]P holds in G1 and nowhere else on the curve, so the results equal those of the plain expansion only for bases in
+ * the prime-order subgroup: neither entry checks that -- zkp_g1_bases_validate below does. */
 int zkp_g1_bases_precompute_glv(zkp_bases *b, unsigned window_bits);
 size_t zkp_g1_bases_len(const zkp_bases *b);
 /* How the bases are expanded: *window_bits = the width asked for (0 = not expanded), *slices = insertions per scalar. */
@@ -157,6 +159,45 @@ typedef struct {
 } zkp_bases_expansion;
 int zkp_g1_bases_expansion(const zkp_bases *b, zkp_bases_expansion *out);
 void zkp_g1_bases_destroy(zkp_bases *b);
+
+/* ---- G1 validity on the GPU.  This ABI is the deserialisation boundary: the reference holds typed arkworks points that were
+ *      validated when they were built, a caller of this library hands over raw limbs.  The verifiers check their few G1 inputs on the
+ *      host ([r]P, csrc/verify_host.inc); these entries check whole arrays -- an SRS -- with one lane per point.  Per point that is not
+ *      flagged as infinity, in this order, the first failure being the point's status:
+ *        1 non-canonical     a coordinate's six limbs are not below p as stored
+ *        2 off the curve     y^2 != x^3 + 4
+ *        3 outside G1        [z^2]P != P + phi(P), z = -0xd201000000010000, phi(x, y) = (beta x, y): 2 x (63 doublings + 5 additions)
+ *                            instead of the 255 doublings of [r]P; sound and complete (csrc/g1_check.hpp)
+ *      and 0 for a valid point.  A point flagged as infinity is valid and its coordinates are not looked at.
+ *      A bad point is a finding, not an error: the entries return ZKP_OK with the report filled; ZKP_E_ARG is for null arguments.
+ *      n == 0 gives an all-zero report.  The status arrays (one byte per point) may be NULL.
+ *      Nothing else in the library calls these: zkp_g1_bases_create* and the expansions take the points as they come. ---- */
+typedef struct {
+    uint64_t checked, bad;                               /* points looked at (infinity flags included), points with status != 0 */
+    uint64_t non_canonical, off_curve, outside_subgroup; /* sums to bad */
+    uint64_t first_bad;                                  /* lowest bad index, or n when bad == 0 */
+    int first_status;                                    /* its status, or 0 */
+} zkp_g1_validation;
+/* n x 12 limbs in device memory (the slot is chosen from the pointer as in zkp_g1_bases_create_dev); d_status: device memory.
+ * Synchronises `stream` before it returns. */
+int zkp_g1_validate_dev(const void *d_xy, const uint8_t *d_is_inf, size_t n, uint8_t *d_status, void *stream, zkp_g1_validation *out);
+/* The same from host memory, uploaded in pieces of 2^18 points (24 MiB of staging); indices in the report are global.  Runs on the
+ * thread's zkp_set_device() slot, or slot 0. */
+int zkp_g1_validate(const uint64_t *xy, const uint8_t *is_inf, size_t n, uint8_t *status, zkp_g1_validation *out);
+/* The points of a handle: plain, expanded either way, or sharded (every chunk on its own device).  `status` is HOST memory of
+ * zkp_g1_bases_len(b) bytes.  The handle holds the device-internal form, which has lost the raw limbs: this entry reports statuses
+ * 0, 2 and 3 only, and a point whose raw limbs were not canonical comes out as 2 or 3 -- use zkp_g1_validate* on the raw points
+ * where that distinction matters.  Call it on any SRS that did not come from typed, checked values, and always before
+ * zkp_g1_bases_precompute_glv. */
+int zkp_g1_bases_validate(const zkp_bases *b, uint8_t *status, zkp_g1_validation *out);
+/* Are the first n points of the handle [s^i]G, i < n, for the s behind g2s = [s]_2?  *accepted = 1 or 0.
+ *   P_0 must be the G1 generator (KzgScheme::verify multiplies G1Point::generator(), kzg/src/scheme.rs:165: an SRS scaled by a constant
+ *   would commit consistently and never verify), and e(sum r_i P_i, [s]_2) = e(sum r_i P_{i+1}, G_2) over i < n - 1.
+ * r: (n - 1) x 4 limbs, Fr memory form, the caller's randomness -- as r_primes of zkp_kzg_batch_verify, which stand for the reference's
+ * Fr::from(rng.gen::<u128>()).  The sums are two MSMs over the handle (sharded and expanded handles work), the pairings run on the
+ * host.  ASSUMES VALID POINTS: call zkp_g1_bases_validate first.  n == 0 or a g2s that is not a valid G2 point: ZKP_E_ARG;
+ * n above the handle's length: ZKP_E_SIZE; n == 1 checks P_0 only. */
+int zkp_srs_check(const zkp_bases *srs, const uint64_t g2s_xy[24], size_t n, const uint64_t *r, int *accepted);
 
 /* ---- MSM: replaces the body of KzgScheme::evaluate_in_s, kzg/src/scheme.rs:84-96 (reached from commit :49,
  *      commit_vector :63, open :108, open_vector :132 and the 9 commit sites of plonk/src/prover.rs:92,123,150,

@@ -39,6 +39,13 @@ impl GpuBases {
     pub fn len(&self) -> usize {
         unsafe { sys::zkp_g1_bases_len(self.ptr) }
     }
+    /// Every point on the curve and in G1 (zkp_g1_bases_validate): for an SRS that did not come from typed, checked arkworks values.
+    pub fn validate(&self) -> sys::zkp_g1_validation {
+        let mut rep: sys::zkp_g1_validation = unsafe { core::mem::zeroed() };
+        let rc = unsafe { sys::zkp_g1_bases_validate(self.ptr, core::ptr::null_mut(), &mut rep) };
+        assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
+        rep
+    }
 }
 impl Drop for GpuBases {
     fn drop(&mut self) {
@@ -53,6 +60,15 @@ impl KzgScheme {
     pub fn new(srs: Srs) -> Self {
         let bases = GpuBases::upload(&srs.g1_points());
         Self(srs, bases)
+    }
+
+    /// `new` for an SRS read from outside (a file, a ceremony transcript): the report of the GPU validity check comes back with the
+    /// scheme, `bad == 0` means every point is a G1 point.  A bad point is the caller's decision, not a panic: the report names the
+    /// first one.  (Whether the points are the powers of one secret is zkp_srs_check, which needs [s]_2 and random scalars.)
+    pub fn new_checked(srs: Srs) -> (Self, sys::zkp_g1_validation) {
+        let scheme = Self::new(srs);
+        let report = scheme.1.validate();
+        (scheme, report)
     }
 
     /// scheme.rs:84-96 -- the one seam: sum_i c_i [s^i]G_1 as ONE Pippenger MSM on the GPU(s) instead of n double-and-add

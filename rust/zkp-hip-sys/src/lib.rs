@@ -30,6 +30,18 @@ pub struct zkp_bases_expansion {
     pub bytes: usize,     // device bytes of the planes, summed over shards
 }
 
+/// report of zkp_g1_validate* / zkp_g1_bases_validate; status of a point: 0 valid, 1 non-canonical, 2 off the curve, 3 outside G1
+#[repr(C)]
+pub struct zkp_g1_validation {
+    pub checked: u64,
+    pub bad: u64,
+    pub non_canonical: u64,
+    pub off_curve: u64,
+    pub outside_subgroup: u64,
+    pub first_bad: u64,    // lowest bad index, or n when bad == 0
+    pub first_status: i32, // its status, or 0
+}
+
 /// struct Proof of plonk/src/prover.rs:23-41 in ABI form
 #[repr(C)]
 pub struct zkp_plonk_proof {
@@ -128,6 +140,10 @@ extern "C" {
     pub fn zkp_g1_bases_info(b: *const zkp_bases, window_bits: *mut u32, slices: *mut u32) -> i32;
     pub fn zkp_g1_bases_expansion(b: *const zkp_bases, out: *mut zkp_bases_expansion) -> i32;
     pub fn zkp_g1_bases_destroy(b: *mut zkp_bases);
+    pub fn zkp_g1_validate_dev(d_xy: *const c_void, d_is_inf: *const u8, n: usize, d_status: *mut u8, stream: *mut c_void, out: *mut zkp_g1_validation) -> i32;
+    pub fn zkp_g1_validate(xy: *const u64, is_inf: *const u8, n: usize, status: *mut u8, out: *mut zkp_g1_validation) -> i32;
+    pub fn zkp_g1_bases_validate(b: *const zkp_bases, status: *mut u8, out: *mut zkp_g1_validation) -> i32;
+    pub fn zkp_srs_check(srs: *const zkp_bases, g2s_xy: *const u64, n: usize, r: *const u64, accepted: *mut i32) -> i32;
     pub fn zkp_msm_g1(bases: *const zkp_bases, scalars: *const u64, n: usize, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_msm_g1_dev(bases: *const zkp_bases, d_scalars: *const c_void, n: usize, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_msm_g1_batch_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;

@@ -10,7 +10,7 @@ PRIM = {"uint64_t": "u64", "uint8_t": "u8", "int": "i32", "unsigned": "u32", "si
         "zkp_plonk_transcript": "zkp_plonk_transcript", "zkp_plonk_proof": "zkp_plonk_proof", "zkp_ntt_layout": "zkp_ntt_layout",
         "zkp_ntt_shard_geometry": "zkp_ntt_shard_geometry", "zkp_nova_r1cs": "zkp_nova_r1cs", "zkp_nova_transcript": "zkp_nova_transcript",
         "zkp_csr": "zkp_csr", "zkp_plonk_gates": "zkp_plonk_gates", "zkp_nova_instance": "zkp_nova_instance", "zkp_nova_proof": "zkp_nova_proof",
-        "zkp_bases_expansion": "zkp_bases_expansion"}
+        "zkp_bases_expansion": "zkp_bases_expansion", "zkp_g1_validation": "zkp_g1_validation"}
 RET = {"int": "i32", "void": "()", "size_t": "usize", "const char *": "*const c_char", "const char*": "*const c_char"}
 
 
@@ -70,6 +70,18 @@ pub struct zkp_bases_expansion {
     pub glv: u32,         // 1: zkp_g1_bases_precompute_glv
     pub widest_slice_bits: u32,
     pub bytes: usize,     // device bytes of the planes, summed over shards
+}
+
+/// report of zkp_g1_validate* / zkp_g1_bases_validate; status of a point: 0 valid, 1 non-canonical, 2 off the curve, 3 outside G1
+#[repr(C)]
+pub struct zkp_g1_validation {
+    pub checked: u64,
+    pub bad: u64,
+    pub non_canonical: u64,
+    pub off_curve: u64,
+    pub outside_subgroup: u64,
+    pub first_bad: u64,    // lowest bad index, or n when bad == 0
+    pub first_status: i32, // its status, or 0
 }
 
 /// struct Proof of plonk/src/prover.rs:23-41 in ABI form

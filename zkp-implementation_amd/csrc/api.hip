@@ -26,6 +26,7 @@
 #include "host_ff.hpp"
 #include "kzg_host.hpp"
 #include "msm.hpp"
+#include "g1_check.hpp"
 #include "ntt.hpp"
 #include "plonk.hpp"
 #include "nova.hpp"
@@ -837,6 +838,20 @@ int unexpand_single(zkp_bases* b) {
     return ZKP_OK;
 }
 
+// device memory belongs to one device: an entry that is given a device pointer works on the slot of that device (the thread's
+// zkp_set_device() slot when it matches, else the first slot on the pointer's device)
+int slot_of_device_pointer(const void* d_ptr, int* slot) {
+    *slot = t_slot;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, d_ptr) != hipSuccess) return ZKP_OK;
+    std::lock_guard<std::mutex> g(g_rt.mu);
+    if (*slot >= 0 && *slot < (int)g_rt.slots.size() && g_rt.slots[(size_t)*slot]->device != attr.device) *slot = -1;
+    for (size_t i = 0; *slot < 0 && i < g_rt.slots.size(); i++)
+        if (g_rt.slots[i]->device == attr.device) *slot = (int)i;
+    if (*slot < 0 && !g_rt.slots.empty()) return fail(ZKP_E_ARG, "device pointer belongs to a device the library was not initialised on");
+    return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -878,19 +893,8 @@ int zkp_g1_bases_create(const uint64_t* xy, const uint8_t* is_inf, size_t n, zkp
 
 int zkp_g1_bases_create_dev(const void* d_xy, const uint8_t* d_is_inf, size_t n, void* stream, zkp_bases** out) try {
     if (!out || (n && !d_xy)) return fail(ZKP_E_ARG, "null argument");
-    // device memory belongs to one device: the handle lives on the slot of that device (the thread's zkp_set_device() slot when
-    // it matches, else the first slot on the pointer's device)
     int slot = t_slot;
-    if (n) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, d_xy) == hipSuccess) {
-            std::lock_guard<std::mutex> g(g_rt.mu);
-            if (slot >= 0 && slot < (int)g_rt.slots.size() && g_rt.slots[(size_t)slot]->device != attr.device) slot = -1;
-            for (size_t i = 0; slot < 0 && i < g_rt.slots.size(); i++)
-                if (g_rt.slots[i]->device == attr.device) slot = (int)i;
-            if (slot < 0 && !g_rt.slots.empty()) return fail(ZKP_E_ARG, "device pointer belongs to a device the library was not initialised on");
-        }
-    }
+    if (n) ZCHK(slot_of_device_pointer(d_xy, &slot));
     CTX_ENTER(slot);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WsOrder ord(st);
@@ -1445,4 +1449,5 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "plonk_compile_host.inc"
 #include "fri_host.inc"
 #include "verify_host.inc"
+#include "g1_check_host.inc"
 #include "nova_host.inc"

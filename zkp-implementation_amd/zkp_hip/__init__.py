@@ -52,6 +52,10 @@ _SIGS = {
     "zkp_g1_bases_info": ([_VP, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], C.c_int),
     "zkp_g1_bases_expansion": ([_VP, _VP], C.c_int),
     "zkp_g1_bases_destroy": ([_VP], None),
+    "zkp_g1_validate_dev": ([_VP, _U8P, _SZ, _U8P, _VP, _VP], C.c_int),
+    "zkp_g1_validate": ([_VP, _U8P, _SZ, _U8P, _VP], C.c_int),
+    "zkp_g1_bases_validate": ([_VP, _U8P, _VP], C.c_int),
+    "zkp_srs_check": ([_VP, _VP, _SZ, _VP, C.POINTER(C.c_int)], C.c_int),
     "zkp_msm_g1": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1_batch_dev": ([_VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
@@ -273,6 +277,50 @@ class _BasesExpansion(C.Structure):  # zkp_bases_expansion in include/zkp_hip.h
                 ("bytes", C.c_size_t)]
 
 
+class _G1Validation(C.Structure):  # zkp_g1_validation in include/zkp_hip.h
+    _fields_ = [("checked", C.c_uint64), ("bad", C.c_uint64), ("non_canonical", C.c_uint64), ("off_curve", C.c_uint64),
+                ("outside_subgroup", C.c_uint64), ("first_bad", C.c_uint64), ("first_status", C.c_int)]
+
+
+G1_VALID, G1_NON_CANONICAL, G1_OFF_CURVE, G1_OUTSIDE_SUBGROUP = 0, 1, 2, 3  # status byte of a point
+
+
+def _validation_dict(v):
+    return {name: int(getattr(v, name)) for name, _ in _G1Validation._fields_}
+
+
+def g1_validate(xy, is_inf=None, want_status=False):
+    """zkp_g1_validate: n x 12 limbs of host memory checked on the GPU (canonical, on the curve, in G1) -> the report as a dict of
+    checked, bad, non_canonical, off_curve, outside_subgroup, first_bad, first_status; with want_status (report, (n,) uint8 statuses)."""
+    xy = _np(xy, np.uint64, (-1, 12))
+    inf = _np(is_inf, np.uint8) if is_inf is not None else None
+    status = np.zeros(xy.shape[0], dtype=np.uint8) if want_status else None
+    v = _G1Validation()
+    _chk(lib().zkp_g1_validate(_ptr(xy), _ptr(inf), xy.shape[0], _ptr(status), C.byref(v)))
+    return (_validation_dict(v), status) if want_status else _validation_dict(v)
+
+
+def g1_validate_dev(xy_tensor, n, is_inf_tensor=None, status_tensor=None, stream=None):
+    """zkp_g1_validate_dev: the same over n x 12 limbs resident on the device; status_tensor: n bytes on the device, or None."""
+    inf = _dev_ptr(is_inf_tensor, n) if is_inf_tensor is not None else None
+    st = _dev_ptr(status_tensor, n) if status_tensor is not None else None
+    v = _G1Validation()
+    _chk(lib().zkp_g1_validate_dev(_dev_ptr(xy_tensor, 96 * n), inf, n, st, _stream_ptr(stream), C.byref(v)))
+    return _validation_dict(v)
+
+
+def srs_check(bases, g2s, n, r):
+    """zkp_srs_check: are the first n points of the handle [s^i]G for the s behind g2s = [s]_2?  r: (n - 1, 4) random Fr limbs.
+    -> 1 accepted, 0 rejected.  Assumes valid points: G1Bases.validate() first."""
+    g2s = _np(g2s, np.uint64, (24,))
+    r = _np(r, np.uint64, (-1, 4)) if n > 1 else None
+    if r is not None and r.shape[0] < n - 1:
+        raise ZkpError(ZKP_E_ARG, "srs_check needs n - 1 random scalars")
+    ok = C.c_int(0)
+    _chk(lib().zkp_srs_check(bases._h, _ptr(g2s), n, _ptr(r), C.byref(ok)))
+    return int(ok.value)
+
+
 class G1Bases:
     """Base points resident in HBM (the SRS of kzg/src/srs.rs:14-21, uploaded once)."""
 
@@ -305,6 +353,14 @@ class G1Bases:
         e = _BasesExpansion()
         _chk(lib().zkp_g1_bases_expansion(self._h, C.byref(e)))
         return {name: int(getattr(e, name)) for name, _ in _BasesExpansion._fields_}
+
+    def validate(self, want_status=False):
+        """zkp_g1_bases_validate: every point of the handle on the curve and in G1 (statuses 0, 2, 3) -> report dict, or
+        (report, (len,) uint8 statuses).  Call it before precompute(glv=True) on points that were not checked elsewhere."""
+        status = np.zeros(len(self), dtype=np.uint8) if want_status else None
+        v = _G1Validation()
+        _chk(lib().zkp_g1_bases_validate(self._h, _ptr(status), C.byref(v)))
+        return (_validation_dict(v), status) if want_status else _validation_dict(v)
 
     def shards(self):
         """[(slot, hip_device, offset, length)] of the chunks of this handle (one entry for a single-slot handle)."""
