@@ -252,6 +252,47 @@ int zkp_kzg_commit(const zkp_bases *srs, const uint64_t *coeffs, size_t len, uin
 int zkp_kzg_open(const zkp_bases *srs, const uint64_t *coeffs, size_t len, const uint64_t z[4], uint64_t out_xy[12],
                  uint8_t *out_is_inf, uint64_t out_eval[4]);
 
+/* ---- Transform over G1 POINTS (beyond the reference's surface; csrc/g1_ntt.hpp).  n = 2^log_n, w = the root zkp_ntt_fr uses for
+ *      the same log_n, natural order in and out:
+ *        forward  Y_i = sum_{j<n} [w^(ij)] P_j          inverse  P_j = [n^-1] sum_{i<n} [w^(-ij)] Y_i
+ *      Points are n x 12 limbs + n flag bytes as everywhere; the limbs of a point flagged as infinity are ignored on input and
+ *      written as zeros on output.  Inputs are NOT validated (zkp_g1_validate* does that): garbage in, garbage out, never a fault.
+ *      One lane per butterfly multiplies a variable point by a 255-bit twiddle: endomorphism split, joint double-and-add over
+ *      {P, phi(P), P + phi(P)}, complete additions.  The cost is n/2 log_n such multiplications; nothing here is a memory-bound pass.
+ *      log_n > 24 is ZKP_E_ARG; a workspace (256 B per point + at most 64 MiB) that does not fit is ZKP_E_NOMEM with the sizes in
+ *      zkp_last_error() and nothing left allocated.  The *_dev entries return without synchronising, with two exceptions shared by
+ *      all of them: the first call on a device slot uploads 41 KB of twiddle constants and waits for them, and a call that needs a
+ *      larger workspace than the slot holds allocates it. ---- */
+/* P_i <- [k_i] P_i in place: d_xy n x 12 limbs, d_scalars n x 4 limbs (Fr memory form), all device memory of one device (the slot
+ * is chosen from d_xy as in zkp_g1_bases_create_dev).  d_is_inf may be NULL (every point finite; a product that is the identity is
+ * then written as zeros only).  k = 0 and P = O give O without arithmetic.  n == 0 does nothing. */
+int zkp_g1_scale_dev(void *d_xy, uint8_t *d_is_inf, const void *d_scalars, size_t n, void *stream);
+/* In place on device memory; d_is_inf is required (a transform of finite points has infinite outputs). */
+int zkp_g1_ntt_dev(void *d_xy, uint8_t *d_is_inf, unsigned log_n, int inverse, void *stream);
+/* The same on host memory, on the thread's zkp_set_device() slot or slot 0. */
+int zkp_g1_ntt(uint64_t *xy, uint8_t *is_inf, unsigned log_n, int inverse);
+/* The Lagrange-basis SRS: the inverse transform of the first n points of `srs`, i.e. [L_i(s)]G for an SRS [s^i]G, as an ordinary
+ * unexpanded handle of n points on the source's slot -- every MSM / KZG / PLONK entry, both expansions and zkp_g1_bases_validate
+ * take it, and zkp_kzg_commit(lagrange, evals, n) is the commitment of the interpolant of `evals` on the domain.  The source may be
+ * plain or expanded either way; a sharded source is ZKP_E_ARG (multi-device transforms are not built), fewer than n points ZKP_E_SIZE. */
+int zkp_g1_bases_lagrange(const zkp_bases *srs, unsigned log_n, zkp_bases **out);
+/* All n openings of one polynomial at the n roots of unity (Feist-Khovratovich): for f = sum_{k<len} f_k X^k, len <= n,
+ *   out point m = [(f(s) - f(w^m)) / (s - w^m)]G = what zkp_kzg_open returns at z = w^m, and out_evals[m] = f(w^m),
+ * from three point transforms (two of 2n, one of n) and one pointwise scaling instead of n MSMs.  An opener holds the transform of
+ * the SRS (256 B x 2n) and the workspaces of a call (about 850 B x n); log_n is 1 .. 23 (else ZKP_E_ARG), the source needs n - 1
+ * points (ZKP_E_SIZE) on one device (sharded: ZKP_E_ARG) and may be destroyed afterwards.  len == 0 is ZKP_E_ARG as in zkp_kzg_open,
+ * len > n ZKP_E_SIZE; coefficients are used as given, zero-padded (an all-zero or constant vector gives n identities).
+ * out_xy n x 12 limbs, out_is_inf n bytes, out_evals n x 4 limbs or NULL.  Calls on one opener are serialised with its slot. */
+typedef struct zkp_kzg_opener zkp_kzg_opener;
+int zkp_kzg_opener_create(const zkp_bases *srs, unsigned log_n, zkp_kzg_opener **out);
+void zkp_kzg_opener_destroy(zkp_kzg_opener *o);
+int zkp_kzg_open_all(const zkp_kzg_opener *o, const uint64_t *coeffs, size_t len, uint64_t *out_xy, uint8_t *out_is_inf,
+                     uint64_t *out_evals);
+/* Everything in device memory of the opener's device, launched on `stream`.  Neither allocates nor synchronises: the opener owns
+ * the workspaces, and zkp_kzg_opener_create has already built the plans and tables of the two Fr transforms a call runs. */
+int zkp_kzg_open_all_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_t len, void *d_out_xy, uint8_t *d_out_is_inf,
+                         void *d_out_evals, void *stream);
+
 /* ---- single scalar multiplication: KzgScheme::commit_para, kzg/src/scheme.rs:78-82 (`g1_0.mul(para)`),
  *      6x per proof at plonk/src/prover.rs:183-188.  Serial by nature: computed on the host. ---- */
 int zkp_g1_mul(const uint64_t base_xy[12], uint8_t base_is_inf, const uint64_t scalar[4], uint64_t out_xy[12],

@@ -18,6 +18,7 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_plonk_transcript { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_r1cs { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_kzg_opener { _private: [u8; 0] }
 
 /// how a bases handle is expanded (zkp_g1_bases_expansion); all zero when it is not
 #[repr(C)]
@@ -156,6 +157,14 @@ extern "C" {
     pub fn zkp_g1_xyzz_sum(partials: *const u64, count: usize, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_kzg_commit(srs: *const zkp_bases, coeffs: *const u64, len: usize, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_kzg_open(srs: *const zkp_bases, coeffs: *const u64, len: usize, z: *const u64, out_xy: *mut u64, out_is_inf: *mut u8, out_eval: *mut u64) -> i32;
+    pub fn zkp_g1_scale_dev(d_xy: *mut c_void, d_is_inf: *mut u8, d_scalars: *const c_void, n: usize, stream: *mut c_void) -> i32;
+    pub fn zkp_g1_ntt_dev(d_xy: *mut c_void, d_is_inf: *mut u8, log_n: u32, inverse: i32, stream: *mut c_void) -> i32;
+    pub fn zkp_g1_ntt(xy: *mut u64, is_inf: *mut u8, log_n: u32, inverse: i32) -> i32;
+    pub fn zkp_g1_bases_lagrange(srs: *const zkp_bases, log_n: u32, out: *mut *mut zkp_bases) -> i32;
+    pub fn zkp_kzg_opener_create(srs: *const zkp_bases, log_n: u32, out: *mut *mut zkp_kzg_opener) -> i32;
+    pub fn zkp_kzg_opener_destroy(o: *mut zkp_kzg_opener);
+    pub fn zkp_kzg_open_all(o: *const zkp_kzg_opener, coeffs: *const u64, len: usize, out_xy: *mut u64, out_is_inf: *mut u8, out_evals: *mut u64) -> i32;
+    pub fn zkp_kzg_open_all_dev(o: *const zkp_kzg_opener, d_coeffs: *const c_void, len: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, d_out_evals: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_g1_mul(base_xy: *const u64, base_is_inf: u8, scalar: *const u64, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_g1_fixed_base_mul_dev(d_scalars: *const c_void, n: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_fq_inverse_dev(d_in: *const c_void, n: usize, form: i32, d_out: *mut c_void, stream: *mut c_void) -> i32;

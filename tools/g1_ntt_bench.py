@@ -1,0 +1,121 @@
+"""The transform over G1 points and what is built on it, one process, device events around each call, median of three after a
+warm-up of the same shape; the shader clock of the library's multiply-add probe is printed before and after.  Not part of bench.py.
+  - zkp_g1_ntt_dev at 2^12 / 2^16 / 2^20
+  - zkp_g1_bases_lagrange at 2^16 / 2^20
+  - zkp_kzg_opener_create and zkp_kzg_open_all_dev at n = 2^10 / 2^12 / 2^14 / 2^16, next to what the library offered for the same
+    result before: zkp_kzg_open, 64 calls at the same length, the time per call MULTIPLIED BY n (labelled as such: an extrapolation)
+Prints markdown tables (profiles/g1_ntt.md).
+python tools/g1_ntt_bench.py [--ntt 12,16,20] [--lagrange 16,20] [--open 10,12,14,16]   (an empty list skips a part)"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "zkp-implementation_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+import zkp_hip as zkp  # noqa: E402
+
+ap = argparse.ArgumentParser()
+for name, default in (("ntt", "12,16,20"), ("lagrange", "16,20"), ("open", "10,12,14,16")):
+    ap.add_argument("--" + name, default=default)
+args = ap.parse_args()
+sizes = lambda s: [int(x) for x in s.split(",") if x]
+
+zkp.init()
+dev = torch.device("cuda", 0)
+SECRET = bench.fr_mont([0x1F2E3D4C5B6A7988])[0]
+
+
+def event_ms(fn, reps=3):
+    """median device time of fn(), which enqueues on the current stream; one warm-up of the same shape first"""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out)
+
+
+def host_ms(fn, reps=3):
+    """median host time of a call that synchronises before it returns (handle and opener creation)"""
+    out = []
+    for _ in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h = fn()
+        out.append((time.perf_counter() - t0) * 1e3)
+        h.close()
+    return statistics.median(out[1:])
+
+
+def clock():
+    rate, mhz, _ = zkp.probe_mad_rate()
+    return f"{mhz:.0f} MHz ({rate / 1e12:.2f} T lane-mads/s)"
+
+
+def random_points(n, seed):
+    pts = torch.zeros(n * 12, dtype=torch.int64, device=dev)
+    zkp.g1_fixed_base_mul_dev(bench.rand_fr_tensor(torch, n, seed, dev), n, pts)
+    torch.cuda.synchronize()
+    return pts
+
+
+print(f"shader clock of the multiply-add probe before: {clock()}\n")
+if sizes(args.ntt):
+    print("| points | zkp_g1_ntt_dev forward | inverse | us per butterfly multiplication (n/2 log n of them) |")
+    print("|---|---|---|---|")
+    for ln in sizes(args.ntt):
+        n = 1 << ln
+        pts, inf = random_points(n, 1), torch.zeros(n, dtype=torch.uint8, device=dev)
+        fwd = event_ms(lambda: zkp.g1_ntt_dev(pts, inf, ln))
+        inv = event_ms(lambda: zkp.g1_ntt_dev(pts, inf, ln, inverse=True))
+        print(f"| 2^{ln} | {fwd:.1f} ms | {inv:.1f} ms | {fwd * 1e3 / (n // 2 * ln):.3f} |", flush=True)
+        del pts
+
+if sizes(args.lagrange):
+    print("\n| points | zkp_g1_bases_lagrange |\n|---|---|")
+    for ln in sizes(args.lagrange):
+        n = 1 << ln
+        srs = zkp.G1Bases.from_device(random_points(n, 2), n)
+        print(f"| 2^{ln} | {host_ms(lambda: srs.lagrange(ln)):.1f} ms |", flush=True)
+        srs.close()
+
+if sizes(args.open):
+    print("\n| n | zkp_kzg_opener_create | zkp_kzg_open_all_dev | zkp_kzg_open, one call (median of 64) | ... x n (extrapolated) | open_all / (open x n) |")
+    print("|---|---|---|---|---|---|")
+    for ln in sizes(args.open):
+        n = 1 << ln
+        srs = zkp.G1Bases.from_host(zkp.srs_g1(SECRET, n))
+        t_create = host_ms(lambda: zkp.KzgOpener(srs, ln))
+        op = zkp.KzgOpener(srs, ln)
+        coeffs = bench.rand_fr_tensor(torch, n, 3, dev)
+        out_xy = torch.zeros(n * 12, dtype=torch.int64, device=dev)
+        out_inf = torch.zeros(n, dtype=torch.uint8, device=dev)
+        out_ev = torch.zeros(n * 4, dtype=torch.int64, device=dev)
+        t_all = event_ms(lambda: op.open_all_dev(coeffs, n, out_xy, out_inf, out_ev))
+        srs.precompute(0)  # what a KzgScheme does to its SRS before it opens
+        host_coeffs = coeffs.cpu().numpy().view(np.uint64).reshape(n, 4)
+        z = bench.fr_mont(list(range(2, 66)))
+        zkp.kzg_open(srs, host_coeffs, z[0])
+        one = []
+        for k in range(64):
+            t0 = time.perf_counter()
+            zkp.kzg_open(srs, host_coeffs, z[k])
+            one.append((time.perf_counter() - t0) * 1e3)
+        t_one = statistics.median(one)
+        print(f"| 2^{ln} | {t_create:.1f} ms | {t_all:.1f} ms | {t_one:.3f} ms | {t_one * n / 1e3:.2f} s | {t_all / (t_one * n):.3f} |", flush=True)
+        op.close()
+        srs.close()
+
+print(f"\nshader clock of the multiply-add probe after: {clock()}")

@@ -10,7 +10,7 @@ PRIM = {"uint64_t": "u64", "uint8_t": "u8", "int": "i32", "unsigned": "u32", "si
         "zkp_plonk_transcript": "zkp_plonk_transcript", "zkp_plonk_proof": "zkp_plonk_proof", "zkp_ntt_layout": "zkp_ntt_layout",
         "zkp_ntt_shard_geometry": "zkp_ntt_shard_geometry", "zkp_nova_r1cs": "zkp_nova_r1cs", "zkp_nova_transcript": "zkp_nova_transcript",
         "zkp_csr": "zkp_csr", "zkp_plonk_gates": "zkp_plonk_gates", "zkp_nova_instance": "zkp_nova_instance", "zkp_nova_proof": "zkp_nova_proof",
-        "zkp_bases_expansion": "zkp_bases_expansion", "zkp_g1_validation": "zkp_g1_validation"}
+        "zkp_bases_expansion": "zkp_bases_expansion", "zkp_g1_validation": "zkp_g1_validation", "zkp_kzg_opener": "zkp_kzg_opener"}
 RET = {"int": "i32", "void": "()", "size_t": "usize", "const char *": "*const c_char", "const char*": "*const c_char"}
 
 
@@ -60,6 +60,7 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_plonk_transcript { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_r1cs { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_kzg_opener { _private: [u8; 0] }
 
 /// how a bases handle is expanded (zkp_g1_bases_expansion); all zero when it is not
 #[repr(C)]

@@ -28,6 +28,7 @@
 #include "msm.hpp"
 #include "g1_check.hpp"
 #include "ntt.hpp"
+#include "g1_ntt.hpp"
 #include "plonk.hpp"
 #include "nova.hpp"
 #include "fri.hpp"
@@ -256,6 +257,8 @@ struct Ctx {
     PinnedBuf fri_small;          // the few dozen words zkp_fri_prove reads back after the folding phase
     DevBuf fb_table;              // fixed-base table (32 x 255 affine points)
     bool fb_ready = false;
+    DevBuf g1_ntt_tw;             // twiddle constants of the transform over points (g1_ntt_host.inc), every size and direction
+    bool g1_ntt_tw_ready = false;
     DevBuf tmp;                   // staging for host-pointer entry points
     Event copy_event;
     std::vector<Event> copy_events;  // one per scalar range of a host-fed MSM beyond the first (created on demand)
@@ -1450,4 +1453,5 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "fri_host.inc"
 #include "verify_host.inc"
 #include "g1_check_host.inc"
+#include "g1_ntt_host.inc"
 #include "nova_host.inc"

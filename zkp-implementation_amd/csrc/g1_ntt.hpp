@@ -1,0 +1,207 @@
+// g1_ntt.hpp -- the transform over G1 POINTS, Y_i = sum_j [w^(ij)] P_j, and the variable-base scalar multiplication under it
+// (zkp_g1_ntt*, zkp_g1_scale_dev, zkp_g1_bases_lagrange, zkp_kzg_open_all: include/zkp_hip.h; driver: g1_ntt_host.inc; every index:
+// g1_ntt_plan.hpp).
+//
+// Between the load and the store a vector lives in the workspace as XYZZ points on 28-bit limbs (g1_28.hpp) in the plane-major
+// layout of the bucket arrays: chunk q of point e at ws[q * capacity + e].  The kernels:
+//   g1_ntt_load_kernel<RAW>   96-byte ABI points or the 128-byte points of a handle -> the workspace, bit-reversed when asked
+//   g1_ntt_butterfly_kernel   one lane per butterfly of a stage: (a, b) <- (a + [w]b, a - [w]b)
+//   g1_ntt_mul_kernel         one lane per point: P_i <- [c k_i] P_i (the pointwise step, zkp_g1_scale_dev, the n^-1 of an inverse)
+//   g1_ntt_slice_kernel       a run of points of one workspace into another, identities behind it
+//   g1_ntt_store_kernel<RAW>  the workspace -> affine, one safegcd inversion per lane
+//
+// [k]P for a variable P (g1_28_mul_glv): k = k1 + lambda k2 (glv_split, both halves below 2^128), then ONE joint MSB-first
+// double-and-add over {P, phi(P), P + phi(P)}: 128 doublings and ~96 additions instead of 255 and ~128.  The table does not fit the
+// register file next to the accumulator and the temporaries of an addition, so it stays in memory: P is the lane's own operand in the
+// workspace (nothing overwrites it before the lane's final store), phi(P) is P with X multiplied by beta when it is loaded, and
+// P + phi(P) goes to the lane's entry of a launch-sized table.  That sum is made by the loop's own addition in an iteration of its
+// own, so the kernel holds one copy of the addition and one of the doubling.  Every addition is the complete one (g1_28_add): ordinary
+// inputs make butterflies add equal and opposite points (a constant vector, a padded one).
+//
+// Operand bounds: as g1_28.hpp, with one extension -- a negated Y is 8p - Y (sub8), at most 8p with limbs below 2^28 after
+// normalise().  Every use of a stored Y in g1_28_add / g1_28_double / xyzz_finish holds for 8p: Y ZZZ is 8 * 2 of the 2520 p^2 a
+// product may reach, 2Y < 16p squares to 256, and sub8's constant 8p still dominates it.
+// Garbage input (points off the curve, non-canonical limbs) gives garbage output; no index and no trip count depends on the data.
+#pragma once
+#include "fr29.hpp"
+#include "msm.hpp"
+#include "g1_check.hpp"  // G1Check28::beta()
+#include "g1_ntt_plan.hpp"
+
+namespace zkp {
+
+// tight (< 2p) -> canonical (< p), 28-bit limbs: through the 30-bit form whose conditional subtraction exists (fq28_inv.hpp)
+ZKP_DEV S30 s30_canonical(const Fq28& a) {
+    S30 g = s30_from_fq28(a);
+    s30_reduce_once(g);
+    return g;
+}
+ZKP_DEV Fq28 fq28_canonical(const Fq28& a) { return fq28_from_s30(s30_canonical(a)); }
+// tight internal residue (radix 2^392) -> the ABI's saturated canonical residue (radix 2^384): x 2^392 * 2^384 / 2^392
+ZKP_DEV Fq fq28_to_abi(const Fq28& a) {
+    const S30 d = s30_canonical(a * fq28_from_sat(Fq::one()));
+    Fq y;
+#pragma unroll
+    for (int w = 0; w < 12; w++) {
+        const int bit = 32 * w, lo = bit / 30, sh = bit % 30;
+        uint64_t v = (uint64_t)(uint32_t)d.v[lo] >> sh;
+        if (lo + 1 < NL30) v |= (uint64_t)(uint32_t)d.v[lo + 1] << (30 - sh);
+        if (lo + 2 < NL30) v |= (uint64_t)(uint32_t)d.v[lo + 2] << (60 - sh);
+        y.l[w] = (uint32_t)v;
+    }
+    return y;
+}
+
+// [k]P: k canonical (8 words, below r), P finite at p[q * pst]; t[q * tst] is the lane's table entry.  See the head of this file.
+ZKP_DEV X28 g1_28_mul_glv(const uint32_t* k, const uint4* p, uint64_t pst, uint4* t, uint64_t tst) {
+    const GlvHalves h = glv_split(k);
+    uint32_t a0 = h.k1[0], a1 = h.k1[1], a2 = h.k1[2], a3 = h.k1[3];
+    uint32_t b0 = h.k2[0], b1 = h.k2[1], b2 = h.k2[2], b3 = h.k2[3];
+    const Fq28 beta = G1Check28::beta();
+    X28 acc = X28::infinity();
+#pragma unroll 1
+    for (int i = -1; i < 128; i++) {
+        uint32_t sel;
+        if (i < 0) {  // the iteration that makes the third table entry: P + phi(P)
+            acc = X28::load_s(p, pst);
+            sel = 2;
+        } else {
+            if (!acc.is_inf()) acc = g1_28_double(acc);
+            sel = (a3 >> 31) | ((b3 >> 31) << 1);  // bit 127 - i of k1 and of k2; the halves shift left by one bit per iteration
+            a3 = (a3 << 1) | (a2 >> 31); a2 = (a2 << 1) | (a1 >> 31); a1 = (a1 << 1) | (a0 >> 31); a0 <<= 1;
+            b3 = (b3 << 1) | (b2 >> 31); b2 = (b2 << 1) | (b1 >> 31); b1 = (b1 << 1) | (b0 >> 31); b0 <<= 1;
+        }
+        if (sel) {
+            const bool third = sel == 3;
+            X28 q = X28::load_s(third ? t : p, third ? tst : pst);
+            if (sel == 2) q.x = q.x * beta;  // phi(X, Y, ZZ, ZZZ) = (beta X, Y, ZZ, ZZZ); 14 * 1 of 2520, tight
+            g1_28_add(acc, q);
+        }
+        if (i < 0) {
+            acc.store_s(t, tst);
+            acc = X28::infinity();
+        }
+    }
+    return acc;
+}
+
+// w = start * prod_{bit b of e} row[b], out of Montgomery form (row: G1_NTT_TW_ROW constants of one size and direction)
+ZKP_DEV Fr g1_ntt_twiddle(const Fr* __restrict__ row, uint32_t e, bool scaled) {
+    Fr w = row[scaled ? G1_NTT_TW_NINV : G1_NTT_TW_ONE];
+#pragma unroll 1
+    for (uint32_t b = 0; e; b++, e >>= 1)
+        if (e & 1) w = w * row[b];
+    return from_mont(w);
+}
+
+template <bool RAW>
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_load_kernel(const uint4* __restrict__ in, const uint8_t* __restrict__ is_inf,
+                                                                 G1NttLoadMap map, uint64_t first, uint4* __restrict__ ws,
+                                                                 uint64_t cap) {
+    const uint64_t i = first + (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;  // slots [first, ...) of the map in this launch
+    if (i >= map.count) return;
+    const int64_t s = g1_ntt_load_source(map, i);
+    X28 p = X28::infinity();
+    if (s >= 0 && !(is_inf && is_inf[s])) {
+        A28 q;
+        if (RAW) {  // as g1_to_internal_kernel: eight modular doublings, then the bits re-sliced
+            G1Affine a = G1Affine::load(in + (uint64_t)s * 6);
+#pragma unroll 1
+            for (int k = 0; k < 8; k++) {
+                a.x = dbl(a.x);
+                a.y = dbl(a.y);
+            }
+            q.x = fq28_from_sat(a.x);
+            q.y = fq28_from_sat(a.y);
+        } else {
+            q = A28::load(in + (uint64_t)s * 8);
+        }
+        p = X28::from_affine(q);
+    }
+    p.store_s(ws + (map.rev_log ? g1_ntt_bitrev((uint32_t)i, map.rev_log) : i), cap);
+}
+
+// lanes [first, first + count) of stage `stage` of a transform of 2^log_n points; scaled: the last stage of an inverse
+__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_butterfly_kernel(uint4* ws, uint64_t cap, uint32_t log_n, uint32_t stage,
+                                                                          uint32_t first, uint32_t count, const Fr* __restrict__ row,
+                                                                          uint32_t scaled, uint4* table, uint64_t tcap) {
+    const uint32_t lane = blockIdx.x * G1_NTT_THREADS + threadIdx.x;
+    if (lane >= count) return;
+    const G1NttButterfly bf = g1_ntt_butterfly(log_n, stage, first + lane);
+    uint4* pa = ws + bf.lo;
+    uint4* pb = ws + bf.hi;
+    const bool b_inf = Fq28::load_s(pb + 8 * cap, cap).all_zero();
+    if (!b_inf && (bf.exp != 0 || scaled)) {  // [1]b and [w]O cost nothing
+        const Fr w = g1_ntt_twiddle(row, bf.exp, scaled != 0);
+        g1_28_mul_glv(w.l, pb, cap, table + lane, tcap).store_s(pb, cap);
+    }
+    const X28 a = X28::load_s(pa, cap);
+    X28 b = X28::load_s(pb, cap);
+#pragma unroll 1
+    for (int t = 0; t < 2; t++) {  // a + b to the left, a - b to the right: one copy of the addition
+        X28 s = a;
+        g1_28_add(s, b);
+        s.store_s(t ? pb : pa, cap);
+        b.y = normalise(sub8(Fq28::zero(), b.y));
+    }
+}
+
+// P_i <- [c k_i] P_i for i in [first, first + count): P_i at src[i], the product at dst[bitrev(i, rev_log)] (rev_log = 0: dst[i]; in
+// place only then).  k_i = scalars[i * scalar_step] (Montgomery; step 0: one constant), c = *factor when given.
+__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mul_kernel(const uint4* src, uint64_t scap, uint4* dst, uint64_t dcap,
+                                                                    uint32_t rev_log, const Fr* __restrict__ scalars, uint32_t scalar_step,
+                                                                    const Fr* __restrict__ factor, uint64_t first, uint32_t count,
+                                                                    uint4* table, uint64_t tcap) {
+    const uint32_t lane = blockIdx.x * G1_NTT_THREADS + threadIdx.x;
+    if (lane >= count) return;
+    const uint64_t i = first + lane;
+    Fr k = scalars[i * scalar_step];
+    if (factor) k = k * *factor;
+    k = from_mont(k);
+    const bool p_inf = Fq28::load_s(src + i + 8 * scap, scap).all_zero();
+    X28 r = X28::infinity();
+    if (!p_inf && !k.is_zero()) r = g1_28_mul_glv(k.l, src + i, scap, table + lane, tcap);
+    r.store_s(dst + (rev_log ? g1_ntt_bitrev((uint32_t)i, rev_log) : i), dcap);
+}
+
+// slot i of `map` <- src[source(i)], the identity where there is none
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_slice_kernel(const uint4* __restrict__ src, uint64_t scap, G1NttLoadMap map,
+                                                                  uint4* __restrict__ dst, uint64_t dcap) {
+    const uint64_t i = (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= map.count) return;
+    const int64_t s = g1_ntt_load_source(map, i);
+    uint4* d = dst + (map.rev_log ? g1_ntt_bitrev((uint32_t)i, map.rev_log) : i);
+#pragma unroll
+    for (int q = 0; q < 16; q++) d[q * dcap] = s >= 0 ? src[q * scap + (uint64_t)s] : make_uint4(0u, 0u, 0u, 0u);
+}
+
+// points [first, n) of the workspace to affine (as many as the launch has lanes): RAW the ABI's 96 bytes (zeros for the identity), else a handle's 128 bytes, canonical
+template <bool RAW>
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_store_kernel(const uint4* __restrict__ ws, uint64_t cap, uint64_t first, uint64_t n,
+                                                                  uint4* __restrict__ out, uint8_t* __restrict__ out_inf) {
+    const uint64_t i = first + (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const X28 p = X28::load_s(ws + i, cap);
+    const bool inf = p.is_inf();
+    const Fq28 zi3 = fq28_inverse_gcd(p.zzz);  // 0 -> 0
+    const Fq28 zi = zi3 * p.zz;                // ZZ / ZZZ = 1 / Z
+    const Fq28 x = p.x * (zi * zi), y = p.y * zi3;  // tight
+    if (RAW) {
+        G1Affine r;
+        r.x = fq28_to_abi(x);
+        r.y = fq28_to_abi(y);
+        if (inf) {
+            r.x = Fq::zero();
+            r.y = Fq::zero();
+        }
+        r.store(out + i * 6);
+    } else {
+        A28 r;
+        r.x = inf ? Fq28::zero() : fq28_canonical(x);
+        r.y = inf ? Fq28::zero() : fq28_canonical(y);
+        r.store(out + i * 8);
+    }
+    if (out_inf) out_inf[i] = inf ? 1 : 0;
+}
+
+}  // namespace zkp

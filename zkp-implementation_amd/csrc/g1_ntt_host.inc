@@ -1,0 +1,359 @@
+// g1_ntt_host.inc -- zkp_g1_scale_dev, zkp_g1_ntt*, zkp_g1_bases_lagrange and the all-openings entries zkp_kzg_opener_* /
+// zkp_kzg_open_all* (included at the end of api.hip).  The kernels are in g1_ntt.hpp, every index and size in g1_ntt_plan.hpp.
+
+namespace {
+
+// Every (log_n, direction) row of twiddle constants (g1_ntt_plan.hpp: G1_NTT_TW_ROW), built once per process and uploaded once per slot
+const std::vector<uint64_t>& g1_ntt_twiddle_rows() {
+    static const std::vector<uint64_t> rows = [] {
+        std::vector<uint64_t> t((size_t)(G1_NTT_MAX_LOG + 1) * 2 * G1_NTT_TW_ROW * 4);
+        const HFr half = HFr::from_u64(2).inverse();
+        HFr ninv = HFr::one();
+        for (unsigned log_n = 0; log_n <= G1_NTT_MAX_LOG; log_n++, ninv = ninv * half)
+            for (int inverse = 0; inverse < 2; inverse++) {
+                uint64_t* row = &t[((size_t)log_n * 2 + inverse) * G1_NTT_TW_ROW * 4];
+                HFr w = fr_root_of_unity(log_n);
+                if (inverse) w = w.inverse();
+                for (unsigned b = 0; b < G1_NTT_TW_ONE; b++, w = w.sqr()) w.store(row + 4 * b);
+                HFr::one().store(row + 4 * G1_NTT_TW_ONE);
+                ninv.store(row + 4 * G1_NTT_TW_NINV);
+            }
+        return t;
+    }();
+    return rows;
+}
+int g1_ntt_twiddle_row(unsigned log_n, int inverse, hipStream_t st, const Fr** row) {
+    Ctx& c = ctx();
+    const std::vector<uint64_t>& rows = g1_ntt_twiddle_rows();
+    if (!c.g1_ntt_tw_ready) {
+        ZCHK(c.g1_ntt_tw.ensure(8 * rows.size()));
+        HIPCHK(hipMemcpyAsync(c.g1_ntt_tw.p, rows.data(), 8 * rows.size(), hipMemcpyHostToDevice, st));  // (the source is never freed)
+        HIPCHK(hipStreamSynchronize(st));
+        c.g1_ntt_tw_ready = true;
+    }
+    *row = reinterpret_cast<const Fr*>(c.g1_ntt_tw.p) + ((size_t)log_n * 2 + (inverse ? 1 : 0)) * G1_NTT_TW_ROW;
+    return ZKP_OK;
+}
+
+// a vector of `cap` points in the plane-major workspace form, and the table its multiplying lanes use
+struct G1NttVec {
+    uint4* pts;
+    uint64_t cap;
+    uint4* table;
+    uint64_t tcap;
+};
+G1NttVec g1_ntt_carve(void* base, unsigned log_n, const G1NttSizes& sz) {
+    return G1NttVec{static_cast<uint4*>(base), (uint64_t)1 << log_n, reinterpret_cast<uint4*>(static_cast<char*>(base) + sz.points),
+                    sz.table / G1_NTT_POINT_BYTES};
+}
+
+unsigned g1_ntt_blocks(uint64_t lanes, unsigned threads) { return (unsigned)((lanes + threads - 1) / threads); }
+
+// The slot's staging buffer grown to `need` bytes, or ZKP_E_NOMEM with the sizes (a failed growth leaves the buffer released)
+int g1_ntt_workspace(size_t need, const char* what, void** out) {
+    DevBuf& tmp = ctx().tmp;
+    if (need > tmp.cap) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
+        const bool fits = !total_b || need <= free_b + tmp.cap;
+        if (!fits || tmp.grow(need) != hipSuccess) {
+            (void)hipGetLastError();
+            tmp.release();
+            return fail(ZKP_E_NOMEM, std::string(what) + ": the workspace of " + std::to_string(need) + " bytes does not fit, " +
+                                         std::to_string(free_b) + " of " + std::to_string(total_b) + " bytes free on the device");
+        }
+    }
+    *out = tmp.p;
+    return ZKP_OK;
+}
+
+// (both in launches of at most G1_NTT_IO_LAUNCH lanes, as the validation kernels)
+template <bool RAW>
+int g1_ntt_load(const void* d_pts, const uint8_t* d_inf, const G1NttLoadMap& map, const G1NttVec& v, hipStream_t st) {
+    for (uint64_t first = 0; first < map.count; first += G1_NTT_IO_LAUNCH) {
+        const uint64_t cnt = std::min<uint64_t>(G1_NTT_IO_LAUNCH, map.count - first);
+        hipLaunchKernelGGL(g1_ntt_load_kernel<RAW>, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st,
+                           static_cast<const uint4*>(d_pts), d_inf, map, first, v.pts, v.cap);
+        HIPCHK(hipGetLastError());
+    }
+    return ZKP_OK;
+}
+template <bool RAW>
+int g1_ntt_store(const G1NttVec& v, uint64_t n, void* d_out, uint8_t* d_out_inf, hipStream_t st) {
+    for (uint64_t first = 0; first < n; first += G1_NTT_IO_LAUNCH) {
+        const uint64_t cnt = std::min<uint64_t>(G1_NTT_IO_LAUNCH, n - first);
+        hipLaunchKernelGGL(g1_ntt_store_kernel<RAW>, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st, v.pts, v.cap, first,
+                           first + cnt, static_cast<uint4*>(d_out), d_out_inf);
+        HIPCHK(hipGetLastError());
+    }
+    return ZKP_OK;
+}
+
+// dst[bitrev(i)] (or dst[i]) <- [c k_i] src[i] for i < n, in launches of at most G1_NTT_LAUNCH lanes; the table is v's
+int g1_ntt_mul(const uint4* src, uint64_t scap, const G1NttVec& v, unsigned rev_log, const Fr* d_scalars, unsigned scalar_step,
+               const Fr* d_factor, uint64_t n, hipStream_t st) {
+    for (uint64_t k = 0; k < g1_ntt_launches(n); k++) {
+        const uint64_t cnt = g1_ntt_launch_lanes(n, k);
+        hipLaunchKernelGGL(g1_ntt_mul_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, src, scap, v.pts, v.cap,
+                           (uint32_t)rev_log, d_scalars, (uint32_t)scalar_step, d_factor, k * G1_NTT_LAUNCH, (uint32_t)cnt, v.table, v.tcap);
+        HIPCHK(hipGetLastError());
+    }
+    return ZKP_OK;
+}
+
+// The stages over a vector loaded in bit-reversed order; natural order out.  scale: an inverse multiplies by n^-1 as well (without
+// it the caller has folded that factor in elsewhere).
+int g1_ntt_stages(const G1NttVec& v, unsigned log_n, int inverse, bool scale, hipStream_t st) {
+    if (!log_n) return ZKP_OK;
+    const Fr* row = nullptr;
+    ZCHK(g1_ntt_twiddle_row(log_n, inverse, st, &row));
+    const uint64_t lanes = (uint64_t)1 << (log_n - 1);
+    scale = scale && inverse;
+    for (unsigned s = 0; s < log_n; s++) {
+        const bool last_scaled = scale && s == log_n - 1;
+        if (last_scaled) ZCHK(g1_ntt_mul(v.pts, v.cap, v, 0, row + G1_NTT_TW_NINV, 0, nullptr, lanes, st));  // the left operands
+        for (uint64_t k = 0; k < g1_ntt_launches(lanes); k++) {
+            const uint64_t cnt = g1_ntt_launch_lanes(lanes, k);
+            hipLaunchKernelGGL(g1_ntt_butterfly_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, v.pts, v.cap,
+                               (uint32_t)log_n, (uint32_t)s, (uint32_t)(k * G1_NTT_LAUNCH), (uint32_t)cnt, row, last_scaled ? 1u : 0u,
+                               v.table, v.tcap);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return ZKP_OK;
+}
+
+// raw device points in place; the caller is inside the slot's context
+int g1_ntt_raw_locked(void* d_xy, uint8_t* d_is_inf, unsigned log_n, int inverse, void* ws, hipStream_t st) {
+    const uint64_t n = (uint64_t)1 << log_n;
+    const G1NttVec v = g1_ntt_carve(ws, log_n, g1_ntt_sizes(log_n, n / 2));
+    ZCHK(g1_ntt_load<true>(d_xy, d_is_inf, g1_ntt_load_plain(log_n), v, st));
+    ZCHK(g1_ntt_stages(v, log_n, inverse, true, st));
+    return g1_ntt_store<true>(v, n, d_xy, d_is_inf, st);
+}
+
+const char* const kShardedG1Ntt = "bases are sharded over several devices: a transform over points runs on one device "
+                                  "(zkp_set_device + zkp_g1_bases_create* make single-device bases)";
+
+}  // namespace
+
+struct zkp_kzg_opener {
+    unsigned log_n = 0;
+    int slot = 0, device = 0;
+    DevBuf srs_hat;  // NTT_2n of the reversed SRS points: depends on the SRS and n only
+    DevBuf work;     // u, the slice h, the scalars g and the lanes' table of one call (entries of a slot are serialised)
+};
+
+extern "C" {
+
+int zkp_g1_scale_dev(void* d_xy, uint8_t* d_is_inf, const void* d_scalars, size_t n, void* stream) try {
+    if (n && (!d_xy || !d_scalars)) return fail(ZKP_E_ARG, "null argument");
+    if (!n) return ZKP_OK;
+    int slot = -1;
+    ZCHK(slot_of_device_pointer(d_xy, &slot));
+    CTX_ENTER(slot);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    const uint64_t step = std::min<uint64_t>(n, G1_NTT_LAUNCH);
+    void* ws = nullptr;
+    ZCHK(g1_ntt_workspace(2 * G1_NTT_POINT_BYTES * step, "zkp_g1_scale_dev", &ws));
+    const G1NttVec v{static_cast<uint4*>(ws), step, static_cast<uint4*>(ws) + 16 * step, step};
+    for (uint64_t off = 0; off < n; off += step) {
+        const uint64_t cnt = std::min<uint64_t>(step, n - off);
+        char* xy = static_cast<char*>(d_xy) + 96 * off;
+        uint8_t* inf = d_is_inf ? d_is_inf + off : nullptr;
+        ZCHK(g1_ntt_load<true>(xy, inf, G1NttLoadMap{cnt, cnt, 0, 1, 0}, v, st));
+        ZCHK(g1_ntt_mul(v.pts, v.cap, v, 0, static_cast<const Fr*>(d_scalars) + off, 1, nullptr, cnt, st));
+        ZCHK(g1_ntt_store<true>(v, cnt, xy, inf, st));
+    }
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_g1_ntt_dev(void* d_xy, uint8_t* d_is_inf, unsigned log_n, int inverse, void* stream) try {
+    if (!d_xy || !d_is_inf) return fail(ZKP_E_ARG, "null argument");
+    if (log_n > G1_NTT_MAX_LOG) return fail(ZKP_E_ARG, "log_n > 24");
+    int slot = -1;
+    ZCHK(slot_of_device_pointer(d_xy, &slot));
+    CTX_ENTER(slot);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    void* ws = nullptr;
+    ZCHK(g1_ntt_workspace(g1_ntt_sizes(log_n, ((uint64_t)1 << log_n) / 2).total, "zkp_g1_ntt_dev", &ws));
+    return g1_ntt_raw_locked(d_xy, d_is_inf, log_n, inverse, ws, st);
+} ZKP_CATCH_INT
+
+int zkp_g1_ntt(uint64_t* xy, uint8_t* is_inf, unsigned log_n, int inverse) try {
+    if (!xy || !is_inf) return fail(ZKP_E_ARG, "null argument");
+    if (log_n > G1_NTT_MAX_LOG) return fail(ZKP_E_ARG, "log_n > 24");
+    CTX_ENTER(-1);
+    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    WsOrder ord(st);
+    const size_t n = (size_t)1 << log_n;
+    const size_t ws_bytes = g1_ntt_sizes(log_n, n / 2).total;
+    void* ws = nullptr;
+    ZCHK(g1_ntt_workspace(ws_bytes + 96 * n + n, "zkp_g1_ntt", &ws));
+    char* d_xy = static_cast<char*>(ws) + ws_bytes;
+    uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * n);
+    HIPCHK(hipMemcpyAsync(d_xy, xy, 96 * n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_inf, is_inf, n, hipMemcpyHostToDevice, st));
+    ZCHK(g1_ntt_raw_locked(d_xy, d_inf, log_n, inverse, ws, st));
+    HIPCHK(hipMemcpyAsync(xy, d_xy, 96 * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(is_inf, d_inf, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_g1_bases_lagrange(const zkp_bases* srs, unsigned log_n, zkp_bases** out) try {
+    if (!srs || !out) return fail(ZKP_E_ARG, "null argument");
+    if (log_n > G1_NTT_MAX_LOG) return fail(ZKP_E_ARG, "log_n > 24");
+    if (!srs->shards.empty()) return fail(ZKP_E_ARG, kShardedG1Ntt);
+    const size_t n = (size_t)1 << log_n;
+    if (srs->n < n) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_n points");
+    CTX_ENTER(srs->slot);
+    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    WsOrder ord(st);
+    void* ws = nullptr;
+    ZCHK(g1_ntt_workspace(g1_ntt_sizes(log_n, n / 2).total, "zkp_g1_bases_lagrange", &ws));
+    const G1NttVec v = g1_ntt_carve(ws, log_n, g1_ntt_sizes(log_n, n / 2));
+    zkp_bases* raw = nullptr;
+    ZCHK(bases_alloc(n, true, &raw));
+    std::unique_ptr<zkp_bases, void (*)(zkp_bases*)> b(raw, zkp_g1_bases_destroy);
+    ZCHK(g1_ntt_load<false>(srs->d_xy.p, srs->d_inf.get(), g1_ntt_load_plain(log_n), v, st));  // plane 0 of an expansion: the points
+    ZCHK(g1_ntt_stages(v, log_n, 1, true, st));
+    ZCHK(g1_ntt_store<false>(v, n, b->d_xy.p, b->d_inf.get(), st));
+    HIPCHK(hipStreamSynchronize(st));
+    *out = b.release();
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_kzg_opener_create(const zkp_bases* srs, unsigned log_n, zkp_kzg_opener** out) try {
+    if (!srs || !out) return fail(ZKP_E_ARG, "null argument");
+    if (log_n < 1 || log_n + 1 > G1_NTT_MAX_LOG) return fail(ZKP_E_ARG, "log_n of an opener must be 1 .. 23");
+    if (!srs->shards.empty()) return fail(ZKP_E_ARG, kShardedG1Ntt);
+    const size_t n = (size_t)1 << log_n;
+    if (srs->n < n - 1) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_n - 1 points");
+    CTX_ENTER(srs->slot);
+    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    WsOrder ord(st);
+    const G1OpenSizes sz = g1_open_sizes(log_n);
+    std::unique_ptr<zkp_kzg_opener, void (*)(zkp_kzg_opener*)> o(new (std::nothrow) zkp_kzg_opener(), zkp_kzg_opener_destroy);
+    if (!o) return fail(ZKP_E_NOMEM, "host allocation failed");
+    o->log_n = log_n;
+    o->slot = ctx().slot;
+    o->device = ctx().device;
+    if (o->srs_hat.grow(sz.srs_hat) != hipSuccess || o->work.grow(sz.total - sz.srs_hat) != hipSuccess) {
+        (void)hipGetLastError();
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
+        return fail(ZKP_E_NOMEM, "zkp_kzg_opener_create: the workspaces of " + std::to_string(sz.total) + " bytes do not fit, " +
+                                     std::to_string(free_b) + " of " + std::to_string(total_b) + " bytes free on the device");
+    }
+    // the table of this one transform sits where the calls keep theirs: at the end of `work`
+    const G1NttVec v{static_cast<uint4*>(o->srs_hat.p), 2 * (uint64_t)n,
+                     reinterpret_cast<uint4*>(static_cast<char*>(o->work.p) + sz.work + sz.slice + sz.scalars), sz.table / G1_NTT_POINT_BYTES};
+    ZCHK(g1_ntt_load<false>(srs->d_xy.p, srs->d_inf.get(), g1_open_srs_map(log_n), v, st));
+    ZCHK(g1_ntt_stages(v, log_n + 1, 0, false, st));
+    {   // Everything a call builds on first use is built here, so that zkp_kzg_open_all_dev neither allocates nor waits: the plans, tables
+        // and scratch of the two Fr transforms (over the zeroed scalar area) and the constants of the two other point transforms
+        Fr* g = reinterpret_cast<Fr*>(static_cast<char*>(o->work.p) + sz.work + sz.slice);
+        const Fr* row = nullptr;
+        HIPCHK(hipMemsetAsync(g, 0, sz.scalars, st));
+        ZCHK(run_ntt<Fr>(g, log_n + 1, 1, 0, nullptr, st));
+        ZCHK(run_ntt<Fr>(g, log_n, 1, 0, nullptr, st));
+        ZCHK(g1_ntt_twiddle_row(log_n + 1, 1, st, &row));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    *out = o.release();
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+void zkp_kzg_opener_destroy(zkp_kzg_opener* o) {
+    if (!o) return;
+    DeviceRestore restore;
+    (void)hipSetDevice(o->device);
+    (void)hipDeviceSynchronize();  // a call may still be running on the caller's stream
+    delete o;
+}
+
+}  // extern "C"
+
+namespace {
+
+// everything on the device, on `st`; the caller is inside the opener's slot
+int kzg_open_all_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
+                        hipStream_t st) {
+    const unsigned log_n = o->log_n;
+    const uint64_t n = (uint64_t)1 << log_n;
+    const G1OpenSizes sz = g1_open_sizes(log_n);
+    char* base = static_cast<char*>(o->work.p);
+    uint4* table = reinterpret_cast<uint4*>(base + sz.work + sz.slice + sz.scalars);
+    const G1NttVec u{reinterpret_cast<uint4*>(base), 2 * n, table, sz.table / G1_NTT_POINT_BYTES};
+    const G1NttVec h{reinterpret_cast<uint4*>(base + sz.work), n, table, sz.table / G1_NTT_POINT_BYTES};
+    Fr* g = reinterpret_cast<Fr*>(base + sz.work + sz.slice);
+    // g_t = f_{t+1}: one run of the coefficients (g1_open_coeff_run), zeros behind it; transformed
+    const G1OpenCoeffRun run = g1_open_coeff_run(len);
+    HIPCHK(hipMemsetAsync(g, 0, sz.scalars, st));
+    if (run.count) HIPCHK(hipMemcpyAsync(g, static_cast<const char*>(d_coeffs) + 32 * run.first, 32 * run.count, hipMemcpyDeviceToDevice, st));
+    ZCHK(run_ntt<Fr>(g, log_n + 1, 1, 0, nullptr, st));
+    // u = iNTT_2n(srs_hat . g), the (2n)^-1 folded into the pointwise scalars; loaded bit-reversed for the stages
+    const Fr* row = nullptr;
+    ZCHK(g1_ntt_twiddle_row(log_n + 1, 1, st, &row));
+    ZCHK(g1_ntt_mul(static_cast<const uint4*>(o->srs_hat.p), 2 * n, u, log_n + 1, g, 1, row + G1_NTT_TW_NINV, 2 * n, st));
+    ZCHK(g1_ntt_stages(u, log_n + 1, 1, false, st));
+    // the proofs: NTT_n of the slice h
+    hipLaunchKernelGGL(g1_ntt_slice_kernel, dim3(g1_ntt_blocks(n, MSM_THREADS)), dim3(MSM_THREADS), 0, st, u.pts, u.cap, g1_open_slice_map(log_n),
+                       h.pts, h.cap);
+    HIPCHK(hipGetLastError());
+    ZCHK(g1_ntt_stages(h, log_n, 0, false, st));
+    ZCHK(g1_ntt_store<true>(h, n, d_out_xy, d_out_is_inf, st));
+    if (d_out_evals) {  // f on the domain
+        HIPCHK(hipMemsetAsync(d_out_evals, 0, 32 * n, st));
+        HIPCHK(hipMemcpyAsync(d_out_evals, d_coeffs, 32 * len, hipMemcpyDeviceToDevice, st));
+        ZCHK(run_ntt<Fr>(static_cast<Fr*>(d_out_evals), log_n, 1, 0, nullptr, st));
+    }
+    return ZKP_OK;
+}
+
+int kzg_open_all_args(const zkp_kzg_opener* o, const void* coeffs, size_t len, const void* out_xy, const void* out_is_inf) {
+    if (!o || !coeffs || !out_xy || !out_is_inf) return fail(ZKP_E_ARG, "null argument");
+    if (len == 0) return fail(ZKP_E_ARG, "open of an empty polynomial (kzg/src/scheme.rs:112 expects at least 1)");
+    if (len > ((size_t)1 << o->log_n)) return fail(ZKP_E_SIZE, "more coefficients than the opener's domain has points");
+    return ZKP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkp_kzg_open_all_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
+                         void* stream) try {
+    ZCHK(kzg_open_all_args(o, d_coeffs, len, d_out_xy, d_out_is_inf));
+    CTX_ENTER(o->slot);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    return kzg_open_all_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st);
+} ZKP_CATCH_INT
+
+int zkp_kzg_open_all(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, uint64_t* out_xy, uint8_t* out_is_inf,
+                     uint64_t* out_evals) try {
+    ZCHK(kzg_open_all_args(o, coeffs, len, out_xy, out_is_inf));
+    CTX_ENTER(o->slot);
+    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    WsOrder ord(st);
+    const size_t n = (size_t)1 << o->log_n;
+    void* ws = nullptr;  // coefficients | evaluations | points | flags
+    ZCHK(g1_ntt_workspace(32 * len + 32 * n + 96 * n + n, "zkp_kzg_open_all", &ws));
+    char* d_coeffs = static_cast<char*>(ws);
+    char* d_evals = d_coeffs + 32 * len;
+    char* d_xy = d_evals + 32 * n;
+    uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * n);
+    HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 32 * len, hipMemcpyHostToDevice, st));
+    ZCHK(kzg_open_all_locked(o, d_coeffs, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
+    HIPCHK(hipMemcpyAsync(out_xy, d_xy, 96 * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, n, hipMemcpyDeviceToHost, st));
+    if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+}  // extern "C"

@@ -1,0 +1,130 @@
+// g1_ntt_plan.hpp -- the index arithmetic of the transform over G1 POINTS (g1_ntt.hpp, g1_ntt_host.inc): which two points and which
+// twiddle a butterfly lane takes, where the SRS points and the coefficients of an all-openings call sit in its two vectors of 2n,
+// where the quotient slice h comes out, how large the workspaces are and how the lanes of a pass are cut into launches.  Plain
+// C++17 without HIP, so that tests/host/g1_ntt_plan.cpp checks it with g++ alone; under hipcc (ff.hpp included first) the kernels
+// call the same functions.
+//
+// The transform is a radix-2 decimation in time, in place: the load puts point i at bitrev(i), stage s = 0 .. log_n - 1 joins blocks
+// of half = 2^s points, the output is in natural order.  Y_i = sum_j [w^(ij)] P_j with w = omega_n (inverse: omega_n^-1, and n^-1
+// folded into the LAST stage: its left operands are the first n / 2 points, which one multiplication pass scales beforehand, and its
+// twiddles start from n^-1 instead of 1).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace zkp {
+
+#ifdef ZKP_HD
+#define ZKP_G1NTT_FN ZKP_HD
+#else
+#define ZKP_G1NTT_FN inline
+#endif
+
+constexpr unsigned G1_NTT_MAX_LOG = 24;              // zkp_g1_ntt*, zkp_g1_bases_lagrange; an opener transforms 2n points: 23
+constexpr uint64_t G1_NTT_LAUNCH = (uint64_t)1 << 18;  // multiplying lanes per launch: no single kernel holds a shared device for long (profiles/g1_ntt.md)
+constexpr uint64_t G1_NTT_IO_LAUNCH = (uint64_t)1 << 22;  // lanes per launch of the load and store kernels (one inversion per lane at most), as G1_CHECK_LAUNCH
+constexpr unsigned G1_NTT_THREADS = 64;              // workgroup of the multiplying kernels: one wave (they run one wave per SIMD)
+constexpr size_t G1_NTT_POINT_BYTES = 256;           // an XYZZ point of g1_28.hpp, plane-major: 16 chunks of 16 B, `capacity` apart
+// per (log_n, direction) the kernels read a row of Montgomery Fr constants: w^(2^b) for b < 24, then 1, then n^-1
+constexpr unsigned G1_NTT_TW_ONE = 24, G1_NTT_TW_NINV = 25, G1_NTT_TW_ROW = 26;
+
+ZKP_G1NTT_FN uint32_t g1_ntt_bitrev(uint32_t i, unsigned log_n) {
+    if (!log_n) return 0;
+    i = ((i & 0x55555555u) << 1) | ((i >> 1) & 0x55555555u);
+    i = ((i & 0x33333333u) << 2) | ((i >> 2) & 0x33333333u);
+    i = ((i & 0x0f0f0f0fu) << 4) | ((i >> 4) & 0x0f0f0f0fu);
+    i = ((i & 0x00ff00ffu) << 8) | ((i >> 8) & 0x00ff00ffu);
+    i = (i << 16) | (i >> 16);
+    return i >> (32 - log_n);
+}
+
+// Butterfly `i` (< n / 2) of stage `stage` (< log_n):  (P[lo], P[hi]) <- (P[lo] + [w^exp] P[hi], P[lo] - [w^exp] P[hi]).
+// Stages whose blocks are shorter than a wave number their butterflies twiddle-major -- the 64 lanes of a wave then share one
+// twiddle, and the waves of twiddle 1 skip the multiplication together -- the others block-major, where neighbouring lanes take
+// neighbouring points.  Either way every pair of a stage is taken exactly once and a lane touches its own two points only.
+struct G1NttButterfly {
+    uint32_t lo, hi, exp;
+};
+ZKP_G1NTT_FN G1NttButterfly g1_ntt_butterfly(unsigned log_n, unsigned stage, uint32_t i) {
+    const unsigned group_log = log_n - 1 - stage;  // 2^group_log blocks of 2 half points
+    const uint32_t half = 1u << stage, groups = 1u << group_log;
+    const bool twiddle_major = half < 64 && groups >= 64;
+    const uint32_t j = twiddle_major ? i >> group_log : i & (half - 1);
+    const uint32_t blk = twiddle_major ? i & (groups - 1) : i >> stage;
+    G1NttButterfly b;
+    b.lo = (blk << (stage + 1)) + j;
+    b.hi = b.lo + half;
+    b.exp = j << group_log;
+    return b;
+}
+
+// What a load kernel puts into slot i of a vector of `count` points: source point src0 + step * i for i < finite, the identity
+// behind them; the slot is stored at bitrev(i, rev_log) (rev_log = 0: at i).
+struct G1NttLoadMap {
+    uint64_t count, finite;
+    int64_t src0;
+    int32_t step;
+    uint32_t rev_log;
+};
+ZKP_G1NTT_FN int64_t g1_ntt_load_source(const G1NttLoadMap& m, uint64_t i) { return i < m.finite ? m.src0 + (int64_t)m.step * (int64_t)i : -1; }
+inline G1NttLoadMap g1_ntt_load_plain(unsigned log_n) {
+    const uint64_t n = (uint64_t)1 << log_n;
+    return G1NttLoadMap{n, n, 0, 1, log_n};
+}
+
+// All n openings of f (len <= n coefficients) over SRS points S_0 .. S_{d-1}, d = n - 1 (include/zkp_hip.h, zkp_kzg_open_all):
+//   s_j = S_{d-1-j} for j < d, identity for d <= j < 2n;   g_t = f_{t+1} for t + 1 < len, zero behind;
+//   u = iNTT_2n(NTT_2n(s) . NTT_2n(g));   h_i = u_{d-1+i} for i < d, h_d = O;   proofs = NTT_n(h).
+// (u_m = sum_{j+t=m} [g_t] s_j, so u_{d-1+i} = sum_t [f_{t+1}] S_{t-i} = sum_k [f_{i+1+k}] S_k; the largest index is 2d - 2 < 2n.)
+inline G1NttLoadMap g1_open_srs_map(unsigned log_n) {
+    const uint64_t n = (uint64_t)1 << log_n;
+    return G1NttLoadMap{2 * n, n - 1, (int64_t)n - 2, -1, log_n + 1};
+}
+struct G1OpenCoeffRun {  // slots [0, count) of g take the coefficients first, first + 1, ...: ONE copy in the driver; zeros behind
+    uint64_t first, count;
+};
+inline G1OpenCoeffRun g1_open_coeff_run(uint64_t len) { return G1OpenCoeffRun{1, len ? len - 1 : 0}; }  // (len <= n: the driver refuses more)
+inline int64_t g1_open_coeff_source(uint64_t len, uint64_t t) {  // the coefficient in slot t of g, -1: zero
+    const G1OpenCoeffRun r = g1_open_coeff_run(len);
+    return t < r.count ? (int64_t)(r.first + t) : -1;
+}
+inline G1NttLoadMap g1_open_slice_map(unsigned log_n) {  // h out of u, loaded for the transform of n
+    const uint64_t n = (uint64_t)1 << log_n;
+    return G1NttLoadMap{n, n - 1, (int64_t)n - 2, 1, log_n};
+}
+
+// Launches of a pass of `lanes` multiplying lanes: launch k covers [k * G1_NTT_LAUNCH, ...) and is the only one that may be short
+inline uint64_t g1_ntt_launches(uint64_t lanes) { return (lanes + G1_NTT_LAUNCH - 1) / G1_NTT_LAUNCH; }
+inline uint64_t g1_ntt_launch_lanes(uint64_t lanes, uint64_t k) {
+    const uint64_t first = k * G1_NTT_LAUNCH;
+    return first >= lanes ? 0 : lanes - first < G1_NTT_LAUNCH ? lanes - first : G1_NTT_LAUNCH;
+}
+
+// Bytes of the workspaces.  Every multiplying lane of a launch parks P + phi(P) in its own entry of `table`.
+struct G1NttSizes {
+    size_t points;  // the vector itself, 2^log_n XYZZ points
+    size_t table;   // one entry per lane of the longest launch
+    size_t total;
+};
+inline G1NttSizes g1_ntt_sizes(unsigned log_n, uint64_t mul_lanes) {  // mul_lanes: the longest multiplying pass the caller runs
+    G1NttSizes s;
+    s.points = G1_NTT_POINT_BYTES << log_n;
+    s.table = G1_NTT_POINT_BYTES * (size_t)(mul_lanes < G1_NTT_LAUNCH ? (mul_lanes ? mul_lanes : 1) : G1_NTT_LAUNCH);
+    s.total = s.points + s.table;
+    return s;
+}
+struct G1OpenSizes {
+    size_t srs_hat, work, slice, scalars, table, total;  // NTT_2n(s) (kept), u, h, g, the lanes' table
+};
+inline G1OpenSizes g1_open_sizes(unsigned log_n) {
+    const uint64_t n = (uint64_t)1 << log_n;
+    G1OpenSizes s;
+    s.srs_hat = s.work = G1_NTT_POINT_BYTES * 2 * n;
+    s.slice = G1_NTT_POINT_BYTES * n;
+    s.scalars = 32 * 2 * n;
+    s.table = g1_ntt_sizes(log_n + 1, 2 * n).table;
+    s.total = s.srs_hat + s.work + s.slice + s.scalars + s.table;
+    return s;
+}
+
+}  // namespace zkp

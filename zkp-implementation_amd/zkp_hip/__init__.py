@@ -56,6 +56,14 @@ _SIGS = {
     "zkp_g1_validate": ([_VP, _U8P, _SZ, _U8P, _VP], C.c_int),
     "zkp_g1_bases_validate": ([_VP, _U8P, _VP], C.c_int),
     "zkp_srs_check": ([_VP, _VP, _SZ, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_g1_scale_dev": ([_VP, _U8P, _VP, _SZ, _VP], C.c_int),
+    "zkp_g1_ntt_dev": ([_VP, _U8P, C.c_uint, C.c_int, _VP], C.c_int),
+    "zkp_g1_ntt": ([_VP, _U8P, C.c_uint, C.c_int], C.c_int),
+    "zkp_g1_bases_lagrange": ([_VP, C.c_uint, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_opener_create": ([_VP, C.c_uint, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_opener_destroy": ([_VP], None),
+    "zkp_kzg_open_all": ([_VP, _VP, _SZ, _VP, _U8P, _VP], C.c_int),
+    "zkp_kzg_open_all_dev": ([_VP, _VP, _SZ, _VP, _U8P, _VP, _VP], C.c_int),
     "zkp_msm_g1": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1_batch_dev": ([_VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
@@ -361,6 +369,13 @@ class G1Bases:
         v = _G1Validation()
         _chk(lib().zkp_g1_bases_validate(self._h, _ptr(status), C.byref(v)))
         return (_validation_dict(v), status) if want_status else _validation_dict(v)
+
+    def lagrange(self, log_n):
+        """zkp_g1_bases_lagrange: the inverse point transform of the first 2^log_n points as a new handle -- [L_i(s)]G for an SRS
+        [s^i]G, so that kzg_commit(lagrange, evals) commits to the interpolant of evals on the domain."""
+        h = C.c_void_p()
+        _chk(lib().zkp_g1_bases_lagrange(self._h, log_n, C.byref(h)))
+        return G1Bases(h)
 
     def shards(self):
         """[(slot, hip_device, offset, length)] of the chunks of this handle (one entry for a single-slot handle)."""
@@ -852,6 +867,62 @@ def kzg_open(srs, coeffs, z):
     return (out, int(inf.value)), ev
 
 
+# ----------------------------------------------------------------------------- transform over G1 points, all openings at once
+def g1_scale_dev(xy_tensor, scalars_tensor, n, is_inf_tensor=None, stream=None):
+    """zkp_g1_scale_dev: P_i <- [k_i] P_i in place over n x 12 limbs and n x 4 scalar limbs resident on the device."""
+    inf = _dev_ptr(is_inf_tensor, n) if is_inf_tensor is not None else None
+    _chk(lib().zkp_g1_scale_dev(_dev_ptr(xy_tensor, 96 * n), inf, _dev_ptr(scalars_tensor, 32 * n), n, _stream_ptr(stream)))
+
+
+def g1_ntt_dev(xy_tensor, is_inf_tensor, log_n, inverse=False, stream=None):
+    """zkp_g1_ntt_dev: Y_i = sum_j [w^(ij)] P_j in place over 2^log_n points (x 12 limbs, and as many flag bytes) on the device."""
+    n = 1 << log_n
+    _chk(lib().zkp_g1_ntt_dev(_dev_ptr(xy_tensor, 96 * n), _dev_ptr(is_inf_tensor, n), log_n, 1 if inverse else 0, _stream_ptr(stream)))
+
+
+def g1_ntt(xy, is_inf=None, inverse=False):
+    """zkp_g1_ntt on host memory: (n, 12) limbs and optional (n,) flags -> (the transformed points, their flags), n a power of two."""
+    xy = _np(xy, np.uint64, (-1, 12)).copy()
+    inf = _np(is_inf, np.uint8).copy() if is_inf is not None else np.zeros(xy.shape[0], dtype=np.uint8)
+    _chk(lib().zkp_g1_ntt(_ptr(xy), _ptr(inf), _log2(xy.shape[0]), 1 if inverse else 0))
+    return xy, inf
+
+
+class KzgOpener:
+    """zkp_kzg_opener: all n = 2^log_n openings of a polynomial at the roots of unity in one call (Feist-Khovratovich)."""
+
+    def __init__(self, srs_bases, log_n):
+        self.log_n, self.n = log_n, 1 << log_n
+        self._h = C.c_void_p()
+        _chk(lib().zkp_kzg_opener_create(srs_bases._h, log_n, C.byref(self._h)))
+
+    def open_all(self, coeffs, want_evals=True):
+        """-> ((n, 12) proof points, (n,) flags), (n, 4) evaluations f(w^m) (None without want_evals); proof m is kzg_open at w^m."""
+        coeffs = _np(coeffs, np.uint64, (-1, 4))
+        xy = np.zeros((self.n, 12), dtype=np.uint64)
+        inf = np.zeros(self.n, dtype=np.uint8)
+        ev = np.zeros((self.n, 4), dtype=np.uint64) if want_evals else None
+        _chk(lib().zkp_kzg_open_all(self._h, _ptr(coeffs), coeffs.shape[0], _ptr(xy), _ptr(inf), _ptr(ev)))
+        return (xy, inf), ev
+
+    def open_all_dev(self, coeffs_tensor, length, out_xy_tensor, out_inf_tensor, out_evals_tensor=None, stream=None):
+        """The same with everything resident on the opener's device; nothing is synchronised."""
+        ev = _dev_ptr(out_evals_tensor, 32 * self.n) if out_evals_tensor is not None else None
+        _chk(lib().zkp_kzg_open_all_dev(self._h, _dev_ptr(coeffs_tensor, 32 * length), length, _dev_ptr(out_xy_tensor, 96 * self.n),
+                                        _dev_ptr(out_inf_tensor, self.n), ev, _stream_ptr(stream)))
+
+    def close(self):
+        if self._h:
+            lib().zkp_kzg_opener_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Srs:
     """kzg/src/srs.rs: g1_points = [s^i]G for i < circuit_size + 3, generated on the GPU and kept resident."""
 
@@ -872,6 +943,7 @@ class KzgScheme:
 
     def __init__(self, srs, expand_bases=True):  # scheme.rs:34
         self.srs = srs
+        self._openers = {}  # log_n -> KzgOpener (open_all), released by close()
         if expand_bases:  # the SRS is fixed for the life of the scheme: pay the one-off expansion here
             srs.bases.precompute(0)
 
@@ -887,6 +959,24 @@ class KzgScheme:
         return kzg_open(self.srs.bases, coeffs, z)
 
     open_vector = open
+
+    def open_all(self, coeffs, log_n):
+        """Every opening of `coeffs` on the domain of 2^log_n roots of unity: KzgOpener.open_all (the opener is kept per log_n)."""
+        if log_n not in self._openers:
+            self._openers[log_n] = KzgOpener(self.srs.bases, log_n)
+        return self._openers[log_n].open_all(coeffs)
+
+    def close(self):
+        """Release the device memory of the openers open_all made (about 1.4 KB per point of each domain); the SRS stays."""
+        for op in self._openers.values():
+            op.close()
+        self._openers = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ----------------------------------------------------------------------------- PLONK prover rounds (plonk/src/prover.rs)
