@@ -45,7 +45,12 @@ template <> struct NttOps<Fr> : NttFrConsts {
     static ZKP_DEV E fix(const E& x) { return normalise(x); }
     // (u, v) -> (u + v, u - v) with no product, for the stage-1 butterflies of a tile's first round whose twiddle is 1: u and v are
     // stage-0 sums (< 4r, limbs < 2^30); v is carry-propagated so that the 8r constant dominates it.  Results < 8r and < 12r: the
-    // later stages add at most 4r each, 12r + 9 * 4r = 48r < 70r for the largest tile (2^11).
+    // later stages add at most 4r each, 12r + 9 * 4r = 48r < 70r for the largest tile (2^11).  That is from tight inputs (a later pass,
+    // a coset pre-scale); canonical inputs (pass 0, a single pass) stay 2r lower.  Canonical / tight per radix, the wide passes included:
+    // 2^8: 34r / 36r, 2^9: 38r / 40r, 2^10: 42r / 44r, 2^11: 46r / 48r.  What reads the finished tile multiplies by a factor below
+    // 1.015r -- a table entry (< r) or powtab_get's product of two (< r / 70.66 + r), not the 2r of a tight value -- so the value
+    // product stays below 48r * 1.015r < 70 r^2, its result is tight (< 2r < 2^256: store_tight), and store finds a top limb below
+    // 2^29.  tests/model/ntt_fr_model.py derives these figures (walk, check_consumers) and drives the kernels to within 2r of them.
     static constexpr int UNIT_Q_MAX = 1;  // (profiles/r02_m: 2-4.5 % of a transform)
     static ZKP_DEV void unit_butterfly(E& u, E& v) {
         const E t = normalise(v);
