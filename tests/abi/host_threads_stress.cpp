@@ -5,6 +5,10 @@
 //             throws, one uploader per slot from concurrent caller threads
 //   RangeUpload: the guard of an uploader job -- released normally, released with an error, and a submitter that leaves its scope by
 //             return or by throw before it releases the job: the guard must cancel and join it
+//   DeviceWorkers: run() with 1 to 8 jobs (job i on thread i) over many rounds, from several caller threads (serialised inside), and again
+//             after stop() has joined the threads
+//   PhaseBarrier: the jobs of one run() meet at it generation after generation; one of them arrives with `false`, after which every
+//             participant must leave with `false` at that same barrier (and at every later one)
 #include <cstdio>
 #include <cstdlib>
 #include "host_threads.hpp"
@@ -115,6 +119,68 @@ int main() {
         std::atomic<int> done{0};
         uploader(2).submit([&]() -> int { done.store(1, std::memory_order_release); return ZKP_HOST_THREADS_OK; });
         if (uploader(2).wait() != ZKP_HOST_THREADS_OK || done.load(std::memory_order_acquire) != 1) bad++;
+    }
+    // ---- DeviceWorkers
+    {
+        DeviceWorkers workers;
+        auto rounds = [&](int count, std::atomic<int>& errs) {
+            for (int round = 0; round < count; round++) {
+                const size_t n = 1 + (size_t)(round % 8);
+                std::vector<long> out(n, 0);
+                std::vector<std::function<void()>> jobs(n);
+                for (size_t i = 0; i < n; i++) jobs[i] = [&out, i, round] { out[i] = (long)(i + 1) * (round + 1); };
+                workers.run(jobs);
+                for (size_t i = 0; i < n; i++)
+                    if (out[i] != (long)(i + 1) * (round + 1)) errs++;
+            }
+        };
+        std::atomic<int> errs{0};
+        rounds(400, errs);
+        {
+            std::vector<std::thread> callers;
+            for (int t = 0; t < 4; t++) callers.emplace_back([&] { rounds(100, errs); });
+            for (auto& c : callers) c.join();
+        }
+        workers.stop();
+        rounds(50, errs);  // the threads come back
+        workers.stop();
+        workers.stop();    // nothing left to join
+        // ---- PhaseBarrier, on the workers as ntt_sharded.inc uses it
+        for (int round = 0; round < 100; round++) {
+            const size_t n = 2 + (size_t)(round % 7);
+            const int generations = 6, bad_gen = round % generations;
+            const size_t bad_one = (size_t)round % n;
+            PhaseBarrier bar;
+            bar.n = n;
+            std::vector<int> left_at(n, -1);  // the barrier at which participant i was told `false`
+            std::vector<long> seen(n, 0);
+            std::vector<long> shared(n, 0);   // written before a barrier, read by the neighbour behind it
+            std::vector<std::function<void()>> jobs(n);
+            for (size_t i = 0; i < n; i++)
+                jobs[i] = [&, i] {
+                    for (int gen = 0; gen < generations; gen++) {
+                        shared[i] = 1000L * gen + (long)i;
+                        if (!bar.arrive(!(gen == bad_gen && i == bad_one))) {
+                            left_at[i] = gen;
+                            return;
+                        }
+                        seen[i] += shared[(i + 1) % n];
+                        if (!bar.arrive(true)) {  // (nobody writes `shared` again before everybody has read it)
+                            left_at[i] = -2;
+                            return;
+                        }
+                    }
+                };
+            workers.run(jobs);
+            long want = 0;
+            for (int gen = 0; gen < bad_gen; gen++) want += 1000L * gen;
+            for (size_t i = 0; i < n; i++)
+                if (left_at[i] != bad_gen || seen[i] != want + (long)bad_gen * (long)((i + 1) % n)) errs++;
+            bar.n = 1;  // a lone arrival: the verdict stays false
+            if (bar.arrive(true)) errs++;
+        }
+        workers.stop();
+        bad += errs.load();
     }
     std::printf("host threads stress: %d failures\n", bad);
     return bad ? 1 : 0;

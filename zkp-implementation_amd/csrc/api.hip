@@ -89,77 +89,34 @@ int hip_fail(hipError_t e, const std::string& what) {
         if (r_ != ZKP_OK) return r_; \
     } while (0)
 
-#include "host_threads.hpp"  // HostPool (host_pool()), Uploader (uploader(slot))
+#include "host_threads.hpp"  // HostPool (host_pool()), Uploader (uploader(slot)), DeviceWorkers, PhaseBarrier
 #include "dev_res.hpp"       // DevBuf, TypedBuf, PinnedBuf, Stream, Event
 static_assert(ZKP_HOST_THREADS_E_DEVICE == ZKP_E_DEVICE && ZKP_HOST_THREADS_OK == ZKP_OK, "host_threads.hpp error codes");
 
-// ----------------------------------------------------------------------------------------------------
-// One resident host thread per device slot for the multi-device entries (zkp_init_devices): job i of a batch runs on thread i,
-// enters its slot's context there and launches on that slot's stream, so the per-device pieces of one call (the chunk MSMs
-// over sharded bases, the per-chunk SRS expansion) run concurrently.  Threads are created on first use and joined by
-// zkp_shutdown.  A job reports through its own (rc, message) pair: the thread-local error string of a worker is not the
-// caller's.
-// ----------------------------------------------------------------------------------------------------
-class DeviceWorkers {
-    struct W {
-        std::thread th;
-        std::mutex mu;
-        std::condition_variable cv;
-        const std::function<void()>* job = nullptr;
-        bool busy = false, quit = false;
-    };
-    std::mutex run_mu;
-    std::vector<W*> ws;
-    static void loop(W* w) {
-        std::unique_lock<std::mutex> lk(w->mu);
-        for (;;) {
-            w->cv.wait(lk, [&] { return w->job != nullptr || w->quit; });
-            if (w->quit) return;
-            const std::function<void()>* j = w->job;
-            lk.unlock();
-            (*j)();
-            lk.lock();
-            w->job = nullptr;
-            w->busy = false;
-            w->cv.notify_all();
-        }
-    }
-
-public:
-    void run(const std::vector<std::function<void()>>& jobs) {
-        std::lock_guard<std::mutex> one(run_mu);
-        while (ws.size() < jobs.size()) {
-            W* w = new W;
-            w->th = std::thread(loop, w);
-            ws.push_back(w);
-        }
-        for (size_t i = 0; i < jobs.size(); i++) {
-            std::lock_guard<std::mutex> lk(ws[i]->mu);
-            ws[i]->job = &jobs[i];
-            ws[i]->busy = true;
-            ws[i]->cv.notify_all();
-        }
-        for (size_t i = 0; i < jobs.size(); i++) {
-            std::unique_lock<std::mutex> lk(ws[i]->mu);
-            ws[i]->cv.wait(lk, [&] { return !ws[i]->busy; });
-        }
-    }
-    void stop() {
-        std::lock_guard<std::mutex> one(run_mu);
-        for (W* w : ws) {
-            {
-                std::lock_guard<std::mutex> lk(w->mu);
-                w->quit = true;
-                w->cv.notify_all();
-            }
-            w->th.join();
-            delete w;
-        }
-        ws.clear();
-    }
-};
-DeviceWorkers g_workers;
+DeviceWorkers g_workers;  // joined by zkp_shutdown
 void device_workers_stop() { g_workers.stop(); }
+
+// Run fn(i) for i < k on the per-slot workers (job i on thread i).  A job reports through its own (code, message) pair: the thread-local
+// error string of a worker is not the caller's.  Which failure the caller reports is the caller's rule.
+struct SlotResults {
+    std::vector<int> rc;
+    std::vector<std::string> msg;
+};
+SlotResults run_on_slots(size_t k, const std::function<int(size_t)>& fn) {
+    SlotResults r{std::vector<int>(k, ZKP_OK), std::vector<std::string>(k)};
+    std::vector<std::function<void()>> jobs(k);
+    for (size_t i = 0; i < k; i++)
+        jobs[i] = [&, i] {
+            try {
+                r.rc[i] = fn(i);
+            } catch (...) {
+                r.rc[i] = on_exception();
+            }
+            if (r.rc[i] != ZKP_OK) r.msg[i] = g_err;
+        };
+    g_workers.run(jobs);
+    return r;
+}
 
 // ----------------------------------------------------------------------------------------------------
 // optional per-phase timing: HIP events on the launch stream (zkp_profile_* in include/zkp_hip.h)
@@ -725,22 +682,10 @@ int bases_create_single(int slot, const uint64_t* xy, const uint8_t* is_inf, siz
 // Run fn(i) for every chunk of a sharded handle on the per-slot workers; the first failure (code + message) is the caller's.
 int for_each_shard(const zkp_bases* b, const std::function<int(size_t)>& fn) {
     const size_t k = b->shards.size();
-    std::vector<int> rc(k, ZKP_OK);
-    std::vector<std::string> msg(k);
-    std::vector<std::function<void()>> jobs(k);
+    const SlotResults r = run_on_slots(k, fn);
     for (size_t i = 0; i < k; i++)
-        jobs[i] = [&, i] {
-            try {
-                rc[i] = fn(i);
-            } catch (...) {
-                rc[i] = on_exception();
-            }
-            if (rc[i] != ZKP_OK) msg[i] = g_err;
-        };
-    g_workers.run(jobs);
-    for (size_t i = 0; i < k; i++)
-        if (rc[i] != ZKP_OK)  // (while a sharded handle is being created its chunk i is slot i and may still be null)
-            return fail(rc[i], "device slot " + std::to_string(b->shards[i] ? b->shards[i]->slot : (int)i) + ": " + msg[i]);
+        if (r.rc[i] != ZKP_OK)  // (while a sharded handle is being created its chunk i is slot i and may still be null)
+            return fail(r.rc[i], "device slot " + std::to_string(b->shards[i] ? b->shards[i]->slot : (int)i) + ": " + r.msg[i]);
     return ZKP_OK;
 }
 

@@ -1,5 +1,6 @@
 // Host-side thread helpers of the library (pure C++17, no HIP): the resident pool for the serial tails of MSM batches, the uploader
-// thread of host-fed MSMs and the caller's guard of an uploader job.  In a header of their own so that tests/abi/host_threads_stress.cpp
+// thread of host-fed MSMs and the caller's guard of an uploader job, the per-slot workers of the multi-device entries and the barrier
+// their jobs meet at.  In a header of their own so that tests/abi/host_threads_stress.cpp
 // can run them under ThreadSanitizer (tests/test_host_threads_cpu.py); api.hip includes this file inside its anonymous namespace.
 #pragma once
 #include <atomic>
@@ -208,3 +209,94 @@ public:
     }
 };
 
+// ----------------------------------------------------------------------------------------------------
+// One resident host thread per device slot for the multi-device entries (zkp_init_devices): job i of a batch runs on thread i,
+// enters its slot's context there and launches on that slot's stream, so the per-device pieces of one call (the chunk MSMs
+// over sharded bases, the per-chunk SRS expansion, the slots of a sharded transform) run concurrently.  Threads are created on first
+// use and joined by stop() (zkp_shutdown); a run() after a stop() starts them again.
+// ----------------------------------------------------------------------------------------------------
+class DeviceWorkers {
+    struct W {
+        std::thread th;
+        std::mutex mu;
+        std::condition_variable cv;
+        const std::function<void()>* job = nullptr;
+        bool busy = false, quit = false;
+    };
+    std::mutex run_mu;
+    std::vector<W*> ws;
+    static void loop(W* w) {
+        std::unique_lock<std::mutex> lk(w->mu);
+        for (;;) {
+            w->cv.wait(lk, [&] { return w->job != nullptr || w->quit; });
+            if (w->quit) return;
+            const std::function<void()>* j = w->job;
+            lk.unlock();
+            (*j)();
+            lk.lock();
+            w->job = nullptr;
+            w->busy = false;
+            w->cv.notify_all();
+        }
+    }
+
+public:
+    void run(const std::vector<std::function<void()>>& jobs) {
+        std::lock_guard<std::mutex> one(run_mu);
+        while (ws.size() < jobs.size()) {
+            W* w = new W;
+            w->th = std::thread(loop, w);
+            ws.push_back(w);
+        }
+        for (size_t i = 0; i < jobs.size(); i++) {
+            std::lock_guard<std::mutex> lk(ws[i]->mu);
+            ws[i]->job = &jobs[i];
+            ws[i]->busy = true;
+            ws[i]->cv.notify_all();
+        }
+        for (size_t i = 0; i < jobs.size(); i++) {
+            std::unique_lock<std::mutex> lk(ws[i]->mu);
+            ws[i]->cv.wait(lk, [&] { return !ws[i]->busy; });
+        }
+    }
+    void stop() {
+        std::lock_guard<std::mutex> one(run_mu);
+        for (W* w : ws) {
+            {
+                std::lock_guard<std::mutex> lk(w->mu);
+                w->quit = true;
+                w->cv.notify_all();
+            }
+            w->th.join();
+            delete w;
+        }
+        ws.clear();
+    }
+};
+
+// Jobs that run side by side on the workers above meet here: every thread arrives with its own verdict and leaves with the
+// conjunction, so a slot that failed takes the others out of their protocol at the same barrier and nobody is left waiting for an
+// event that will never be recorded (ntt_sharded.inc).  Once false, the verdict stays false.  A waiter leaves with the verdict of ITS
+// barrier (`verdict`, fixed by the last arrival), not with `ok`: a fast thread may already have arrived at the next barrier with `false`,
+// and a waiter that read that would leave one barrier early while the fast thread waits for it at the next one for ever.
+struct PhaseBarrier {
+    std::mutex mu;
+    std::condition_variable cv;
+    size_t n = 1, arrived = 0;
+    uint64_t gen = 0;
+    bool ok = true, verdict = true;
+    bool arrive(bool mine) {
+        std::unique_lock<std::mutex> lk(mu);
+        ok = ok && mine;
+        if (++arrived == n) {
+            arrived = 0;
+            verdict = ok;
+            gen++;
+            cv.notify_all();
+        } else {
+            const uint64_t g0 = gen;
+            cv.wait(lk, [&] { return gen != g0; });  // (the next barrier cannot complete, and overwrite `verdict`, before this thread arrives at it)
+        }
+        return verdict;
+    }
+};

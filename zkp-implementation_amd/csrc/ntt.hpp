@@ -211,20 +211,7 @@ ZKP_DEV void ntt_tile(typename NttOps<F>::E* tile, const typename NttOps<F>::W* 
     if (log_r - s_lo == 1) ntt_round<F, 1, false>(tile, tw, log_r, s_lo, t_log, stride, tid);
 }
 
-// Gathered input layout (first pass of a transform only): logical element e of transform b lives at physical element
-//   b * batch_stride + (e mod 2^lo_bits) + ((e >> lo_bits) mod 2^mid_bits) * mid_stride + (e >> (lo_bits + mid_bits)) * hi_stride.
-// This is how the row transforms of the multi-GPU four-step NTT read what the all-to-all delivered -- [source rank][my row]
-// [that rank's columns] blocks, possibly in several column chunks -- without a transpose pass (zkp_hip/dist.py).
-struct NttRemap {
-    uint32_t on;  // 0: contiguous transforms, element e of transform b at b * n + e
-    uint32_t lo_bits, mid_bits;
-    uint64_t mid_stride, hi_stride, batch_stride;
-};
-ZKP_DEV uint64_t ntt_phys(const NttRemap& r, uint64_t b, uint64_t n, uint64_t e) {
-    if (!r.on) return b * n + e;
-    const uint64_t lo = e & ((1ull << r.lo_bits) - 1), rest = e >> r.lo_bits;
-    return b * r.batch_stride + lo + (rest & ((1ull << r.mid_bits) - 1)) * r.mid_stride + (rest >> r.mid_bits) * r.hi_stride;
-}
+// (NttRemap and ntt_phys, the gathered / scattered layout of a transform's first load and last store: ntt_plan.hpp)
 
 template <class F>
 struct NttStridedParams {
@@ -428,28 +415,15 @@ __global__ void twiddle_rows_kernel(F* data, uint64_t rows, uint64_t cols, uint6
     data[i] = O::store(x);
 }
 
-// Index permutation of 32-byte elements between two strided views of up to four power-of-two dimensions (most significant
-// first): element (i0, i1, i2, i3) moves from in[sum i_k in_stride_k] to out[sum i_k out_stride_k].  The copies of the in-process
-// multi-GPU transform (csrc/ntt_sharded.inc): packing a slab into per-peer blocks, unpacking what the peers delivered, and the
-// transposition behind a natural-order output.  Two lanes per element (16 bytes each), consecutive lanes on consecutive elements
+// Index permutation of 32-byte elements between two strided views (PermuteSpec and permute_index: ntt_plan.hpp).  The copies of the
+// in-process multi-GPU transform (csrc/ntt_sharded.inc): packing a slab into per-peer blocks, unpacking what the peers delivered, and
+// the transposition behind a natural-order output.  Two lanes per element (16 bytes each), consecutive lanes on consecutive elements
 // of the innermost dimension: whichever side has stride 1 there moves whole cache lines, the other whole 32-byte sectors.
-struct PermuteSpec {
-    uint32_t bits[4];
-    uint64_t in_stride[4], out_stride[4];  // in elements
-};
 __global__ void fr_permute_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, PermuteSpec s, uint64_t total) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t e = t >> 1;
-    if (e >= total) return;
-    uint64_t src = 0, dst = 0;
-#pragma unroll
-    for (int d = 3; d >= 0; d--) {
-        const uint64_t i = e & ((1ull << s.bits[d]) - 1);
-        e >>= s.bits[d];
-        src += i * s.in_stride[d];
-        dst += i * s.out_stride[d];
-    }
-    out[2 * dst + (t & 1)] = in[2 * src + (t & 1)];
+    if ((t >> 1) >= total) return;
+    const PermuteIndex x = permute_index(s, t >> 1);
+    out[2 * x.dst + (t & 1)] = in[2 * x.src + (t & 1)];
 }
 
 // data[i] *= c * base^(idx0 + i): the coset scaling of a slab of a distributed vector (pre-scaling of coset_fft, post-scaling of

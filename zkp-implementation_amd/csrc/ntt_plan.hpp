@@ -1,12 +1,20 @@
 // ntt_plan.hpp -- the shape of a transform (ntt_host.inc): the per-field constants of the pass kernels (NttOps<F> inherits them), how
 // many passes of which radix, the geometry of every launch and the tables it reads.  Pure arithmetic on (field, log_n, allow_wide, knob
-// values): plain C++17 without HIP and without the environment, so that tests/host/ntt_plan_table.cpp checks it with g++ alone.
+// values): plain C++17 without HIP and without the environment, so that tests/host/ntt_plan_table.cpp checks it with g++ alone.  Also
+// the two index maps that the kernels of ntt.hpp share with the plan of the sharded transform (ntt_shard_plan.hpp): NttRemap and
+// PermuteSpec; under hipcc (ff.hpp included first) the kernels call the same functions.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 
 namespace zkp {
+
+#ifdef ZKP_HD
+#define ZKP_NTTPLAN_FN ZKP_HD
+#else
+#define ZKP_NTTPLAN_FN inline
+#endif
 
 #ifndef ZKP_GL_LOG_T
 #define ZKP_GL_LOG_T 4
@@ -149,6 +157,41 @@ NttAxis0Shape plan_ntt_axis0(unsigned log_len, size_t cols) {
 // exponent (first + count - 1) * (2^log_len - 1) must stay below 2^tw_log_n.  tw_log_n == 0: no twiddle.
 inline bool four_step_exponent_ok(unsigned tw_log_n, uint64_t first, uint64_t count, unsigned log_len) {
     return tw_log_n <= 32 && (tw_log_n == 0 || (((first + count - 1) * ((1ull << log_len) - 1)) >> tw_log_n) == 0);
+}
+
+// Gathered input layout (first pass of a transform only): logical element e of transform b lives at physical element
+//   b * batch_stride + (e mod 2^lo_bits) + ((e >> lo_bits) mod 2^mid_bits) * mid_stride + (e >> (lo_bits + mid_bits)) * hi_stride.
+// This is how the row transforms of the multi-GPU four-step NTT read what the all-to-all delivered -- [source rank][my row]
+// [that rank's columns] blocks, possibly in several column chunks -- without a transpose pass (zkp_hip/dist.py).
+struct NttRemap {
+    uint32_t on;  // 0: contiguous transforms, element e of transform b at b * n + e
+    uint32_t lo_bits, mid_bits;
+    uint64_t mid_stride, hi_stride, batch_stride;
+};
+ZKP_NTTPLAN_FN uint64_t ntt_phys(const NttRemap& r, uint64_t b, uint64_t n, uint64_t e) {
+    if (!r.on) return b * n + e;
+    const uint64_t lo = e & ((1ull << r.lo_bits) - 1), rest = e >> r.lo_bits;
+    return b * r.batch_stride + lo + (rest & ((1ull << r.mid_bits) - 1)) * r.mid_stride + (rest >> r.mid_bits) * r.hi_stride;
+}
+
+// Index permutation of 32-byte elements between two strided views of up to four power-of-two dimensions (most significant
+// first): element (i0, i1, i2, i3) moves from in[sum i_k in_stride_k] to out[sum i_k out_stride_k] (fr_permute_kernel, ntt.hpp)
+struct PermuteSpec {
+    uint32_t bits[4];
+    uint64_t in_stride[4], out_stride[4];  // in elements
+};
+struct PermuteIndex {
+    uint64_t src, dst;
+};
+ZKP_NTTPLAN_FN PermuteIndex permute_index(const PermuteSpec& s, uint64_t e) {  // e < 2^(bits[0] + .. + bits[3])
+    PermuteIndex x = {0, 0};
+    for (int d = 3; d >= 0; d--) {
+        const uint64_t i = e & ((1ull << s.bits[d]) - 1);
+        e >>= s.bits[d];
+        x.src += i * s.in_stride[d];
+        x.dst += i * s.out_stride[d];
+    }
+    return x;
 }
 
 }  // namespace zkp
