@@ -37,7 +37,9 @@
  * ZKP_PYR_TAIL_THREADS / ZKP_PYR_TAIL_BLOCKS / ZKP_PYR_TAIL_HALF (geometry of the launch that runs the last levels of the bucket reduction:
  * workgroup size 64..512, workgroups per bucket set 1..256, pairs per array from which it takes over; defaults 256 / 16 / 64; tuning aids),
  * ZKP_FRI_FR_TAIL_LOG (0..10: log2 of the largest layer zkp_fri_prove_fr runs in its one-workgroup tail kernel, default 9, 0 = none;
- * tuning aid).
+ * tuning aid), ZKP_KZG_COSET_GROUP_LOG (0..3: log2 of the terms one lane of a coset opener's multiply-accumulate pass sums, read by
+ * zkp_kzg_opener_create_cosets, default 0; tuning aid), ZKP_KZG_OPENER_MAX_BYTES (zkp_kzg_opener_create_cosets refuses, with
+ * ZKP_E_NOMEM and the sizes in zkp_last_error(), an opener that needs more device memory than this many bytes).
  */
 #ifndef ZKP_HIP_H
 #define ZKP_HIP_H
@@ -292,6 +294,37 @@ int zkp_kzg_open_all(const zkp_kzg_opener *o, const uint64_t *coeffs, size_t len
  * the workspaces, and zkp_kzg_opener_create has already built the plans and tables of the two Fr transforms a call runs. */
 int zkp_kzg_open_all_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_t len, void *d_out_xy, uint8_t *d_out_is_inf,
                          void *d_out_evals, void *stream);
+/* Coset openings: the n / l multi-point proofs of one polynomial, one per coset of l = 2^log_l points of the domain (the "cells" of
+ * data-availability sampling).  With r = n / l and w the root zkp_ntt_fr uses for log_n, coset k < r is {w^(k + j r) : j < l}, the
+ * roots of X^l - x_k^l for x_k = w^k, and
+ *   out point k = [q_k(s)]G, q_k the quotient of f by X^l - x_k^l,
+ * from the multi-point form of the same algorithm: per slice b < l of the SRS a transform of 2r points (kept by the opener), per
+ * call one batched Fr transform of l rows of 2r, a multiply-accumulate pass over the 2n products (one joint double-and-add per
+ * group of terms, then a pairwise fold), and point transforms of 2r and r only.  zkp_kzg_opener_create_cosets returns the same
+ * opaque type as zkp_kzg_opener_create: it holds the l transformed slices (256 B x 2n in all) and the workspaces, and has built
+ * every plan and table a call uses.  1 <= log_n - log_l and log_n <= 23, else ZKP_E_ARG; the source needs n - l points
+ * (ZKP_E_SIZE) on one device (sharded: ZKP_E_ARG); workspaces that do not fit -- more than the device has free, or more than
+ * ZKP_KZG_OPENER_MAX_BYTES -- are ZKP_E_NOMEM with the sizes in zkp_last_error() and nothing left allocated.  log_l = 0 is zkp_kzg_opener_create itself.
+ * zkp_kzg_open_cosets: out_xy r x 12 limbs, out_is_inf r bytes, out_evals n x 4 limbs or NULL -- f on the whole domain in natural
+ * order, so the values of coset k sit at k + j r.  len == 0 is ZKP_E_ARG, len > n ZKP_E_SIZE; len <= l gives r identities.  On an
+ * opener with log_l = 0 it returns what zkp_kzg_open_all returns; zkp_kzg_open_all* on an opener with log_l > 0 is ZKP_E_ARG.
+ * The device entry, like zkp_kzg_open_all_dev, neither allocates nor synchronises.
+ * ZKP_KZG_COSET_GROUP_LOG (0..3, read when an opener is created; tuning aid) sets how many terms a lane of the multiply-accumulate
+ * pass sums: profiles/kzg_open_cosets.md. */
+int zkp_kzg_opener_create_cosets(const zkp_bases *srs, unsigned log_n, unsigned log_l, zkp_kzg_opener **out);
+int zkp_kzg_open_cosets(const zkp_kzg_opener *o, const uint64_t *coeffs, size_t len, uint64_t *out_xy, uint8_t *out_is_inf,
+                        uint64_t *out_evals);
+int zkp_kzg_open_cosets_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_t len, void *d_out_xy, uint8_t *d_out_is_inf,
+                            void *d_out_evals, void *stream);
+/* host + one commitment on the GPU: the check of one coset proof.  evals[j] = f(x w_l^j) for j < l = 2^log_l, w_l the root of
+ * zkp_ntt_fr for log_l (for coset k of an opener: x = w^k, evals[j] = out_evals[k + j r]); g2_sl is [s^l]_2.  Accepts iff
+ *   e(W, [s^l]_2 - [x^l]_2) == e(C - [I(s)]_1, G_2),
+ * I the interpolant of the evaluations on the coset (its coefficients are computed on the host, [I(s)]_1 is zkp_kzg_commit over
+ * the first l points of `srs`).  The G2 point and both G1 points are validated as in zkp_kzg_verify (off the curve, outside the
+ * subgroup, limbs >= p: ZKP_E_ARG); fewer than l points in `srs` is ZKP_E_SIZE, x = 0 ZKP_E_ARG. */
+int zkp_kzg_verify_coset(const zkp_bases *srs, const uint64_t g2_sl_xy[24], const uint64_t commit_xy[12], uint8_t commit_is_inf,
+                         const uint64_t w_xy[12], uint8_t w_is_inf, const uint64_t x[4], unsigned log_l, const uint64_t *evals,
+                         int *accepted);
 
 /* ---- single scalar multiplication: KzgScheme::commit_para, kzg/src/scheme.rs:78-82 (`g1_0.mul(para)`),
  *      6x per proof at plonk/src/prover.rs:183-188.  Serial by nature: computed on the host. ---- */

@@ -4,8 +4,12 @@ warm-up of the same shape; the shader clock of the library's multiply-add probe 
   - zkp_g1_bases_lagrange at 2^16 / 2^20
   - zkp_kzg_opener_create and zkp_kzg_open_all_dev at n = 2^10 / 2^12 / 2^14 / 2^16, next to what the library offered for the same
     result before: zkp_kzg_open, 64 calls at the same length, the time per call MULTIPLIED BY n (labelled as such: an extrapolation)
-Prints markdown tables (profiles/g1_ntt.md).
-python tools/g1_ntt_bench.py [--ntt 12,16,20] [--lagrange 16,20] [--open 10,12,14,16]   (an empty list skips a part)"""
+  - zkp_kzg_open_cosets_dev at (log_n, log_l) = (12,6) / (13,6) / (16,6) / (20,6) for every group size B = 1, 2, 4, 8 of the
+    multiply-accumulate pass (ZKP_KZG_COSET_GROUP_LOG, set around the creation of each opener), with the spread (max - min) / median
+    of the three timed calls, the creation time of each opener, and zkp_kzg_open_all_dev at the same n in the same process
+Prints markdown tables (profiles/g1_ntt.md, profiles/kzg_open_cosets.md).
+python tools/g1_ntt_bench.py [--ntt 12,16,20] [--lagrange 16,20] [--open 10,12,14,16] [--cosets 12:6,13:6,16:6,20:6]
+(an empty list skips a part)"""
 import argparse
 import os
 import statistics
@@ -24,6 +28,7 @@ import zkp_hip as zkp  # noqa: E402
 ap = argparse.ArgumentParser()
 for name, default in (("ntt", "12,16,20"), ("lagrange", "16,20"), ("open", "10,12,14,16")):
     ap.add_argument("--" + name, default=default)
+ap.add_argument("--cosets", default="12:6,13:6,16:6,20:6")
 args = ap.parse_args()
 sizes = lambda s: [int(x) for x in s.split(",") if x]
 
@@ -32,8 +37,8 @@ dev = torch.device("cuda", 0)
 SECRET = bench.fr_mont([0x1F2E3D4C5B6A7988])[0]
 
 
-def event_ms(fn, reps=3):
-    """median device time of fn(), which enqueues on the current stream; one warm-up of the same shape first"""
+def event_times(fn, reps=3):
+    """device times of `reps` calls of fn(), which enqueues on the current stream; one warm-up of the same shape first"""
     fn()
     torch.cuda.synchronize()
     out = []
@@ -44,7 +49,12 @@ def event_ms(fn, reps=3):
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b))
-    return statistics.median(out)
+    return out
+
+
+def event_ms(fn, reps=3):
+    """their median"""
+    return statistics.median(event_times(fn, reps))
 
 
 def host_ms(fn, reps=3):
@@ -116,6 +126,41 @@ if sizes(args.open):
         t_one = statistics.median(one)
         print(f"| 2^{ln} | {t_create:.1f} ms | {t_all:.1f} ms | {t_one:.3f} ms | {t_one * n / 1e3:.2f} s | {t_all / (t_one * n):.3f} |", flush=True)
         op.close()
+        srs.close()
+
+if args.cosets:
+    KNOB = "ZKP_KZG_COSET_GROUP_LOG"
+    print("\n| log_n | log_l | B | zkp_kzg_opener_create_cosets (one call) | zkp_kzg_open_cosets_dev, median of 3 | spread (max - min) / median | "
+          "against B = 1 | zkp_kzg_open_all_dev, same n | open_all / cosets |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for shape in args.cosets.split(","):
+        ln, ll = (int(x) for x in shape.split(":"))
+        n, r = 1 << ln, 1 << (ln - ll)
+        srs = zkp.G1Bases.from_host(zkp.srs_g1(SECRET, n))
+        coeffs = bench.rand_fr_tensor(torch, n, 4, dev)
+        out_ev = torch.zeros(n * 4, dtype=torch.int64, device=dev)
+        plain = zkp.KzgOpener(srs, ln)
+        all_xy = torch.zeros(n * 12, dtype=torch.int64, device=dev)
+        all_inf = torch.zeros(n, dtype=torch.uint8, device=dev)
+        t_all = event_ms(lambda: plain.open_all_dev(coeffs, n, all_xy, all_inf, out_ev))
+        plain.close()
+        del all_xy, all_inf
+        out_xy = torch.zeros(r * 12, dtype=torch.int64, device=dev)
+        out_inf = torch.zeros(r, dtype=torch.uint8, device=dev)
+        base = None
+        for group_log in range(4):
+            os.environ[KNOB] = str(group_log)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            op = zkp.KzgOpener(srs, ln, ll)
+            t_create = (time.perf_counter() - t0) * 1e3
+            del os.environ[KNOB]
+            ts = event_times(lambda: op.open_cosets_dev(coeffs, n, out_xy, out_inf, out_ev))
+            med = statistics.median(ts)
+            base = med if base is None else base
+            print(f"| {ln} | {ll} | {1 << group_log} | {t_create:.1f} ms | {med:.2f} ms | {(max(ts) - min(ts)) / med * 100:.1f} % | "
+                  f"{med / base:.3f} | {t_all:.1f} ms | {t_all / med:.1f} |", flush=True)
+            op.close()
         srs.close()
 
 print(f"\nshader clock of the multiply-add probe after: {clock()}")

@@ -9,6 +9,12 @@
 //   g1_ntt_mul_kernel         one lane per point: P_i <- [c k_i] P_i (the pointwise step, zkp_g1_scale_dev, the n^-1 of an inverse)
 //   g1_ntt_slice_kernel       a run of points of one workspace into another, identities behind it
 //   g1_ntt_store_kernel<RAW>  the workspace -> affine, one safegcd inversion per lane
+// and for the coset openings (zkp_kzg_open_cosets), at the end of this file:
+//   g1_ntt_load_slices_kernel the points of a handle -> the l slices of an opener, each bit-reversed
+//   g1_ntt_gather_kernel      the strided coefficients -> the l rows of scalars
+//   g1_ntt_split_kernel       every transformed scalar, times (2r)^-1, -> its two endomorphism halves
+//   g1_ntt_mac_kernel         one lane per output and group of terms: sum_j [k_j] P_j by one joint double-and-add
+//   g1_ntt_fold_kernel        the groups' partial sums of an output, pairwise
 //
 // [k]P for a variable P (g1_28_mul_glv): k = k1 + lambda k2 (glv_split, both halves below 2^128), then ONE joint MSB-first
 // double-and-add over {P, phi(P), P + phi(P)}: 128 doublings and ~96 additions instead of 255 and ~128.  The table does not fit the
@@ -121,12 +127,16 @@ __global__ __launch_bounds__(MSM_THREADS) void g1_ntt_load_kernel(const uint4* _
     p.store_s(ws + (map.rev_log ? g1_ntt_bitrev((uint32_t)i, map.rev_log) : i), cap);
 }
 
-// lanes [first, first + count) of stage `stage` of a transform of 2^log_n points; scaled: the last stage of an inverse
+// lanes [first, first + count) of stage `stage` of a transform of 2^log_n points; scaled: the last stage of an inverse.  Row y of the
+// grid runs the same lanes of the y-th of several vectors that lie 2^log_n points apart in one workspace (the slices of a coset
+// opener); its table entries follow those of row y - 1.
 __global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_butterfly_kernel(uint4* ws, uint64_t cap, uint32_t log_n, uint32_t stage,
                                                                           uint32_t first, uint32_t count, const Fr* __restrict__ row,
                                                                           uint32_t scaled, uint4* table, uint64_t tcap) {
     const uint32_t lane = blockIdx.x * G1_NTT_THREADS + threadIdx.x;
     if (lane >= count) return;
+    ws += (uint64_t)blockIdx.y << log_n;
+    table += (uint64_t)blockIdx.y * count;
     const G1NttButterfly bf = g1_ntt_butterfly(log_n, stage, first + lane);
     uint4* pa = ws + bf.lo;
     uint4* pb = ws + bf.hi;
@@ -202,6 +212,125 @@ __global__ __launch_bounds__(MSM_THREADS) void g1_ntt_store_kernel(const uint4* 
         r.store(out + i * 8);
     }
     if (out_inf) out_inf[i] = inf ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- coset openings
+// (zkp_kzg_open_cosets: g1_ntt_plan.hpp has the construction and every index below)
+
+// the l slices of a handle's points (128 bytes each, plane 0 of an expansion) into one workspace of 2n: slot i in [first, ...) is slot
+// j = i mod 2r of slice b = i / 2r (g1_coset_srs_map), stored bit-reversed within its slice
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_load_slices_kernel(const uint4* __restrict__ in, const uint8_t* __restrict__ is_inf,
+                                                                        uint32_t log_n, uint32_t log_l, uint64_t first, uint4* __restrict__ ws,
+                                                                        uint64_t cap) {
+    const uint64_t i = first + (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >> (log_n + 1)) return;
+    const uint32_t log_m = log_n - log_l + 1;
+    const uint64_t b = i >> log_m, j = i & (((uint64_t)1 << log_m) - 1);
+    const int64_t s = g1_ntt_load_source(g1_coset_srs_map(log_n, log_l, b), j);
+    X28 p = X28::infinity();
+    if (s >= 0 && !(is_inf && is_inf[s])) p = X28::from_affine(A28::load(in + (uint64_t)s * 8));
+    p.store_s(ws + (b << log_m) + g1_ntt_bitrev((uint32_t)j, log_m), cap);
+}
+
+// the l rows of g, 2r slots each, out of the strided coefficients: slot i of the 2n in [first, ...)
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_gather_kernel(const Fr* __restrict__ coeffs, uint64_t len, uint32_t log_n, uint32_t log_l,
+                                                                   uint64_t first, Fr* __restrict__ g) {
+    const uint64_t i = first + (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >> (log_n + 1)) return;
+    const uint32_t log_m = log_n - log_l + 1;
+    const int64_t s = g1_coset_coeff_source(log_n, log_l, len, i >> log_m, i & (((uint64_t)1 << log_m) - 1));
+    (s >= 0 ? Fr::load(coeffs + s) : Fr::zero()).store(g + i);
+}
+
+// g_i <- the halves of c g_i (glv_split), in place over the 32 bytes of the element: words 0..3 k1, words 4..7 k2
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_split_kernel(Fr* g, const Fr* __restrict__ factor, uint64_t first, uint64_t count) {
+    const uint64_t i = first + (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const Fr k = from_mont(Fr::load(g + i) * *factor);
+    const GlvHalves h = glv_split(k.l);
+    Fr o;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        o.l[w] = h.k1[w];
+        o.l[4 + w] = h.k2[w];
+    }
+    o.store(g + i);
+}
+
+// Lane `first + lane` of the multiply-accumulate pass: sum_{j < terms} [k_j] P_j over its group (g1_coset_mac_element), by ONE joint
+// MSB-first double-and-add -- 128 doublings for the whole group, and per bit and term one complete addition from {P_j, phi(P_j),
+// P_j + phi(P_j)} as in g1_28_mul_glv.  halves: what g1_ntt_split_kernel left, 8 words per element.  The lane keeps the current word
+// of every half in its column of `words` (indexed by j: registers cannot be), the rest stays in memory; P_j + phi(P_j) goes to entry
+// j * count + lane of the table, made by the loop's own addition in step -1.  Terms with a zero scalar or an identity point are
+// masked out before the loop.  The sum goes to dst[bitrev(k, rev_log)] when rev_log is given (one group per output), else to
+// dst[first + lane], the partial sums the fold takes.
+__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mac_kernel(const uint4* __restrict__ srs, uint64_t scap, const uint32_t* __restrict__ halves,
+                                                                    uint32_t log_m, uint32_t terms, uint64_t first, uint32_t count, uint4* dst,
+                                                                    uint64_t dcap, uint32_t rev_log, uint4* table, uint64_t tcap) {
+    __shared__ uint32_t words[2 << G1_COSET_MAX_GROUP_LOG][G1_NTT_THREADS];
+    const uint32_t lane = blockIdx.x * G1_NTT_THREADS + threadIdx.x;
+    if (lane >= count) return;
+    const uint64_t i = first + lane;
+    uint32_t live = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < terms; j++) {
+        const uint64_t e = g1_coset_mac_element(log_m, terms, i, j);
+        const uint4* kk = reinterpret_cast<const uint4*>(halves + 8 * e);
+        const uint4 a = kk[0], b = kk[1];
+        const bool zero = (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0;
+        if (!zero && !Fq28::load_s(srs + e + 8 * scap, scap).all_zero()) live |= 1u << j;
+    }
+    const Fq28 beta = G1Check28::beta();
+    X28 acc = X28::infinity();
+#pragma unroll 1
+    for (int s = -1; s < 128 && live; s++) {
+        if (s >= 0) {
+            if (!acc.is_inf()) acc = g1_28_double(acc);
+            if ((s & 31) == 0) {  // the next word of every half, most significant first
+                const uint32_t w = 3 - (s >> 5);
+#pragma unroll 1
+                for (uint32_t j = 0; j < terms; j++) {
+                    const uint32_t* kk = halves + 8 * g1_coset_mac_element(log_m, terms, i, j);
+                    words[2 * j][threadIdx.x] = kk[w];
+                    words[2 * j + 1][threadIdx.x] = kk[4 + w];
+                }
+            }
+        }
+        const uint32_t bit = 31 - (s & 31);
+#pragma unroll 1
+        for (uint32_t j = 0; j < terms; j++) {
+            if (!((live >> j) & 1)) continue;
+            const uint4* p = srs + g1_coset_mac_element(log_m, terms, i, j);
+            uint4* t = table + (uint64_t)j * count + lane;
+            uint32_t sel = 2;
+            if (s < 0) acc = X28::load_s(p, scap);  // the step that makes the third table entry: P + phi(P)
+            else sel = ((words[2 * j][threadIdx.x] >> bit) & 1) | (((words[2 * j + 1][threadIdx.x] >> bit) & 1) << 1);
+            if (sel) {
+                const bool third = sel == 3;
+                X28 q = X28::load_s(third ? t : p, third ? tcap : scap);
+                if (sel == 2) q.x = q.x * beta;
+                g1_28_add(acc, q);
+            }
+            if (s < 0) {
+                acc.store_s(t, tcap);
+                acc = X28::infinity();
+            }
+        }
+    }
+    acc.store_s(dst + (rev_log ? g1_ntt_bitrev((uint32_t)(i & (((uint64_t)1 << log_m) - 1)), rev_log) : i), dcap);
+}
+
+// One step of the fold (g1_coset_fold_step): partial i += partial i + half_lanes for lane i in [first, half_lanes); the last step
+// (rev_log given, half_lanes = 2r) writes the sum to dst[bitrev(i, rev_log)] instead
+__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_fold_kernel(uint4* part, uint64_t pcap, uint64_t half_lanes, uint64_t first, uint4* dst,
+                                                                     uint64_t dcap, uint32_t rev_log) {
+    const uint64_t i = first + (uint64_t)blockIdx.x * G1_NTT_THREADS + threadIdx.x;
+    if (i >= half_lanes) return;
+    X28 a = X28::load_s(part + i, pcap);
+    const X28 b = X28::load_s(part + i + half_lanes, pcap);
+    g1_28_add(a, b);
+    if (rev_log) a.store_s(dst + g1_ntt_bitrev((uint32_t)i, rev_log), dcap);
+    else a.store_s(part + i, pcap);
 }
 
 }  // namespace zkp

@@ -1,5 +1,6 @@
 // g1_ntt_host.inc -- zkp_g1_scale_dev, zkp_g1_ntt*, zkp_g1_bases_lagrange and the all-openings entries zkp_kzg_opener_* /
-// zkp_kzg_open_all* (included at the end of api.hip).  The kernels are in g1_ntt.hpp, every index and size in g1_ntt_plan.hpp.
+// zkp_kzg_open_all*, the coset openings zkp_kzg_opener_create_cosets / zkp_kzg_open_cosets* and their verifier zkp_kzg_verify_coset
+// (included at the end of api.hip, after verify_host.inc).  The kernels are in g1_ntt.hpp, every index and size in g1_ntt_plan.hpp.
 
 namespace {
 
@@ -102,23 +103,29 @@ int g1_ntt_mul(const uint4* src, uint64_t scap, const G1NttVec& v, unsigned rev_
 }
 
 // The stages over a vector loaded in bit-reversed order; natural order out.  scale: an inverse multiplies by n^-1 as well (without
-// it the caller has folded that factor in elsewhere).
-int g1_ntt_stages(const G1NttVec& v, unsigned log_n, int inverse, bool scale, hipStream_t st) {
+// it the caller has folded that factor in elsewhere).  slices > 1: as many vectors, 2^log_n points apart behind v.pts, stage by
+// stage together (unscaled only) -- a launch takes as many whole slices as G1_NTT_LAUNCH lanes and the table hold.  The kernel puts
+// the table entries of grid row y at y * count, count <= lanes: nothing but `together` * lanes <= v.tcap, computed here, keeps them
+// inside the table.
+int g1_ntt_stages(const G1NttVec& v, unsigned log_n, int inverse, bool scale, hipStream_t st, uint64_t slices = 1) {
     if (!log_n) return ZKP_OK;
     const Fr* row = nullptr;
     ZCHK(g1_ntt_twiddle_row(log_n, inverse, st, &row));
     const uint64_t lanes = (uint64_t)1 << (log_n - 1);
     scale = scale && inverse;
+    if (slices > 1 && scale) return fail(ZKP_E_ARG, "g1_ntt_stages: slices are transformed unscaled");
+    const uint64_t together = std::max<uint64_t>(1, std::min<uint64_t>({slices, std::min(G1_NTT_LAUNCH, v.tcap) / lanes, 65535}));
     for (unsigned s = 0; s < log_n; s++) {
         const bool last_scaled = scale && s == log_n - 1;
         if (last_scaled) ZCHK(g1_ntt_mul(v.pts, v.cap, v, 0, row + G1_NTT_TW_NINV, 0, nullptr, lanes, st));  // the left operands
-        for (uint64_t k = 0; k < g1_ntt_launches(lanes); k++) {
-            const uint64_t cnt = g1_ntt_launch_lanes(lanes, k);
-            hipLaunchKernelGGL(g1_ntt_butterfly_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, v.pts, v.cap,
-                               (uint32_t)log_n, (uint32_t)s, (uint32_t)(k * G1_NTT_LAUNCH), (uint32_t)cnt, row, last_scaled ? 1u : 0u,
-                               v.table, v.tcap);
-            HIPCHK(hipGetLastError());
-        }
+        for (uint64_t y = 0; y < slices; y += together)
+            for (uint64_t k = 0; k < g1_ntt_launches(lanes); k++) {
+                const uint64_t cnt = g1_ntt_launch_lanes(lanes, k);
+                hipLaunchKernelGGL(g1_ntt_butterfly_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS), (unsigned)std::min(together, slices - y)),
+                                   dim3(G1_NTT_THREADS), 0, st, v.pts + (y << log_n), v.cap, (uint32_t)log_n, (uint32_t)s,
+                                   (uint32_t)(k * G1_NTT_LAUNCH), (uint32_t)cnt, row, last_scaled ? 1u : 0u, v.table, v.tcap);
+                HIPCHK(hipGetLastError());
+            }
     }
     return ZKP_OK;
 }
@@ -139,9 +146,11 @@ const char* const kShardedG1Ntt = "bases are sharded over several devices: a tra
 
 struct zkp_kzg_opener {
     unsigned log_n = 0;
+    unsigned log_l = 0;      // > 0: made by zkp_kzg_opener_create_cosets, one proof per coset of 2^log_l points
+    unsigned group_log = 0;  // ... whose lanes sum 2^group_log terms (g1_coset_mac)
     int slot = 0, device = 0;
-    DevBuf srs_hat;  // NTT_2n of the reversed SRS points: depends on the SRS and n only
-    DevBuf work;     // u, the slice h, the scalars g and the lanes' table of one call (entries of a slot are serialised)
+    DevBuf srs_hat;  // NTT_2n of the reversed SRS points (cosets: the l transformed slices): depends on the SRS, n and l only
+    DevBuf work;     // (the partial sums,) u, the slice h, the scalars g and the lanes' table of one call (entries of a slot are serialised)
 };
 
 extern "C" {
@@ -314,10 +323,96 @@ int kzg_open_all_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t le
     return ZKP_OK;
 }
 
-int kzg_open_all_args(const zkp_kzg_opener* o, const void* coeffs, size_t len, const void* out_xy, const void* out_is_inf) {
+// (cosets: the call is one of zkp_kzg_open_cosets*, which take either kind of opener)
+int kzg_open_all_args(const zkp_kzg_opener* o, const void* coeffs, size_t len, const void* out_xy, const void* out_is_inf, bool cosets = false) {
     if (!o || !coeffs || !out_xy || !out_is_inf) return fail(ZKP_E_ARG, "null argument");
+    if (o->log_l && !cosets) return fail(ZKP_E_ARG, "the opener was made for cosets (zkp_kzg_opener_create_cosets): zkp_kzg_open_cosets opens with it");
     if (len == 0) return fail(ZKP_E_ARG, "open of an empty polynomial (kzg/src/scheme.rs:112 expects at least 1)");
     if (len > ((size_t)1 << o->log_n)) return fail(ZKP_E_SIZE, "more coefficients than the opener's domain has points");
+    return ZKP_OK;
+}
+
+// the l rows of g, each of 2^log_m scalars, transformed in place (a batched transform takes at most 65535 rows)
+int coset_fr_rows(Fr* g, unsigned log_m, uint64_t rows, hipStream_t st) {
+    const uint64_t step = 32768;
+    for (uint64_t first = 0; first < rows; first += step)
+        ZCHK(run_ntt<Fr>(g + (first << log_m), log_m, (size_t)std::min<uint64_t>(step, rows - first), 0, nullptr, st));
+    return ZKP_OK;
+}
+
+// where the pieces of a coset opener's `work` begin (g1_coset_sizes)
+struct CosetWork {
+    G1CosetSizes sz;
+    G1CosetMac mac;
+    uint4 *partial, *u, *h, *table;
+    Fr* g;
+    uint64_t tcap;
+};
+CosetWork coset_work(const zkp_kzg_opener* o) {
+    CosetWork w;
+    w.sz = g1_coset_sizes(o->log_n, o->log_l, o->group_log);
+    w.mac = g1_coset_mac(o->log_n, o->log_l, o->group_log);
+    char* base = static_cast<char*>(o->work.p);
+    w.partial = reinterpret_cast<uint4*>(base);
+    w.u = reinterpret_cast<uint4*>(base + w.sz.partial);
+    w.h = reinterpret_cast<uint4*>(base + w.sz.partial + w.sz.work);
+    w.g = reinterpret_cast<Fr*>(base + w.sz.partial + w.sz.work + w.sz.slice);
+    w.table = reinterpret_cast<uint4*>(base + w.sz.partial + w.sz.work + w.sz.slice + w.sz.scalars);
+    w.tcap = w.sz.table / G1_NTT_POINT_BYTES;
+    return w;
+}
+
+// everything on the device, on `st`; the caller is inside the opener's slot
+int kzg_open_cosets_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
+                           hipStream_t st) {
+    const unsigned log_n = o->log_n, log_l = o->log_l, log_r = log_n - log_l, log_m = log_r + 1;
+    const uint64_t n = (uint64_t)1 << log_n, r = (uint64_t)1 << log_r, l = (uint64_t)1 << log_l;
+    const CosetWork w = coset_work(o);
+    const G1NttVec u{w.u, 2 * r, w.table, w.tcap}, h{w.h, r, w.table, w.tcap};
+    // the l rows of g in one launch per G1_NTT_IO_LAUNCH slots, transformed as one batch; then every scalar times (2r)^-1, split
+    const Fr* row = nullptr;
+    ZCHK(g1_ntt_twiddle_row(log_m, 1, st, &row));
+    for (uint64_t first = 0; first < 2 * n; first += G1_NTT_IO_LAUNCH) {
+        hipLaunchKernelGGL(g1_ntt_gather_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, 2 * n - first), MSM_THREADS)),
+                           dim3(MSM_THREADS), 0, st, static_cast<const Fr*>(d_coeffs), (uint64_t)len, (uint32_t)log_n, (uint32_t)log_l, first, w.g);
+        HIPCHK(hipGetLastError());
+    }
+    ZCHK(coset_fr_rows(w.g, log_m, l, st));
+    for (uint64_t first = 0; first < 2 * n; first += G1_NTT_IO_LAUNCH) {
+        hipLaunchKernelGGL(g1_ntt_split_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, 2 * n - first), MSM_THREADS)),
+                           dim3(MSM_THREADS), 0, st, w.g, row + G1_NTT_TW_NINV, first, 2 * n);
+        HIPCHK(hipGetLastError());
+    }
+    // U_k = sum_b [g^_k] S^_k: the lanes' groups, then the fold of the partial sums into u (bit-reversed for the stages)
+    const bool folded = w.mac.groups > 1;
+    for (uint64_t k = 0; k < g1_coset_mac_launches(w.mac); k++) {
+        const uint64_t cnt = g1_coset_mac_launch_lanes(w.mac, k);
+        hipLaunchKernelGGL(g1_ntt_mac_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st,
+                           static_cast<const uint4*>(o->srs_hat.p), 2 * n, reinterpret_cast<const uint32_t*>(w.g), (uint32_t)log_m, w.mac.terms,
+                           k * w.mac.launch_lanes, (uint32_t)cnt, folded ? w.partial : u.pts, folded ? w.mac.lanes : u.cap,
+                           folded ? 0u : (uint32_t)log_m, w.table, w.tcap);
+        HIPCHK(hipGetLastError());
+    }
+    for (unsigned i = 0; i < g1_coset_fold_steps(w.mac); i++) {
+        const G1CosetFoldStep f = g1_coset_fold_step(log_n, log_l, w.mac, i);
+        for (uint64_t first = 0; first < f.lanes; first += G1_NTT_IO_LAUNCH) {
+            hipLaunchKernelGGL(g1_ntt_fold_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, f.lanes - first), G1_NTT_THREADS)),
+                               dim3(G1_NTT_THREADS), 0, st, w.partial, w.mac.lanes, f.lanes, first, u.pts, u.cap, f.last ? (uint32_t)log_m : 0u);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    ZCHK(g1_ntt_stages(u, log_m, 1, false, st));
+    // the proofs: NTT_r of the slice h
+    hipLaunchKernelGGL(g1_ntt_slice_kernel, dim3(g1_ntt_blocks(r, MSM_THREADS)), dim3(MSM_THREADS), 0, st, u.pts, u.cap,
+                       g1_coset_slice_map(log_n, log_l), h.pts, h.cap);
+    HIPCHK(hipGetLastError());
+    ZCHK(g1_ntt_stages(h, log_r, 0, false, st));
+    ZCHK(g1_ntt_store<true>(h, r, d_out_xy, d_out_is_inf, st));
+    if (d_out_evals) {  // f on the whole domain, natural order: coset k at k + j r
+        HIPCHK(hipMemsetAsync(d_out_evals, 0, 32 * n, st));
+        HIPCHK(hipMemcpyAsync(d_out_evals, d_coeffs, 32 * len, hipMemcpyDeviceToDevice, st));
+        ZCHK(run_ntt<Fr>(static_cast<Fr*>(d_out_evals), log_n, 1, 0, nullptr, st));
+    }
     return ZKP_OK;
 }
 
@@ -353,6 +448,147 @@ int zkp_kzg_open_all(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len
     HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, n, hipMemcpyDeviceToHost, st));
     if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------- coset openings
+extern "C" {
+
+int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned log_l, zkp_kzg_opener** out) try {
+    if (!srs || !out) return fail(ZKP_E_ARG, "null argument");
+    if (!g1_coset_shape_ok(log_n, log_l)) return fail(ZKP_E_ARG, "a coset opener needs log_l < log_n <= 23");
+    if (log_l == 0) return zkp_kzg_opener_create(srs, log_n, out);  // cosets of one point: the all-openings opener itself
+    if (!srs->shards.empty()) return fail(ZKP_E_ARG, kShardedG1Ntt);
+    const uint64_t n = (uint64_t)1 << log_n, l = (uint64_t)1 << log_l;
+    if (srs->n < n - l) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_n - 2^log_l points");
+    CTX_ENTER(srs->slot);
+    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    WsOrder ord(st);
+    std::unique_ptr<zkp_kzg_opener, void (*)(zkp_kzg_opener*)> o(new (std::nothrow) zkp_kzg_opener(), zkp_kzg_opener_destroy);
+    if (!o) return fail(ZKP_E_NOMEM, "host allocation failed");
+    o->log_n = log_n;
+    o->log_l = log_l;
+    static_assert(kKnobs[KNOB_KZG_COSET_GROUP_LOG].hi == G1_COSET_MAX_GROUP_LOG && G1_COSET_GROUP_LOG <= G1_COSET_MAX_GROUP_LOG,
+                  "knobs.hpp: g1_ntt_mac_kernel keeps the words of at most 2^G1_COSET_MAX_GROUP_LOG terms");
+    o->group_log = (unsigned)knob_int(KNOB_KZG_COSET_GROUP_LOG, G1_COSET_GROUP_LOG);
+    o->slot = ctx().slot;
+    o->device = ctx().device;
+    const G1CosetSizes sz = g1_coset_sizes(log_n, log_l, o->group_log);
+    {   // refused before anything is allocated when the sizes exceed the caller's budget or the free memory; a failed allocation
+        // after that ends in the same message, and `o` releases what it got
+        const size_t budget = (size_t)knob_int(KNOB_KZG_OPENER_MAX_BYTES);
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
+        const bool fits = sz.total <= budget && (!total_b || sz.total <= free_b);
+        if (!fits || o->srs_hat.grow(sz.srs_hat) != hipSuccess || o->work.grow(sz.total - sz.srs_hat) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ZKP_E_NOMEM, "zkp_kzg_opener_create_cosets: the workspaces of " + std::to_string(sz.total) + " bytes (" +
+                                         std::to_string(sz.srs_hat) + " kept slices + " + std::to_string(sz.total - sz.srs_hat) +
+                                         " per call) do not fit, " + std::to_string(free_b) + " of " + std::to_string(total_b) +
+                                         " bytes free on the device, ZKP_KZG_OPENER_MAX_BYTES " + std::to_string(budget));
+        }
+    }
+    const CosetWork w = coset_work(o.get());
+    // slice b: 2r points of the plane-major array of 2n, at b 2r; all of them are transformed where they stay, stage by stage together
+    const G1NttVec all{static_cast<uint4*>(o->srs_hat.p), 2 * n, w.table, w.tcap};
+    for (uint64_t first = 0; first < 2 * n; first += G1_NTT_IO_LAUNCH) {
+        hipLaunchKernelGGL(g1_ntt_load_slices_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, 2 * n - first), MSM_THREADS)),
+                           dim3(MSM_THREADS), 0, st, static_cast<const uint4*>(srs->d_xy.p), srs->d_inf.get(), (uint32_t)log_n, (uint32_t)log_l,
+                           first, all.pts, all.cap);
+        HIPCHK(hipGetLastError());
+    }
+    ZCHK(g1_ntt_stages(all, log_n - log_l + 1, 0, false, st, l));
+    {   // as zkp_kzg_opener_create: the plans, tables and scratch of the Fr transforms of a call, and the point transforms' constants
+        const Fr* row = nullptr;
+        HIPCHK(hipMemsetAsync(w.g, 0, sz.scalars, st));
+        ZCHK(coset_fr_rows(w.g, log_n - log_l + 1, l, st));
+        ZCHK(run_ntt<Fr>(w.g, log_n, 1, 0, nullptr, st));
+        ZCHK(g1_ntt_twiddle_row(log_n - log_l + 1, 1, st, &row));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    *out = o.release();
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_kzg_open_cosets_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
+                            void* stream) try {
+    ZCHK(kzg_open_all_args(o, d_coeffs, len, d_out_xy, d_out_is_inf, true));
+    CTX_ENTER(o->slot);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    return o->log_l ? kzg_open_cosets_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st)
+                    : kzg_open_all_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st);
+} ZKP_CATCH_INT
+
+int zkp_kzg_open_cosets(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, uint64_t* out_xy, uint8_t* out_is_inf,
+                        uint64_t* out_evals) try {
+    ZCHK(kzg_open_all_args(o, coeffs, len, out_xy, out_is_inf, true));
+    if (!o->log_l) return zkp_kzg_open_all(o, coeffs, len, out_xy, out_is_inf, out_evals);
+    CTX_ENTER(o->slot);
+    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    WsOrder ord(st);
+    const size_t n = (size_t)1 << o->log_n, r = n >> o->log_l;
+    void* ws = nullptr;  // coefficients | evaluations | points | flags
+    ZCHK(g1_ntt_workspace(32 * len + 32 * n + 96 * r + r, "zkp_kzg_open_cosets", &ws));
+    char* d_coeffs = static_cast<char*>(ws);
+    char* d_evals = d_coeffs + 32 * len;
+    char* d_xy = d_evals + 32 * n;
+    uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * r);
+    HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 32 * len, hipMemcpyHostToDevice, st));
+    ZCHK(kzg_open_cosets_locked(o, d_coeffs, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
+    HIPCHK(hipMemcpyAsync(out_xy, d_xy, 96 * r, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, r, hipMemcpyDeviceToHost, st));
+    if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+// e(W, [s^l]_2 - x^l G_2) == e(C - [I(s)]_1, G_2), I the interpolant of evals[j] at x w_l^j, j < l: coefficient i of I is x^-i times
+// coefficient i of the inverse transform of size l of the evaluations (host, O(l log l)); [I(s)]_1 is zkp_kzg_commit over `srs`
+int zkp_kzg_verify_coset(const zkp_bases* srs, const uint64_t g2_sl_xy[24], const uint64_t commit_xy[12], uint8_t commit_is_inf,
+                         const uint64_t w_xy[12], uint8_t w_is_inf, const uint64_t x[4], unsigned log_l, const uint64_t* evals,
+                         int* accepted) try {
+    if (!srs || !g2_sl_xy || (!commit_is_inf && !commit_xy) || (!w_is_inf && !w_xy) || !x || !evals || !accepted)
+        return fail(ZKP_E_ARG, "null argument");
+    if (log_l >= G1_NTT_MAX_LOG - 1) return fail(ZKP_E_ARG, "log_l of a coset is below 23");
+    const uint64_t l = (uint64_t)1 << log_l;
+    if (srs->n < l) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_l points");
+    const G2Aff g2 = G2Aff::generator();
+    G2Aff g2sl = G2Aff::infinity();
+    ZCHK(g2_validate(g2_sl_xy, "[s^l]_2", &g2sl));
+    ZCHK(g1_validate(commit_xy, commit_is_inf, "commitment"));
+    ZCHK(g1_validate(w_xy, w_is_inf, "opening"));
+    const HFr hx = HFr::load(x);
+    if (hx == HFr::zero()) return fail(ZKP_E_ARG, "x = 0 is the shift of no coset");
+    // inverse transform of the evaluations, decimation in time
+    std::vector<HFr> c(l);
+    for (uint64_t j = 0; j < l; j++) c[g1_ntt_bitrev((uint32_t)j, log_l)] = HFr::load(evals + 4 * j);
+    const HFr w_inv = fr_root_of_unity(log_l).inverse();
+    for (unsigned s = 0; s < log_l; s++) {
+        const uint64_t half = (uint64_t)1 << s;
+        HFr ws = w_inv;
+        for (unsigned q = s + 1; q < log_l; q++) ws = ws.sqr();  // the root of order 2 half
+        for (uint64_t blk = 0; blk < l; blk += 2 * half) {
+            HFr tw = HFr::one();
+            for (uint64_t j = 0; j < half; j++, tw = tw * ws) {
+                const HFr a = c[blk + j], t = c[blk + j + half] * tw;
+                c[blk + j] = a + t;
+                c[blk + j + half] = a - t;
+            }
+        }
+    }
+    const HFr x_inv = hx.inverse();
+    HFr scale = HFr::from_u64(l).inverse();
+    std::vector<uint64_t> coeffs(4 * l);
+    for (uint64_t i = 0; i < l; i++, scale = scale * x_inv) (c[i] * scale).store(&coeffs[4 * i]);
+    uint64_t i_xy[12];
+    uint8_t i_inf = 0;
+    ZCHK(zkp_kzg_commit(srs, coeffs.data(), (size_t)l, i_xy, &i_inf));
+    const G2Aff a = g2sl.add(g2.mul(hx.pow_u64(l).from_mont().l).neg());
+    const HXyzz b = g1_load(commit_xy, commit_is_inf).add(g1_load(i_xy, i_inf).negate());
+    *accepted = pairings_equal(g1_load(w_xy, w_is_inf), a, b, g2) ? 1 : 0;
     return ZKP_OK;
 } ZKP_CATCH_INT
 

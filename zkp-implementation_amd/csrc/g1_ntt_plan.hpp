@@ -127,4 +127,97 @@ inline G1OpenSizes g1_open_sizes(unsigned log_n) {
     return s;
 }
 
+// The n / l multi-point proofs of f, one per coset of l = 2^log_l points (include/zkp_hip.h, zkp_kzg_open_cosets): r = n / l >= 2
+// cosets, coset k = {w^(k + j r) : j < l}, the roots of X^l - x_k^l with x_k = w^k; proof k is the commitment of the quotient of f
+// by that binomial.  The all-openings construction above, once per slice b < l of the SRS and of f, in vectors of 2r:
+//   s^(b)_j = S_{(r-2-j) l + b} for j < r - 1, identity behind;   g^(b)_t = f_{(t+1) l + b} for t < r - 1 and below len, zero behind;
+//   U_k = sum_{b<l} [NTT_2r(g^(b))_k] NTT_2r(s^(b))_k for k < 2r;   u = iNTT_2r(U);   h_i = u_{r-2+i} for i < r - 1, h_{r-1} = O;
+//   proofs = NTT_r(h), whose root is w^l.
+// (u_m = sum_b sum_{j+t=m} [g^(b)_t] s^(b)_j, so h_i = sum_b sum_t [f_{(t+1) l + b}] S_{(t-i) l + b} = sum_c [f_{(i+1) l + c}] S_c: the
+// coefficient of x_k^(l i) in the quotient's commitment, q_k = sum_i x_k^(l i) sum_c f_{(i+1) l + c} X^c.)  SRS points S_0 .. S_{n-l-1}
+// are read.  l = 1 gives the maps of the all-openings call (d = r - 1).
+constexpr unsigned G1_COSET_MAX_GROUP_LOG = 3;  // a lane of the multiply-accumulate pass sums at most 8 terms
+// B = 2^G1_COSET_GROUP_LOG terms share the 128 doublings of one lane.  0 is the per-term multiplication plus the fold; it stays 0
+// until profiles/kzg_open_cosets.md holds a measurement in which a larger group wins.
+constexpr unsigned G1_COSET_GROUP_LOG = 0;
+
+inline bool g1_coset_shape_ok(unsigned log_n, unsigned log_l) { return log_l < log_n && log_n + 1 <= G1_NTT_MAX_LOG; }
+ZKP_G1NTT_FN G1NttLoadMap g1_coset_srs_map(unsigned log_n, unsigned log_l, uint64_t b) {  // slice b < l of the SRS, a vector of 2r
+    const uint64_t r = (uint64_t)1 << (log_n - log_l), l = (uint64_t)1 << log_l;
+    return G1NttLoadMap{2 * r, r - 1, (int64_t)((r - 2) * l + b), -(int32_t)l, log_n - log_l + 1};
+}
+ZKP_G1NTT_FN int64_t g1_coset_coeff_source(unsigned log_n, unsigned log_l, uint64_t len, uint64_t b, uint64_t t) {  // slot t of row b of g, -1: zero
+    const uint64_t r = (uint64_t)1 << (log_n - log_l), src = ((t + 1) << log_l) + b;
+    return t + 1 < r && src < len ? (int64_t)src : -1;
+}
+inline G1NttLoadMap g1_coset_slice_map(unsigned log_n, unsigned log_l) {  // h out of u, loaded for the transform of r
+    const uint64_t r = (uint64_t)1 << (log_n - log_l);
+    return G1NttLoadMap{r, r - 1, (int64_t)r - 2, 1, log_n - log_l};
+}
+
+// The multiply-accumulate pass: 2r outputs of l terms each.  Group q of output k holds the `terms` slices b = q terms + j, j < terms
+// (all l of them where l is below the group size), and belongs to lane q 2r + k -- neighbouring lanes take neighbouring points of a
+// slice.  Term j of that lane is element ((q terms + j) 2r + k) of the transformed SRS and of the transformed rows of g.  A launch
+// takes at most G1_NTT_LAUNCH terms, for each of them parks P + phi(P) in the table.
+struct G1CosetMac {
+    uint32_t terms;        // per lane
+    uint64_t groups;       // per output: l / terms partial sums
+    uint64_t lanes;        // groups * 2r
+    uint64_t launch_lanes; // lanes of every launch but the last
+};
+inline G1CosetMac g1_coset_mac(unsigned log_n, unsigned log_l, unsigned group_log) {
+    const unsigned t_log = group_log < log_l ? group_log : log_l;
+    G1CosetMac m;
+    m.terms = 1u << t_log;
+    m.groups = (uint64_t)1 << (log_l - t_log);
+    m.lanes = m.groups << (log_n - log_l + 1);
+    m.launch_lanes = G1_NTT_LAUNCH >> t_log;
+    return m;
+}
+inline uint64_t g1_coset_mac_launches(const G1CosetMac& m) { return (m.lanes + m.launch_lanes - 1) / m.launch_lanes; }
+inline uint64_t g1_coset_mac_launch_lanes(const G1CosetMac& m, uint64_t k) {
+    const uint64_t first = k * m.launch_lanes;
+    return first >= m.lanes ? 0 : m.lanes - first < m.launch_lanes ? m.lanes - first : m.launch_lanes;
+}
+ZKP_G1NTT_FN uint64_t g1_coset_mac_element(unsigned log_m, uint32_t terms, uint64_t lane, uint32_t j) {  // log_m: of 2r
+    return (((lane >> log_m) * terms + j) << log_m) + (lane & (((uint64_t)1 << log_m) - 1));
+}
+
+// The fold of the `groups` partial sums of every output, pairwise: step i halves what is left, partial q += partial q + half for
+// q < half, over half * 2r lanes; the last step (half == 1) writes into the vector the stages run on.  No step when groups == 1:
+// the multiply-accumulate pass then writes there itself.
+struct G1CosetFoldStep {
+    uint64_t half, lanes;
+    bool last;
+};
+inline unsigned g1_coset_fold_steps(const G1CosetMac& m) {
+    unsigned s = 0;
+    while (((uint64_t)1 << s) < m.groups) s++;
+    return s;
+}
+inline G1CosetFoldStep g1_coset_fold_step(unsigned log_n, unsigned log_l, const G1CosetMac& m, unsigned i) {
+    G1CosetFoldStep f;
+    f.half = m.groups >> (i + 1);
+    f.lanes = f.half << (log_n - log_l + 1);
+    f.last = f.half == 1;
+    return f;
+}
+
+struct G1CosetSizes {
+    size_t srs_hat, partial, work, slice, scalars, table, total;  // the l transformed slices (kept); the partial sums, u, h, g, the lanes' table
+};
+inline G1CosetSizes g1_coset_sizes(unsigned log_n, unsigned log_l, unsigned group_log) {
+    const uint64_t n = (uint64_t)1 << log_n, r = n >> log_l;
+    const G1CosetMac m = g1_coset_mac(log_n, log_l, group_log);
+    G1CosetSizes s;
+    s.srs_hat = G1_NTT_POINT_BYTES * 2 * n;
+    s.partial = m.groups > 1 ? G1_NTT_POINT_BYTES * m.lanes : 0;
+    s.work = G1_NTT_POINT_BYTES * 2 * r;
+    s.slice = G1_NTT_POINT_BYTES * r;
+    s.scalars = 32 * 2 * n;
+    s.table = g1_ntt_sizes(log_n + 1, 2 * n).table;  // one entry per term of the longest launch; the stages need fewer
+    s.total = s.srs_hat + s.partial + s.work + s.slice + s.scalars + s.table;
+    return s;
+}
+
 }  // namespace zkp

@@ -16,6 +16,7 @@ enum Knob {
     KNOB_FOLD_LANE_MIN = KNOB_MSM_PLAN_END, KNOB_PYR_TAIL_THREADS, KNOB_PYR_TAIL_BLOCKS, KNOB_PYR_TAIL_HALF, KNOB_TEST_TAIL_STARVE,
     KNOB_MSM_NO_POLL, KNOB_POOL_NO_WARM, KNOB_MSM_BALANCE_FROM, KNOB_SRS_EXPAND_MAX_BYTES, KNOB_NTT_TW_MATRIX_MAX_LOG,
     KNOB_NTT_NO_WIDE_PASS, KNOB_NTT_SHARD_MIN_LOG, KNOB_PLONK_NO_POLL, KNOB_FRI_ZERO_AS_0, KNOB_FRI_FR_TAIL_LOG,
+    KNOB_KZG_COSET_GROUP_LOG, KNOB_KZG_OPENER_MAX_BYTES,
     KNOB_COUNT
 };
 
@@ -89,6 +90,11 @@ constexpr KnobRow kKnobs[KNOB_COUNT] = {
      "1: a zero field element enters hashes and the transcript as \"0\" instead of the empty string"},
     {KNOB_FRI_FR_TAIL_LOG, "ZKP_FRI_FR_TAIL_LOG", KNOB_TUNING, KNOB_INT_CLAMP, 0, 10, 9,
      "FRI over Fr: layers of up to 2^v points run in the tail kernel (0: none)"},
+    {KNOB_KZG_COSET_GROUP_LOG, "ZKP_KZG_COSET_GROUP_LOG", KNOB_TUNING, KNOB_INT, 0, 3, KNOB_COMPUTED,
+     "coset openers created from now on sum 2^v terms per lane of the multiply-accumulate pass (default: G1_COSET_GROUP_LOG): "
+     "profiles/kzg_open_cosets.md"},
+    {KNOB_KZG_OPENER_MAX_BYTES, "ZKP_KZG_OPENER_MAX_BYTES", KNOB_POLICY, KNOB_INT, 0, LLONG_MAX, LLONG_MAX,
+     "a coset opener whose slices and workspaces are larger than this is refused with ZKP_E_NOMEM before anything is allocated"},
 };
 
 constexpr bool knob_rows_in_enum_order() {

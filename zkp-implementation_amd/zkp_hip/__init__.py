@@ -64,6 +64,10 @@ _SIGS = {
     "zkp_kzg_opener_destroy": ([_VP], None),
     "zkp_kzg_open_all": ([_VP, _VP, _SZ, _VP, _U8P, _VP], C.c_int),
     "zkp_kzg_open_all_dev": ([_VP, _VP, _SZ, _VP, _U8P, _VP, _VP], C.c_int),
+    "zkp_kzg_opener_create_cosets": ([_VP, C.c_uint, C.c_uint, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_open_cosets": ([_VP, _VP, _SZ, _VP, _U8P, _VP], C.c_int),
+    "zkp_kzg_open_cosets_dev": ([_VP, _VP, _SZ, _VP, _U8P, _VP, _VP], C.c_int),
+    "zkp_kzg_verify_coset": ([_VP, _VP, _VP, C.c_uint8, _VP, C.c_uint8, _VP, C.c_uint, _VP, C.POINTER(C.c_int)], C.c_int),
     "zkp_msm_g1": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1_batch_dev": ([_VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
@@ -795,6 +799,18 @@ def kzg_verify(g2s_xy, commitment, opening, y, z):
     return bool(acc.value)
 
 
+def kzg_verify_coset(srs, g2_sl_xy, commitment, opening, x, evals):
+    """zkp_kzg_verify_coset: one coset proof of KzgOpener.open_cosets.  evals: the (l, 4) values f(x w_l^j), l a power of two;
+    g2_sl_xy = [s^l]_2; commitment / opening = (xy, is_inf); srs: G1Bases with at least l points."""
+    acc = C.c_int(0)
+    g2 = _np(g2_sl_xy, np.uint64).reshape(24)
+    c, w = _np(commitment[0], np.uint64).reshape(12), _np(opening[0], np.uint64).reshape(12)
+    xx, ev = _np(x, np.uint64).reshape(4), _np(evals, np.uint64, (-1, 4))
+    _chk(lib().zkp_kzg_verify_coset(srs._h, _ptr(g2), _ptr(c), int(commitment[1]), _ptr(w), int(opening[1]), _ptr(xx), _log2(ev.shape[0]),
+                                    _ptr(ev), C.byref(acc)))
+    return bool(acc.value)
+
+
 def kzg_batch_verify(g2s_xy, commitments, points, openings, evals, r_primes):
     """KzgScheme::batch_verify (kzg/src/scheme.rs:215-245); commitments / openings: (n, 12) finite points."""
     g2s = _np(g2s_xy, np.uint64).reshape(24)
@@ -889,12 +905,17 @@ def g1_ntt(xy, is_inf=None, inverse=False):
 
 
 class KzgOpener:
-    """zkp_kzg_opener: all n = 2^log_n openings of a polynomial at the roots of unity in one call (Feist-Khovratovich)."""
+    """zkp_kzg_opener: all n = 2^log_n openings of a polynomial at the roots of unity in one call (Feist-Khovratovich); with
+    log_l > 0 the n / 2^log_l multi-point proofs, one per coset of 2^log_l points (open_cosets)."""
 
-    def __init__(self, srs_bases, log_n):
-        self.log_n, self.n = log_n, 1 << log_n
+    def __init__(self, srs_bases, log_n, log_l=0):
+        self.log_n, self.n, self.log_l = log_n, 1 << log_n, log_l
+        self.cosets = self.n >> log_l
         self._h = C.c_void_p()
-        _chk(lib().zkp_kzg_opener_create(srs_bases._h, log_n, C.byref(self._h)))
+        if log_l:
+            _chk(lib().zkp_kzg_opener_create_cosets(srs_bases._h, log_n, log_l, C.byref(self._h)))
+        else:
+            _chk(lib().zkp_kzg_opener_create(srs_bases._h, log_n, C.byref(self._h)))
 
     def open_all(self, coeffs, want_evals=True):
         """-> ((n, 12) proof points, (n,) flags), (n, 4) evaluations f(w^m) (None without want_evals); proof m is kzg_open at w^m."""
@@ -910,6 +931,22 @@ class KzgOpener:
         ev = _dev_ptr(out_evals_tensor, 32 * self.n) if out_evals_tensor is not None else None
         _chk(lib().zkp_kzg_open_all_dev(self._h, _dev_ptr(coeffs_tensor, 32 * length), length, _dev_ptr(out_xy_tensor, 96 * self.n),
                                         _dev_ptr(out_inf_tensor, self.n), ev, _stream_ptr(stream)))
+
+    def open_cosets(self, coeffs, evals=False):
+        """-> ((r, 12) proof points, (r,) flags), (n, 4) evaluations on the whole domain (None without evals), r = n / 2^log_l: proof
+        k is the commitment of the quotient of f by X^l - w^(k l); the values of coset k are evaluations[k::r]."""
+        coeffs = _np(coeffs, np.uint64, (-1, 4))
+        xy = np.zeros((self.cosets, 12), dtype=np.uint64)
+        inf = np.zeros(self.cosets, dtype=np.uint8)
+        ev = np.zeros((self.n, 4), dtype=np.uint64) if evals else None
+        _chk(lib().zkp_kzg_open_cosets(self._h, _ptr(coeffs), coeffs.shape[0], _ptr(xy), _ptr(inf), _ptr(ev)))
+        return (xy, inf), ev
+
+    def open_cosets_dev(self, coeffs_tensor, length, out_xy_tensor, out_inf_tensor, out_evals_tensor=None, stream=None):
+        """The same with everything resident on the opener's device; nothing is synchronised."""
+        ev = _dev_ptr(out_evals_tensor, 32 * self.n) if out_evals_tensor is not None else None
+        _chk(lib().zkp_kzg_open_cosets_dev(self._h, _dev_ptr(coeffs_tensor, 32 * length), length, _dev_ptr(out_xy_tensor, 96 * self.cosets),
+                                           _dev_ptr(out_inf_tensor, self.cosets), ev, _stream_ptr(stream)))
 
     def close(self):
         if self._h:
@@ -944,6 +981,7 @@ class KzgScheme:
     def __init__(self, srs, expand_bases=True):  # scheme.rs:34
         self.srs = srs
         self._openers = {}  # log_n -> KzgOpener (open_all), released by close()
+        self._coset_openers = {}  # (log_n, log_l) -> KzgOpener (open_cosets), released by close()
         if expand_bases:  # the SRS is fixed for the life of the scheme: pay the one-off expansion here
             srs.bases.precompute(0)
 
@@ -966,11 +1004,20 @@ class KzgScheme:
             self._openers[log_n] = KzgOpener(self.srs.bases, log_n)
         return self._openers[log_n].open_all(coeffs)
 
+    def open_cosets(self, coeffs, log_n, log_l, evals=False):
+        """One proof per coset of 2^log_l points of the domain of 2^log_n roots of unity: KzgOpener.open_cosets (the opener is kept
+        per shape)."""
+        if (log_n, log_l) not in self._coset_openers:
+            self._coset_openers[log_n, log_l] = KzgOpener(self.srs.bases, log_n, log_l)
+        return self._coset_openers[log_n, log_l].open_cosets(coeffs, evals=evals)
+
     def close(self):
-        """Release the device memory of the openers open_all made (about 1.4 KB per point of each domain); the SRS stays."""
-        for op in self._openers.values():
+        """Release the device memory of the openers open_all and open_cosets made (about 1.4 KB per point of a domain for open_all, about
+        1.1 KB for open_cosets: 512 B of kept slices, 512 B of partial sums and 64 B of scalars, plus up to 64 MiB); the SRS stays."""
+        for op in list(self._openers.values()) + list(self._coset_openers.values()):
             op.close()
         self._openers = {}
+        self._coset_openers = {}
 
     def __del__(self):
         try:
