@@ -37,9 +37,10 @@
  * ZKP_PYR_TAIL_THREADS / ZKP_PYR_TAIL_BLOCKS / ZKP_PYR_TAIL_HALF (geometry of the launch that runs the last levels of the bucket reduction:
  * workgroup size 64..512, workgroups per bucket set 1..256, pairs per array from which it takes over; defaults 256 / 16 / 64; tuning aids),
  * ZKP_FRI_FR_TAIL_LOG (0..10: log2 of the largest layer zkp_fri_prove_fr runs in its one-workgroup tail kernel, default 9, 0 = none;
- * tuning aid), ZKP_KZG_COSET_GROUP_LOG (0..3: log2 of the terms one lane of a coset opener's multiply-accumulate pass sums, read by
- * zkp_kzg_opener_create_cosets, default 0; tuning aid), ZKP_KZG_OPENER_MAX_BYTES (zkp_kzg_opener_create_cosets refuses, with
- * ZKP_E_NOMEM and the sizes in zkp_last_error(), an opener that needs more device memory than this many bytes).
+ * tuning aid), ZKP_KZG_COSET_GROUP_LOG (0..3: log2 of the terms one lane of an opener's multiply-accumulate pass sums, read by
+ * zkp_kzg_opener_create_cosets, default 0, without effect at log_l = 0; tuning aid), ZKP_KZG_OPENER_MAX_BYTES (zkp_kzg_opener_create
+ * and zkp_kzg_opener_create_cosets refuse, with ZKP_E_NOMEM and the sizes in zkp_last_error(), an opener that needs more device
+ * memory than this many bytes; default: no limit).
  */
 #ifndef ZKP_HIP_H
 #define ZKP_HIP_H
@@ -280,10 +281,13 @@ int zkp_g1_ntt(uint64_t *xy, uint8_t *is_inf, unsigned log_n, int inverse);
 int zkp_g1_bases_lagrange(const zkp_bases *srs, unsigned log_n, zkp_bases **out);
 /* All n openings of one polynomial at the n roots of unity (Feist-Khovratovich): for f = sum_{k<len} f_k X^k, len <= n,
  *   out point m = [(f(s) - f(w^m)) / (s - w^m)]G = what zkp_kzg_open returns at z = w^m, and out_evals[m] = f(w^m),
- * from three point transforms (two of 2n, one of n) and one pointwise scaling instead of n MSMs.  An opener holds the transform of
- * the SRS (256 B x 2n) and the workspaces of a call (about 850 B x n); log_n is 1 .. 23 (else ZKP_E_ARG), the source needs n - 1
- * points (ZKP_E_SIZE) on one device (sharded: ZKP_E_ARG) and may be destroyed afterwards.  len == 0 is ZKP_E_ARG as in zkp_kzg_open,
- * len > n ZKP_E_SIZE; coefficients are used as given, zero-padded (an all-zero or constant vector gives n identities).
+ * from three point transforms (two of 2n, one of n) and one pointwise pass of 2n products instead of n MSMs.  This is the coset
+ * construction below with cosets of one point: zkp_kzg_opener_create(srs, log_n, out) is zkp_kzg_opener_create_cosets(srs, log_n, 0,
+ * out), and zkp_kzg_open_all* run what zkp_kzg_open_cosets* run on such an opener.  It holds the transform of the SRS (256 B x 2n)
+ * and the workspaces of a call (832 B x n, plus a table of 256 B x min(2n, 2^18), at most 64 MiB); log_n is 1 .. 23 (else ZKP_E_ARG),
+ * the source needs n - 1 points (ZKP_E_SIZE) on one device (sharded: ZKP_E_ARG) and may be destroyed afterwards; workspaces that do
+ * not fit are ZKP_E_NOMEM as below.  len == 0 is ZKP_E_ARG as in zkp_kzg_open, len > n ZKP_E_SIZE; coefficients are used as given,
+ * zero-padded (an all-zero or constant vector gives n identities).
  * out_xy n x 12 limbs, out_is_inf n bytes, out_evals n x 4 limbs or NULL.  Calls on one opener are serialised with its slot. */
 typedef struct zkp_kzg_opener zkp_kzg_opener;
 int zkp_kzg_opener_create(const zkp_bases *srs, unsigned log_n, zkp_kzg_opener **out);
@@ -291,7 +295,7 @@ void zkp_kzg_opener_destroy(zkp_kzg_opener *o);
 int zkp_kzg_open_all(const zkp_kzg_opener *o, const uint64_t *coeffs, size_t len, uint64_t *out_xy, uint8_t *out_is_inf,
                      uint64_t *out_evals);
 /* Everything in device memory of the opener's device, launched on `stream`.  Neither allocates nor synchronises: the opener owns
- * the workspaces, and zkp_kzg_opener_create has already built the plans and tables of the two Fr transforms a call runs. */
+ * the workspaces, and its creation has already built the plans and tables of the two Fr transforms a call runs. */
 int zkp_kzg_open_all_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_t len, void *d_out_xy, uint8_t *d_out_is_inf,
                          void *d_out_evals, void *stream);
 /* Coset openings: the n / l multi-point proofs of one polynomial, one per coset of l = 2^log_l points of the domain (the "cells" of
@@ -300,17 +304,20 @@ int zkp_kzg_open_all_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_t l
  *   out point k = [q_k(s)]G, q_k the quotient of f by X^l - x_k^l,
  * from the multi-point form of the same algorithm: per slice b < l of the SRS a transform of 2r points (kept by the opener), per
  * call one batched Fr transform of l rows of 2r, a multiply-accumulate pass over the 2n products (one joint double-and-add per
- * group of terms, then a pairwise fold), and point transforms of 2r and r only.  zkp_kzg_opener_create_cosets returns the same
- * opaque type as zkp_kzg_opener_create: it holds the l transformed slices (256 B x 2n in all) and the workspaces, and has built
- * every plan and table a call uses.  1 <= log_n - log_l and log_n <= 23, else ZKP_E_ARG; the source needs n - l points
- * (ZKP_E_SIZE) on one device (sharded: ZKP_E_ARG); workspaces that do not fit -- more than the device has free, or more than
- * ZKP_KZG_OPENER_MAX_BYTES -- are ZKP_E_NOMEM with the sizes in zkp_last_error() and nothing left allocated.  log_l = 0 is zkp_kzg_opener_create itself.
+ * group of terms, then a pairwise fold), and point transforms of 2r and r only.  zkp_kzg_opener_create_cosets is the one creation
+ * of a zkp_kzg_opener: it holds the l transformed slices (256 B x 2n in all) and the workspaces of a call (256 B x 2n / B of partial sums
+ * where a lane sums B < l terms, 768 B x r, 64 B x n of scalars and a table of 256 B x min(2n, 2^18)), and has built every
+ * plan and table a call uses.  1 <= log_n - log_l and log_n <= 23, else ZKP_E_ARG; the source needs n - l points (ZKP_E_SIZE) on one
+ * device (sharded: ZKP_E_ARG); workspaces that do not fit -- more than the device has free, or more than ZKP_KZG_OPENER_MAX_BYTES
+ * (default: no limit) -- are ZKP_E_NOMEM with the sizes in zkp_last_error() and nothing left allocated, for every log_l.
+ * log_l = 0 is the case of all n openings, one slice and one row: a lane of the pass takes one product and writes it where the
+ * inverse transform runs, nothing is folded, and proof k is the opening at w^k.
  * zkp_kzg_open_cosets: out_xy r x 12 limbs, out_is_inf r bytes, out_evals n x 4 limbs or NULL -- f on the whole domain in natural
- * order, so the values of coset k sit at k + j r.  len == 0 is ZKP_E_ARG, len > n ZKP_E_SIZE; len <= l gives r identities.  On an
- * opener with log_l = 0 it returns what zkp_kzg_open_all returns; zkp_kzg_open_all* on an opener with log_l > 0 is ZKP_E_ARG.
+ * order, so the values of coset k sit at k + j r.  len == 0 is ZKP_E_ARG, len > n ZKP_E_SIZE; len <= l gives r identities.  It
+ * takes an opener of any log_l (with log_l = 0 it is zkp_kzg_open_all); zkp_kzg_open_all* on an opener with log_l > 0 is ZKP_E_ARG.
  * The device entry, like zkp_kzg_open_all_dev, neither allocates nor synchronises.
- * ZKP_KZG_COSET_GROUP_LOG (0..3, read when an opener is created; tuning aid) sets how many terms a lane of the multiply-accumulate
- * pass sums: profiles/kzg_open_cosets.md. */
+ * ZKP_KZG_COSET_GROUP_LOG (0..3, read when an opener is created; tuning aid; without effect at log_l = 0) sets how many terms a lane
+ * of the multiply-accumulate pass sums: profiles/kzg_open_cosets.md. */
 int zkp_kzg_opener_create_cosets(const zkp_bases *srs, unsigned log_n, unsigned log_l, zkp_kzg_opener **out);
 int zkp_kzg_open_cosets(const zkp_kzg_opener *o, const uint64_t *coeffs, size_t len, uint64_t *out_xy, uint8_t *out_is_inf,
                         uint64_t *out_evals);

@@ -109,6 +109,28 @@ static void check_maps(unsigned log_n, unsigned log_l) {
         for (uint64_t i = 0; ok && i < r; i++) ok = g1_ntt_load_source(hm, i) == (i < r - 1 ? (int64_t)(r - 2 + i) : -1);
         CHECK(ok && 2 * (r - 2) < 2 * r, "(%u,%u): slice map", log_n, log_l);
     }
+    if (log_l == 0) {  // all n openings, d = n - 1 SRS points: the closed forms of zkp_kzg_open_all (tests/host/g1_ntt_plan.cpp has them too)
+        const uint64_t d = n - 1;
+        const G1NttLoadMap sm = g1_coset_srs_map(log_n, 0, 0), hm = g1_coset_slice_map(log_n, 0);
+        bool ok = sm.count == 2 * n && sm.rev_log == log_n + 1 && hm.count == n && hm.rev_log == log_n;
+        for (uint64_t j = 0; ok && j < 2 * n; j++) ok = g1_ntt_load_source(sm, j) == (j < d ? (int64_t)(d - 1 - j) : -1);  // source d-1-j
+        for (uint64_t i = 0; ok && i < n; i++) ok = g1_ntt_load_source(hm, i) == (i < d ? (int64_t)(d - 1 + i) : -1);      // slice d-1+i
+        CHECK(ok && 2 * d - 2 < 2 * n, "(%u,0): the maps of all openings", log_n);
+        for (uint64_t len = 1; len <= n; len++) {
+            bool cok = true;
+            for (uint64_t t = 0; t < 2 * n; t++) cok = cok && g1_coset_coeff_source(log_n, 0, len, 0, t) == (t + 1 < len ? (int64_t)(t + 1) : -1);
+            CHECK(cok, "(%u,0) len=%llu: slot t of g is not coefficient t + 1", log_n, (ull)len);
+        }
+        for (unsigned group_log : GROUPS) {
+            const G1CosetSizes sz = g1_coset_sizes(log_n, 0, group_log);
+            const G1CosetMac m = g1_coset_mac(log_n, 0, group_log);
+            CHECK(sz.srs_hat == 512 * n && sz.partial == 0 && sz.work == 512 * n && sz.slice == 256 * n && sz.scalars == 64 * n &&
+                      sz.table == g1_ntt_sizes(log_n + 1, 2 * n).table && sz.total == sz.srs_hat + sz.work + sz.slice + sz.scalars + sz.table,
+                  "(%u,0) B=2^%u: the sizes of all openings", log_n, group_log);
+            CHECK(m.terms == 1 && m.groups == 1 && m.lanes == 2 * n && m.launch_lanes == G1_NTT_LAUNCH && g1_coset_fold_steps(m) == 0,
+                  "(%u,0) B=2^%u: one term per lane, no fold", log_n, group_log);
+        }
+    }
 }
 
 // groups, launches, fold and sizes of one shape and group size; `elements`: also walk every term (small shapes)
@@ -272,8 +294,10 @@ int main(int argc, char** argv) {
             check_pipeline(log_n, log_l);
         }
     for (unsigned log_n : {17u, 18u, 20u, 23u})  // where a pass takes more than one launch
-        for (unsigned log_l : {1u, 6u, 10u, log_n - 1})
+        for (unsigned log_l : {0u, 1u, 6u, 10u, log_n - 1})
             for (unsigned group_log : GROUPS) check_mac(log_n, log_l, group_log, log_n <= 18);
+    // all openings: n = 2^18 is the smallest whose 2n products take two launches (the suite's test_open_all_two_launches)
+    CHECK(g1_coset_mac_launches(g1_coset_mac(17, 0, 0)) == 1 && g1_coset_mac_launches(g1_coset_mac(18, 0, 0)) == 2, "(18,0): two launches");
     {   // (18, 10), the suite's launch-splitting case: 2^19 terms in two launches, and with groups of 8 lane 2^15 -- the first of the
         // second launch -- begins a group
         const G1CosetMac m = g1_coset_mac(18, 10, 3);

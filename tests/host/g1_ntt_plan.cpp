@@ -115,10 +115,10 @@ static void check_size(unsigned log_n) {
                       sz.points % 256 == 0, "log_n=%u: sizes", log_n);
         }
     }
-    if (log_n >= 1 && log_n + 1 <= G1_NTT_MAX_LOG) {  // an opener
+    if (log_n >= 1 && log_n + 1 <= G1_NTT_MAX_LOG) {  // an opener of all n points: the coset construction with log_l = 0
         const uint64_t d = n - 1;
-        const G1NttLoadMap sm = g1_open_srs_map(log_n), hm = g1_open_slice_map(log_n);
-        bool ok = sm.count == 2 * n && sm.rev_log == log_n + 1 && hm.count == n && hm.rev_log == log_n;
+        const G1NttLoadMap sm = g1_coset_srs_map(log_n, 0, 0), hm = g1_coset_slice_map(log_n, 0);
+        bool ok = g1_coset_shape_ok(log_n, 0) && sm.count == 2 * n && sm.rev_log == log_n + 1 && hm.count == n && hm.rev_log == log_n;
         for (uint64_t j = 0; ok && j < 2 * n; j++) ok = g1_ntt_load_source(sm, j) == (j < d ? (int64_t)(d - 1 - j) : -1);
         for (uint64_t i = 0; ok && i < n; i++) ok = g1_ntt_load_source(hm, i) == (i < d ? (int64_t)(d - 1 + i) : -1);
         CHECK(ok && 2 * d - 2 < 2 * n, "log_n=%u: opener maps", log_n);  // (the largest index of u that is read)
@@ -127,16 +127,16 @@ static void check_size(unsigned log_n) {
             bool cok = true;
             for (uint64_t t : {(uint64_t)0, (uint64_t)1, len - 2, len - 1, len, d - 1, d, 2 * n - 1}) {
                 if (t >= 2 * n) continue;
-                cok = cok && g1_open_coeff_source(len, t) == (t + 1 < len ? (int64_t)(t + 1) : -1);
+                cok = cok && g1_coset_coeff_source(log_n, 0, len, 0, t) == (t + 1 < len ? (int64_t)(t + 1) : -1);
             }
-            const G1OpenCoeffRun run = g1_open_coeff_run(len);  // what the driver copies: inside the coefficients and inside g
-            cok = cok && run.first + run.count <= len && run.count <= d && (len < 2 || (run.first == 1 && run.count == len - 1));
             CHECK(cok, "log_n=%u len=%llu: coefficient slots", log_n, (unsigned long long)len);
         }
-        const G1OpenSizes os = g1_open_sizes(log_n);
-        CHECK(os.srs_hat == 512 * n && os.work == 512 * n && os.slice == 256 * n && os.scalars == 64 * n &&
-                  os.table == g1_ntt_sizes(log_n + 1, 2 * n).table &&
-                  os.total == os.srs_hat + os.work + os.slice + os.scalars + os.table, "log_n=%u: opener sizes", log_n);
+        for (unsigned group_log = 0; group_log <= G1_COSET_MAX_GROUP_LOG; group_log++) {  // (no group size changes anything at l = 1)
+            const G1CosetSizes os = g1_coset_sizes(log_n, 0, group_log);
+            CHECK(os.srs_hat == 512 * n && os.partial == 0 && os.work == 512 * n && os.slice == 256 * n && os.scalars == 64 * n &&
+                      os.table == g1_ntt_sizes(log_n + 1, 2 * n).table &&
+                      os.total == os.srs_hat + os.work + os.slice + os.scalars + os.table, "log_n=%u: opener sizes", log_n);
+        }
     }
 }
 
@@ -149,11 +149,12 @@ static void dump(unsigned log_n) {
         }
     for (uint64_t i = 0; i < n; i++) printf("r %llu %u\n", (unsigned long long)i, g1_ntt_bitrev((uint32_t)i, log_n));
     if (log_n < 1) return;
-    const G1NttLoadMap sm = g1_open_srs_map(log_n), hm = g1_open_slice_map(log_n);
+    const G1NttLoadMap sm = g1_coset_srs_map(log_n, 0, 0), hm = g1_coset_slice_map(log_n, 0);  // all openings: log_l = 0
     for (uint64_t j = 0; j < 2 * n; j++) printf("s %llu %lld\n", (unsigned long long)j, (long long)g1_ntt_load_source(sm, j));
     for (uint64_t i = 0; i < n; i++) printf("h %llu %lld\n", (unsigned long long)i, (long long)g1_ntt_load_source(hm, i));
     for (uint64_t len = 1; len <= n; len++)
-        for (uint64_t t = 0; t < 2 * n; t++) printf("g %llu %llu %lld\n", (unsigned long long)len, (unsigned long long)t, (long long)g1_open_coeff_source(len, t));
+        for (uint64_t t = 0; t < 2 * n; t++)
+            printf("g %llu %llu %lld\n", (unsigned long long)len, (unsigned long long)t, (long long)g1_coset_coeff_source(log_n, 0, len, 0, t));
 }
 
 int main(int argc, char** argv) {

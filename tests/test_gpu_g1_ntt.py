@@ -261,6 +261,28 @@ def test_open_all_against_the_trapdoor_and_kzg_open(zkp, orc, n):
             assert inf == got[1][m] and np.array_equal(xy, got[0][m]) and np.array_equal(e, ev[m]), (n, length, m)
 
 
+def test_open_all_two_launches(zkp, orc):
+    """n = 2^18: the smallest n whose 2n pointwise products take two launches of G1_NTT_LAUNCH = 2^18 lanes.  The evaluations are compared
+    in full with the oracle's Fr transform; proofs 0, 1, n/2 - 1, n/2, n - 2, n - 1 limb for limb with zkp_kzg_open at w^m -- every proof
+    depends on all 2n products through the inverse transform, so a sample checks both launches."""
+    log_n = 18
+    n = 1 << log_n
+    h = zkp.G1Bases.from_host(zkp.srs_g1(orc.fr_from_ints([SECRET])[0], n - 1))
+    op = zkp.KzgOpener(h, log_n)  # about 0.4 GB, released below
+    try:
+        coeffs = orc.rand_fr(0x61B8, n)
+        got, ev = op.open_all(coeffs)
+    finally:
+        op.close()
+    assert np.array_equal(ev, orc.ntt_fr(coeffs))
+    w = root(orc, log_n)
+    for m in (0, 1, n // 2 - 1, n // 2, n - 2, n - 1):
+        z = orc.fr_from_ints([pow(w, m, R)])[0]
+        (xy, inf), e = zkp.kzg_open(h, coeffs, z)
+        assert inf == got[1][m] and np.array_equal(xy, got[0][m]) and np.array_equal(e, ev[m]), m
+    h.close()
+
+
 def test_open_all_proof_verifies(zkp, orc):
     import pairing_model as PairM
     from test_pairing_cpu import g2_from_ints

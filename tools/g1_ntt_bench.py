@@ -1,5 +1,5 @@
 """The transform over G1 points and what is built on it, one process, device events around each call, median of three after a
-warm-up of the same shape; the shader clock of the library's multiply-add probe is printed before and after.  Not part of bench.py.
+warm-up of the same shape, with the spread (max - min) / median of the three in the transform, opener and coset tables; the shader clock of the library's multiply-add probe is printed before and after.  Not part of bench.py.
   - zkp_g1_ntt_dev at 2^12 / 2^16 / 2^20
   - zkp_g1_bases_lagrange at 2^16 / 2^20
   - zkp_kzg_opener_create and zkp_kzg_open_all_dev at n = 2^10 / 2^12 / 2^14 / 2^16, next to what the library offered for the same
@@ -57,8 +57,8 @@ def event_ms(fn, reps=3):
     return statistics.median(event_times(fn, reps))
 
 
-def host_ms(fn, reps=3):
-    """median host time of a call that synchronises before it returns (handle and opener creation)"""
+def host_times(fn, reps=3):
+    """host times of `reps` calls that synchronise before they return (handle and opener creation), after one warm-up"""
     out = []
     for _ in range(reps + 1):
         torch.cuda.synchronize()
@@ -66,7 +66,18 @@ def host_ms(fn, reps=3):
         h = fn()
         out.append((time.perf_counter() - t0) * 1e3)
         h.close()
-    return statistics.median(out[1:])
+    return out[1:]
+
+
+def host_ms(fn, reps=3):
+    """their median"""
+    return statistics.median(host_times(fn, reps))
+
+
+def med_spread(ts):
+    """'median ms (spread %)' of the timed calls, the spread being (max - min) / median"""
+    med = statistics.median(ts)
+    return f"{med:.2f} ms ({(max(ts) - min(ts)) / med * 100:.1f} %)"
 
 
 def clock():
@@ -83,14 +94,14 @@ def random_points(n, seed):
 
 print(f"shader clock of the multiply-add probe before: {clock()}\n")
 if sizes(args.ntt):
-    print("| points | zkp_g1_ntt_dev forward | inverse | us per butterfly multiplication (n/2 log n of them) |")
+    print("| points | zkp_g1_ntt_dev forward, median of 3 (spread) | inverse | us per butterfly multiplication (n/2 log n of them) |")
     print("|---|---|---|---|")
     for ln in sizes(args.ntt):
         n = 1 << ln
         pts, inf = random_points(n, 1), torch.zeros(n, dtype=torch.uint8, device=dev)
-        fwd = event_ms(lambda: zkp.g1_ntt_dev(pts, inf, ln))
-        inv = event_ms(lambda: zkp.g1_ntt_dev(pts, inf, ln, inverse=True))
-        print(f"| 2^{ln} | {fwd:.1f} ms | {inv:.1f} ms | {fwd * 1e3 / (n // 2 * ln):.3f} |", flush=True)
+        fwd = event_times(lambda: zkp.g1_ntt_dev(pts, inf, ln))
+        inv = event_times(lambda: zkp.g1_ntt_dev(pts, inf, ln, inverse=True))
+        print(f"| 2^{ln} | {med_spread(fwd)} | {med_spread(inv)} | {statistics.median(fwd) * 1e3 / (n // 2 * ln):.3f} |", flush=True)
         del pts
 
 if sizes(args.lagrange):
@@ -102,18 +113,20 @@ if sizes(args.lagrange):
         srs.close()
 
 if sizes(args.open):
-    print("\n| n | zkp_kzg_opener_create | zkp_kzg_open_all_dev | zkp_kzg_open, one call (median of 64) | ... x n (extrapolated) | open_all / (open x n) |")
+    print("\n| n | zkp_kzg_opener_create, median of 3 (spread) | zkp_kzg_open_all_dev, median of 3 (spread) | zkp_kzg_open, one call (median of 64) | "
+          "... x n (extrapolated) | open_all / (open x n) |")
     print("|---|---|---|---|---|---|")
     for ln in sizes(args.open):
         n = 1 << ln
         srs = zkp.G1Bases.from_host(zkp.srs_g1(SECRET, n))
-        t_create = host_ms(lambda: zkp.KzgOpener(srs, ln))
+        ts_create = host_times(lambda: zkp.KzgOpener(srs, ln))
         op = zkp.KzgOpener(srs, ln)
         coeffs = bench.rand_fr_tensor(torch, n, 3, dev)
         out_xy = torch.zeros(n * 12, dtype=torch.int64, device=dev)
         out_inf = torch.zeros(n, dtype=torch.uint8, device=dev)
         out_ev = torch.zeros(n * 4, dtype=torch.int64, device=dev)
-        t_all = event_ms(lambda: op.open_all_dev(coeffs, n, out_xy, out_inf, out_ev))
+        ts_all = event_times(lambda: op.open_all_dev(coeffs, n, out_xy, out_inf, out_ev))
+        t_all = statistics.median(ts_all)
         srs.precompute(0)  # what a KzgScheme does to its SRS before it opens
         host_coeffs = coeffs.cpu().numpy().view(np.uint64).reshape(n, 4)
         z = bench.fr_mont(list(range(2, 66)))
@@ -124,7 +137,7 @@ if sizes(args.open):
             zkp.kzg_open(srs, host_coeffs, z[k])
             one.append((time.perf_counter() - t0) * 1e3)
         t_one = statistics.median(one)
-        print(f"| 2^{ln} | {t_create:.1f} ms | {t_all:.1f} ms | {t_one:.3f} ms | {t_one * n / 1e3:.2f} s | {t_all / (t_one * n):.3f} |", flush=True)
+        print(f"| 2^{ln} | {med_spread(ts_create)} | {med_spread(ts_all)} | {t_one:.3f} ms | {t_one * n / 1e3:.2f} s | {t_all / (t_one * n):.3f} |", flush=True)
         op.close()
         srs.close()
 

@@ -89,6 +89,17 @@ int hip_fail(hipError_t e, const std::string& what) {
         if (r_ != ZKP_OK) return r_; \
     } while (0)
 
+// The current device's free and total bytes as it reports them now (zeros where it does not), and the ZKP_E_NOMEM that quotes them
+struct DevFree {
+    size_t free_b = 0, total_b = 0;
+    DevFree() {
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
+    }
+    int refuse(const std::string& what, const std::string& tail = "") const {
+        return fail(ZKP_E_NOMEM, what + ", " + std::to_string(free_b) + " of " + std::to_string(total_b) + " bytes free on the device" + tail);
+    }
+};
+
 #include "host_threads.hpp"  // HostPool (host_pool()), Uploader (uploader(slot)), DeviceWorkers, PhaseBarrier
 #include "dev_res.hpp"       // DevBuf, TypedBuf, PinnedBuf, Stream, Event
 static_assert(ZKP_HOST_THREADS_E_DEVICE == ZKP_E_DEVICE && ZKP_HOST_THREADS_OK == ZKP_OK, "host_threads.hpp error codes");
@@ -731,17 +742,14 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool glv, bool check_o
     {   // The expansion is `planes` x the SRS (13 x at 20 bits, 12 x at 22: 103 GB for 2^26 points, and a 2^27 SRS no longer fits one
         // device; split planes: 7 x and 6 x).  Say so with the numbers instead of a bare allocation failure; the handle stays usable unexpanded (per-window MSM).
         const size_t need = 128 * (size_t)planes * b->n;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
-        const size_t budget = std::min<size_t>(free_b ? free_b : ~(size_t)0, (size_t)knob_int(KNOB_SRS_EXPAND_MAX_BYTES));
+        const DevFree mem;
+        const size_t budget = std::min<size_t>(mem.free_b ? mem.free_b : ~(size_t)0, (size_t)knob_int(KNOB_SRS_EXPAND_MAX_BYTES));
         auto too_large = [&](const char* why) {
-            return fail(ZKP_E_NOMEM, "SRS expansion does not fit (" + std::string(why) + "): " + std::to_string(planes) + " planes x " +
-                                         std::to_string(b->n) + " points x 128 B = " + std::to_string(need) + " bytes, " +
-                                         std::to_string(free_b) + " of " + std::to_string(total_b) +
-                                         " bytes free on the device; the bases stay unexpanded (per-window MSM), or shard the SRS over "
-                                         "more devices (zkp_init_devices)");
+            return mem.refuse("SRS expansion does not fit (" + std::string(why) + "): " + std::to_string(planes) + " planes x " +
+                                  std::to_string(b->n) + " points x 128 B = " + std::to_string(need) + " bytes",
+                              "; the bases stay unexpanded (per-window MSM), or shard the SRS over more devices (zkp_init_devices)");
         };
-        if (need > budget) return too_large(need > free_b && free_b ? "device memory" : "ZKP_SRS_EXPAND_MAX_BYTES");
+        if (need > budget) return too_large(need > mem.free_b && mem.free_b ? "device memory" : "ZKP_SRS_EXPAND_MAX_BYTES");
         if (check_only) return ZKP_OK;
         if (p.ensure(need) != ZKP_OK) {
             (void)hipGetLastError();

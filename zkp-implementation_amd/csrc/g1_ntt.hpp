@@ -6,10 +6,10 @@
 // layout of the bucket arrays: chunk q of point e at ws[q * capacity + e].  The kernels:
 //   g1_ntt_load_kernel<RAW>   96-byte ABI points or the 128-byte points of a handle -> the workspace, bit-reversed when asked
 //   g1_ntt_butterfly_kernel   one lane per butterfly of a stage: (a, b) <- (a + [w]b, a - [w]b)
-//   g1_ntt_mul_kernel         one lane per point: P_i <- [c k_i] P_i (the pointwise step, zkp_g1_scale_dev, the n^-1 of an inverse)
+//   g1_ntt_mul_kernel         one lane per point, in place: P_i <- [k_i] P_i (zkp_g1_scale_dev, the n^-1 of an inverse)
 //   g1_ntt_slice_kernel       a run of points of one workspace into another, identities behind it
 //   g1_ntt_store_kernel<RAW>  the workspace -> affine, one safegcd inversion per lane
-// and for the coset openings (zkp_kzg_open_cosets), at the end of this file:
+// and for the openers (zkp_kzg_open_cosets and, as its l = 1 case, zkp_kzg_open_all), at the end of this file:
 //   g1_ntt_load_slices_kernel the points of a handle -> the l slices of an opener, each bit-reversed
 //   g1_ntt_gather_kernel      the strided coefficients -> the l rows of scalars
 //   g1_ntt_split_kernel       every transformed scalar, times (2r)^-1, -> its two endomorphism halves
@@ -156,22 +156,18 @@ __global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_butterfly_kernel(uint4*
     }
 }
 
-// P_i <- [c k_i] P_i for i in [first, first + count): P_i at src[i], the product at dst[bitrev(i, rev_log)] (rev_log = 0: dst[i]; in
-// place only then).  k_i = scalars[i * scalar_step] (Montgomery; step 0: one constant), c = *factor when given.
-__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mul_kernel(const uint4* src, uint64_t scap, uint4* dst, uint64_t dcap,
-                                                                    uint32_t rev_log, const Fr* __restrict__ scalars, uint32_t scalar_step,
-                                                                    const Fr* __restrict__ factor, uint64_t first, uint32_t count,
-                                                                    uint4* table, uint64_t tcap) {
+// P_i <- [k_i] P_i in place for i in [first, first + count): P_i at ws[i], k_i = scalars[i * scalar_step] (Montgomery; step 0: one
+// constant)
+__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mul_kernel(uint4* ws, uint64_t cap, const Fr* __restrict__ scalars, uint32_t scalar_step,
+                                                                    uint64_t first, uint32_t count, uint4* table, uint64_t tcap) {
     const uint32_t lane = blockIdx.x * G1_NTT_THREADS + threadIdx.x;
     if (lane >= count) return;
     const uint64_t i = first + lane;
-    Fr k = scalars[i * scalar_step];
-    if (factor) k = k * *factor;
-    k = from_mont(k);
-    const bool p_inf = Fq28::load_s(src + i + 8 * scap, scap).all_zero();
+    const Fr k = from_mont(scalars[i * scalar_step]);
+    const bool p_inf = Fq28::load_s(ws + i + 8 * cap, cap).all_zero();
     X28 r = X28::infinity();
-    if (!p_inf && !k.is_zero()) r = g1_28_mul_glv(k.l, src + i, scap, table + lane, tcap);
-    r.store_s(dst + (rev_log ? g1_ntt_bitrev((uint32_t)i, rev_log) : i), dcap);
+    if (!p_inf && !k.is_zero()) r = g1_28_mul_glv(k.l, ws + i, cap, table + lane, tcap);
+    r.store_s(ws + i, cap);
 }
 
 // slot i of `map` <- src[source(i)], the identity where there is none
@@ -214,8 +210,8 @@ __global__ __launch_bounds__(MSM_THREADS) void g1_ntt_store_kernel(const uint4* 
     if (out_inf) out_inf[i] = inf ? 1 : 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- coset openings
-// (zkp_kzg_open_cosets: g1_ntt_plan.hpp has the construction and every index below)
+// ---------------------------------------------------------------------------------------------------------------- the openers
+// (zkp_kzg_open_cosets, zkp_kzg_open_all at l = 1: g1_ntt_plan.hpp has the construction and every index below)
 
 // the l slices of a handle's points (128 bytes each, plane 0 of an expansion) into one workspace of 2n: slot i in [first, ...) is slot
 // j = i mod 2r of slice b = i / 2r (g1_coset_srs_map), stored bit-reversed within its slice

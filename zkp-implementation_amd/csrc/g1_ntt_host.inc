@@ -1,5 +1,5 @@
-// g1_ntt_host.inc -- zkp_g1_scale_dev, zkp_g1_ntt*, zkp_g1_bases_lagrange and the all-openings entries zkp_kzg_opener_* /
-// zkp_kzg_open_all*, the coset openings zkp_kzg_opener_create_cosets / zkp_kzg_open_cosets* and their verifier zkp_kzg_verify_coset
+// g1_ntt_host.inc -- zkp_g1_scale_dev, zkp_g1_ntt*, zkp_g1_bases_lagrange, the openers zkp_kzg_opener_* with zkp_kzg_open_cosets* and
+// zkp_kzg_open_all* (one construction: all openings are the cosets of one point, log_l = 0) and the verifier zkp_kzg_verify_coset
 // (included at the end of api.hip, after verify_host.inc).  The kernels are in g1_ntt.hpp, every index and size in g1_ntt_plan.hpp.
 
 namespace {
@@ -54,49 +54,50 @@ unsigned g1_ntt_blocks(uint64_t lanes, unsigned threads) { return (unsigned)((la
 int g1_ntt_workspace(size_t need, const char* what, void** out) {
     DevBuf& tmp = ctx().tmp;
     if (need > tmp.cap) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
-        const bool fits = !total_b || need <= free_b + tmp.cap;
+        const DevFree mem;
+        const bool fits = !mem.total_b || need <= mem.free_b + tmp.cap;
         if (!fits || tmp.grow(need) != hipSuccess) {
             (void)hipGetLastError();
             tmp.release();
-            return fail(ZKP_E_NOMEM, std::string(what) + ": the workspace of " + std::to_string(need) + " bytes does not fit, " +
-                                         std::to_string(free_b) + " of " + std::to_string(total_b) + " bytes free on the device");
+            return mem.refuse(std::string(what) + ": the workspace of " + std::to_string(need) + " bytes does not fit");
         }
     }
     *out = tmp.p;
     return ZKP_OK;
 }
 
-// (both in launches of at most G1_NTT_IO_LAUNCH lanes, as the validation kernels)
-template <bool RAW>
-int g1_ntt_load(const void* d_pts, const uint8_t* d_inf, const G1NttLoadMap& map, const G1NttVec& v, hipStream_t st) {
-    for (uint64_t first = 0; first < map.count; first += G1_NTT_IO_LAUNCH) {
-        const uint64_t cnt = std::min<uint64_t>(G1_NTT_IO_LAUNCH, map.count - first);
-        hipLaunchKernelGGL(g1_ntt_load_kernel<RAW>, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st,
-                           static_cast<const uint4*>(d_pts), d_inf, map, first, v.pts, v.cap);
-        HIPCHK(hipGetLastError());
-    }
-    return ZKP_OK;
-}
-template <bool RAW>
-int g1_ntt_store(const G1NttVec& v, uint64_t n, void* d_out, uint8_t* d_out_inf, hipStream_t st) {
-    for (uint64_t first = 0; first < n; first += G1_NTT_IO_LAUNCH) {
-        const uint64_t cnt = std::min<uint64_t>(G1_NTT_IO_LAUNCH, n - first);
-        hipLaunchKernelGGL(g1_ntt_store_kernel<RAW>, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st, v.pts, v.cap, first,
-                           first + cnt, static_cast<uint4*>(d_out), d_out_inf);
+// launch(first, count) over the lanes [0, total) in pieces of at most G1_NTT_IO_LAUNCH, as the validation kernels: the load, store,
+// gather, split and fold kernels, which take `first` and bound their own lanes
+template <class Launch>
+int g1_ntt_io_launches(uint64_t total, Launch&& launch) {
+    for (uint64_t first = 0; first < total; first += G1_NTT_IO_LAUNCH) {
+        launch(first, std::min<uint64_t>(G1_NTT_IO_LAUNCH, total - first));
         HIPCHK(hipGetLastError());
     }
     return ZKP_OK;
 }
 
-// dst[bitrev(i)] (or dst[i]) <- [c k_i] src[i] for i < n, in launches of at most G1_NTT_LAUNCH lanes; the table is v's
-int g1_ntt_mul(const uint4* src, uint64_t scap, const G1NttVec& v, unsigned rev_log, const Fr* d_scalars, unsigned scalar_step,
-               const Fr* d_factor, uint64_t n, hipStream_t st) {
+template <bool RAW>
+int g1_ntt_load(const void* d_pts, const uint8_t* d_inf, const G1NttLoadMap& map, const G1NttVec& v, hipStream_t st) {
+    return g1_ntt_io_launches(map.count, [&](uint64_t first, uint64_t cnt) {
+        hipLaunchKernelGGL(g1_ntt_load_kernel<RAW>, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st,
+                           static_cast<const uint4*>(d_pts), d_inf, map, first, v.pts, v.cap);
+    });
+}
+template <bool RAW>
+int g1_ntt_store(const G1NttVec& v, uint64_t n, void* d_out, uint8_t* d_out_inf, hipStream_t st) {
+    return g1_ntt_io_launches(n, [&](uint64_t first, uint64_t cnt) {
+        hipLaunchKernelGGL(g1_ntt_store_kernel<RAW>, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st, v.pts, v.cap, first,
+                           first + cnt, static_cast<uint4*>(d_out), d_out_inf);
+    });
+}
+
+// v[i] <- [k_i] v[i] for i < n, in launches of at most G1_NTT_LAUNCH lanes; k_i = d_scalars[i * scalar_step]
+int g1_ntt_mul(const G1NttVec& v, const Fr* d_scalars, unsigned scalar_step, uint64_t n, hipStream_t st) {
     for (uint64_t k = 0; k < g1_ntt_launches(n); k++) {
         const uint64_t cnt = g1_ntt_launch_lanes(n, k);
-        hipLaunchKernelGGL(g1_ntt_mul_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, src, scap, v.pts, v.cap,
-                           (uint32_t)rev_log, d_scalars, (uint32_t)scalar_step, d_factor, k * G1_NTT_LAUNCH, (uint32_t)cnt, v.table, v.tcap);
+        hipLaunchKernelGGL(g1_ntt_mul_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, v.pts, v.cap, d_scalars,
+                           (uint32_t)scalar_step, k * G1_NTT_LAUNCH, (uint32_t)cnt, v.table, v.tcap);
         HIPCHK(hipGetLastError());
     }
     return ZKP_OK;
@@ -117,7 +118,7 @@ int g1_ntt_stages(const G1NttVec& v, unsigned log_n, int inverse, bool scale, hi
     const uint64_t together = std::max<uint64_t>(1, std::min<uint64_t>({slices, std::min(G1_NTT_LAUNCH, v.tcap) / lanes, 65535}));
     for (unsigned s = 0; s < log_n; s++) {
         const bool last_scaled = scale && s == log_n - 1;
-        if (last_scaled) ZCHK(g1_ntt_mul(v.pts, v.cap, v, 0, row + G1_NTT_TW_NINV, 0, nullptr, lanes, st));  // the left operands
+        if (last_scaled) ZCHK(g1_ntt_mul(v, row + G1_NTT_TW_NINV, 0, lanes, st));  // the left operands
         for (uint64_t y = 0; y < slices; y += together)
             for (uint64_t k = 0; k < g1_ntt_launches(lanes); k++) {
                 const uint64_t cnt = g1_ntt_launch_lanes(lanes, k);
@@ -146,10 +147,10 @@ const char* const kShardedG1Ntt = "bases are sharded over several devices: a tra
 
 struct zkp_kzg_opener {
     unsigned log_n = 0;
-    unsigned log_l = 0;      // > 0: made by zkp_kzg_opener_create_cosets, one proof per coset of 2^log_l points
-    unsigned group_log = 0;  // ... whose lanes sum 2^group_log terms (g1_coset_mac)
+    unsigned log_l = 0;      // one proof per coset of 2^log_l points; 0: all n openings
+    unsigned group_log = 0;  // a lane of the multiply-accumulate pass sums 2^group_log terms (g1_coset_mac; one at most when l = 1)
     int slot = 0, device = 0;
-    DevBuf srs_hat;  // NTT_2n of the reversed SRS points (cosets: the l transformed slices): depends on the SRS, n and l only
+    DevBuf srs_hat;  // the l slices of the reversed SRS points, each transformed (NTT_2r): depends on the SRS, n and l only
     DevBuf work;     // (the partial sums,) u, the slice h, the scalars g and the lanes' table of one call (entries of a slot are serialised)
 };
 
@@ -172,7 +173,7 @@ int zkp_g1_scale_dev(void* d_xy, uint8_t* d_is_inf, const void* d_scalars, size_
         char* xy = static_cast<char*>(d_xy) + 96 * off;
         uint8_t* inf = d_is_inf ? d_is_inf + off : nullptr;
         ZCHK(g1_ntt_load<true>(xy, inf, G1NttLoadMap{cnt, cnt, 0, 1, 0}, v, st));
-        ZCHK(g1_ntt_mul(v.pts, v.cap, v, 0, static_cast<const Fr*>(d_scalars) + off, 1, nullptr, cnt, st));
+        ZCHK(g1_ntt_mul(v, static_cast<const Fr*>(d_scalars) + off, 1, cnt, st));
         ZCHK(g1_ntt_store<true>(v, cnt, xy, inf, st));
     }
     return ZKP_OK;
@@ -235,47 +236,6 @@ int zkp_g1_bases_lagrange(const zkp_bases* srs, unsigned log_n, zkp_bases** out)
     return ZKP_OK;
 } ZKP_CATCH_INT
 
-int zkp_kzg_opener_create(const zkp_bases* srs, unsigned log_n, zkp_kzg_opener** out) try {
-    if (!srs || !out) return fail(ZKP_E_ARG, "null argument");
-    if (log_n < 1 || log_n + 1 > G1_NTT_MAX_LOG) return fail(ZKP_E_ARG, "log_n of an opener must be 1 .. 23");
-    if (!srs->shards.empty()) return fail(ZKP_E_ARG, kShardedG1Ntt);
-    const size_t n = (size_t)1 << log_n;
-    if (srs->n < n - 1) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_n - 1 points");
-    CTX_ENTER(srs->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
-    WsOrder ord(st);
-    const G1OpenSizes sz = g1_open_sizes(log_n);
-    std::unique_ptr<zkp_kzg_opener, void (*)(zkp_kzg_opener*)> o(new (std::nothrow) zkp_kzg_opener(), zkp_kzg_opener_destroy);
-    if (!o) return fail(ZKP_E_NOMEM, "host allocation failed");
-    o->log_n = log_n;
-    o->slot = ctx().slot;
-    o->device = ctx().device;
-    if (o->srs_hat.grow(sz.srs_hat) != hipSuccess || o->work.grow(sz.total - sz.srs_hat) != hipSuccess) {
-        (void)hipGetLastError();
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
-        return fail(ZKP_E_NOMEM, "zkp_kzg_opener_create: the workspaces of " + std::to_string(sz.total) + " bytes do not fit, " +
-                                     std::to_string(free_b) + " of " + std::to_string(total_b) + " bytes free on the device");
-    }
-    // the table of this one transform sits where the calls keep theirs: at the end of `work`
-    const G1NttVec v{static_cast<uint4*>(o->srs_hat.p), 2 * (uint64_t)n,
-                     reinterpret_cast<uint4*>(static_cast<char*>(o->work.p) + sz.work + sz.slice + sz.scalars), sz.table / G1_NTT_POINT_BYTES};
-    ZCHK(g1_ntt_load<false>(srs->d_xy.p, srs->d_inf.get(), g1_open_srs_map(log_n), v, st));
-    ZCHK(g1_ntt_stages(v, log_n + 1, 0, false, st));
-    {   // Everything a call builds on first use is built here, so that zkp_kzg_open_all_dev neither allocates nor waits: the plans, tables
-        // and scratch of the two Fr transforms (over the zeroed scalar area) and the constants of the two other point transforms
-        Fr* g = reinterpret_cast<Fr*>(static_cast<char*>(o->work.p) + sz.work + sz.slice);
-        const Fr* row = nullptr;
-        HIPCHK(hipMemsetAsync(g, 0, sz.scalars, st));
-        ZCHK(run_ntt<Fr>(g, log_n + 1, 1, 0, nullptr, st));
-        ZCHK(run_ntt<Fr>(g, log_n, 1, 0, nullptr, st));
-        ZCHK(g1_ntt_twiddle_row(log_n + 1, 1, st, &row));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    *out = o.release();
-    return ZKP_OK;
-} ZKP_CATCH_INT
-
 void zkp_kzg_opener_destroy(zkp_kzg_opener* o) {
     if (!o) return;
     DeviceRestore restore;
@@ -288,42 +248,7 @@ void zkp_kzg_opener_destroy(zkp_kzg_opener* o) {
 
 namespace {
 
-// everything on the device, on `st`; the caller is inside the opener's slot
-int kzg_open_all_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
-                        hipStream_t st) {
-    const unsigned log_n = o->log_n;
-    const uint64_t n = (uint64_t)1 << log_n;
-    const G1OpenSizes sz = g1_open_sizes(log_n);
-    char* base = static_cast<char*>(o->work.p);
-    uint4* table = reinterpret_cast<uint4*>(base + sz.work + sz.slice + sz.scalars);
-    const G1NttVec u{reinterpret_cast<uint4*>(base), 2 * n, table, sz.table / G1_NTT_POINT_BYTES};
-    const G1NttVec h{reinterpret_cast<uint4*>(base + sz.work), n, table, sz.table / G1_NTT_POINT_BYTES};
-    Fr* g = reinterpret_cast<Fr*>(base + sz.work + sz.slice);
-    // g_t = f_{t+1}: one run of the coefficients (g1_open_coeff_run), zeros behind it; transformed
-    const G1OpenCoeffRun run = g1_open_coeff_run(len);
-    HIPCHK(hipMemsetAsync(g, 0, sz.scalars, st));
-    if (run.count) HIPCHK(hipMemcpyAsync(g, static_cast<const char*>(d_coeffs) + 32 * run.first, 32 * run.count, hipMemcpyDeviceToDevice, st));
-    ZCHK(run_ntt<Fr>(g, log_n + 1, 1, 0, nullptr, st));
-    // u = iNTT_2n(srs_hat . g), the (2n)^-1 folded into the pointwise scalars; loaded bit-reversed for the stages
-    const Fr* row = nullptr;
-    ZCHK(g1_ntt_twiddle_row(log_n + 1, 1, st, &row));
-    ZCHK(g1_ntt_mul(static_cast<const uint4*>(o->srs_hat.p), 2 * n, u, log_n + 1, g, 1, row + G1_NTT_TW_NINV, 2 * n, st));
-    ZCHK(g1_ntt_stages(u, log_n + 1, 1, false, st));
-    // the proofs: NTT_n of the slice h
-    hipLaunchKernelGGL(g1_ntt_slice_kernel, dim3(g1_ntt_blocks(n, MSM_THREADS)), dim3(MSM_THREADS), 0, st, u.pts, u.cap, g1_open_slice_map(log_n),
-                       h.pts, h.cap);
-    HIPCHK(hipGetLastError());
-    ZCHK(g1_ntt_stages(h, log_n, 0, false, st));
-    ZCHK(g1_ntt_store<true>(h, n, d_out_xy, d_out_is_inf, st));
-    if (d_out_evals) {  // f on the domain
-        HIPCHK(hipMemsetAsync(d_out_evals, 0, 32 * n, st));
-        HIPCHK(hipMemcpyAsync(d_out_evals, d_coeffs, 32 * len, hipMemcpyDeviceToDevice, st));
-        ZCHK(run_ntt<Fr>(static_cast<Fr*>(d_out_evals), log_n, 1, 0, nullptr, st));
-    }
-    return ZKP_OK;
-}
-
-// (cosets: the call is one of zkp_kzg_open_cosets*, which take either kind of opener)
+// (cosets: the call is one of zkp_kzg_open_cosets*, which take an opener of any log_l; zkp_kzg_open_all* one of log_l = 0 only)
 int kzg_open_all_args(const zkp_kzg_opener* o, const void* coeffs, size_t len, const void* out_xy, const void* out_is_inf, bool cosets = false) {
     if (!o || !coeffs || !out_xy || !out_is_inf) return fail(ZKP_E_ARG, "null argument");
     if (o->log_l && !cosets) return fail(ZKP_E_ARG, "the opener was made for cosets (zkp_kzg_opener_create_cosets): zkp_kzg_open_cosets opens with it");
@@ -340,7 +265,7 @@ int coset_fr_rows(Fr* g, unsigned log_m, uint64_t rows, hipStream_t st) {
     return ZKP_OK;
 }
 
-// where the pieces of a coset opener's `work` begin (g1_coset_sizes)
+// where the pieces of an opener's `work` begin (g1_coset_sizes)
 struct CosetWork {
     G1CosetSizes sz;
     G1CosetMac mac;
@@ -362,28 +287,28 @@ CosetWork coset_work(const zkp_kzg_opener* o) {
     return w;
 }
 
-// everything on the device, on `st`; the caller is inside the opener's slot
-int kzg_open_cosets_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
-                           hipStream_t st) {
+// One call of an opener, log_l = 0 (all openings, r = n) as any other: everything on the device, on `st`; the caller is inside the
+// opener's slot
+int kzg_open_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
+                    hipStream_t st) {
     const unsigned log_n = o->log_n, log_l = o->log_l, log_r = log_n - log_l, log_m = log_r + 1;
     const uint64_t n = (uint64_t)1 << log_n, r = (uint64_t)1 << log_r, l = (uint64_t)1 << log_l;
     const CosetWork w = coset_work(o);
     const G1NttVec u{w.u, 2 * r, w.table, w.tcap}, h{w.h, r, w.table, w.tcap};
-    // the l rows of g in one launch per G1_NTT_IO_LAUNCH slots, transformed as one batch; then every scalar times (2r)^-1, split
+    // the l rows of g, transformed as one batch; then every scalar times (2r)^-1, split
     const Fr* row = nullptr;
     ZCHK(g1_ntt_twiddle_row(log_m, 1, st, &row));
-    for (uint64_t first = 0; first < 2 * n; first += G1_NTT_IO_LAUNCH) {
-        hipLaunchKernelGGL(g1_ntt_gather_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, 2 * n - first), MSM_THREADS)),
-                           dim3(MSM_THREADS), 0, st, static_cast<const Fr*>(d_coeffs), (uint64_t)len, (uint32_t)log_n, (uint32_t)log_l, first, w.g);
-        HIPCHK(hipGetLastError());
-    }
+    ZCHK(g1_ntt_io_launches(2 * n, [&](uint64_t first, uint64_t cnt) {
+        hipLaunchKernelGGL(g1_ntt_gather_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st,
+                           static_cast<const Fr*>(d_coeffs), (uint64_t)len, (uint32_t)log_n, (uint32_t)log_l, first, w.g);
+    }));
     ZCHK(coset_fr_rows(w.g, log_m, l, st));
-    for (uint64_t first = 0; first < 2 * n; first += G1_NTT_IO_LAUNCH) {
-        hipLaunchKernelGGL(g1_ntt_split_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, 2 * n - first), MSM_THREADS)),
-                           dim3(MSM_THREADS), 0, st, w.g, row + G1_NTT_TW_NINV, first, 2 * n);
-        HIPCHK(hipGetLastError());
-    }
-    // U_k = sum_b [g^_k] S^_k: the lanes' groups, then the fold of the partial sums into u (bit-reversed for the stages)
+    ZCHK(g1_ntt_io_launches(2 * n, [&](uint64_t first, uint64_t cnt) {
+        hipLaunchKernelGGL(g1_ntt_split_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st, w.g, row + G1_NTT_TW_NINV,
+                           first, 2 * n);
+    }));
+    // U_k = sum_b [g^_k] S^_k: the lanes' groups, then the fold of the partial sums into u (bit-reversed for the stages); one group per
+    // output (always so at l = 1) writes u itself
     const bool folded = w.mac.groups > 1;
     for (uint64_t k = 0; k < g1_coset_mac_launches(w.mac); k++) {
         const uint64_t cnt = g1_coset_mac_launch_lanes(w.mac, k);
@@ -395,11 +320,10 @@ int kzg_open_cosets_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t
     }
     for (unsigned i = 0; i < g1_coset_fold_steps(w.mac); i++) {
         const G1CosetFoldStep f = g1_coset_fold_step(log_n, log_l, w.mac, i);
-        for (uint64_t first = 0; first < f.lanes; first += G1_NTT_IO_LAUNCH) {
-            hipLaunchKernelGGL(g1_ntt_fold_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, f.lanes - first), G1_NTT_THREADS)),
-                               dim3(G1_NTT_THREADS), 0, st, w.partial, w.mac.lanes, f.lanes, first, u.pts, u.cap, f.last ? (uint32_t)log_m : 0u);
-            HIPCHK(hipGetLastError());
-        }
+        ZCHK(g1_ntt_io_launches(f.lanes, [&](uint64_t first, uint64_t cnt) {
+            hipLaunchKernelGGL(g1_ntt_fold_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, w.partial, w.mac.lanes,
+                               f.lanes, first, u.pts, u.cap, f.last ? (uint32_t)log_m : 0u);
+        }));
     }
     ZCHK(g1_ntt_stages(u, log_m, 1, false, st));
     // the proofs: NTT_r of the slice h
@@ -416,50 +340,46 @@ int kzg_open_cosets_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t
     return ZKP_OK;
 }
 
+// the device entries: nothing is allocated, nothing waited for
+int kzg_open_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
+                 void* stream, bool cosets) {
+    ZCHK(kzg_open_all_args(o, d_coeffs, len, d_out_xy, d_out_is_inf, cosets));
+    CTX_ENTER(o->slot);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    return kzg_open_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st);
+}
+
+// the host entries (`what`: the entry's name), r = n / l proofs out
+int kzg_open_host(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, uint64_t* out_xy, uint8_t* out_is_inf, uint64_t* out_evals,
+                  const char* what, bool cosets) {
+    ZCHK(kzg_open_all_args(o, coeffs, len, out_xy, out_is_inf, cosets));
+    CTX_ENTER(o->slot);
+    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    WsOrder ord(st);
+    const size_t n = (size_t)1 << o->log_n, r = n >> o->log_l;
+    void* ws = nullptr;  // coefficients | evaluations | points | flags
+    ZCHK(g1_ntt_workspace(32 * len + 32 * n + 96 * r + r, what, &ws));
+    char* d_coeffs = static_cast<char*>(ws);
+    char* d_evals = d_coeffs + 32 * len;
+    char* d_xy = d_evals + 32 * n;
+    uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * r);
+    HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 32 * len, hipMemcpyHostToDevice, st));
+    ZCHK(kzg_open_locked(o, d_coeffs, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
+    HIPCHK(hipMemcpyAsync(out_xy, d_xy, 96 * r, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, r, hipMemcpyDeviceToHost, st));
+    if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-int zkp_kzg_open_all_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
-                         void* stream) try {
-    ZCHK(kzg_open_all_args(o, d_coeffs, len, d_out_xy, d_out_is_inf));
-    CTX_ENTER(o->slot);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    WsOrder ord(st);
-    return kzg_open_all_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st);
-} ZKP_CATCH_INT
-
-int zkp_kzg_open_all(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, uint64_t* out_xy, uint8_t* out_is_inf,
-                     uint64_t* out_evals) try {
-    ZCHK(kzg_open_all_args(o, coeffs, len, out_xy, out_is_inf));
-    CTX_ENTER(o->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
-    WsOrder ord(st);
-    const size_t n = (size_t)1 << o->log_n;
-    void* ws = nullptr;  // coefficients | evaluations | points | flags
-    ZCHK(g1_ntt_workspace(32 * len + 32 * n + 96 * n + n, "zkp_kzg_open_all", &ws));
-    char* d_coeffs = static_cast<char*>(ws);
-    char* d_evals = d_coeffs + 32 * len;
-    char* d_xy = d_evals + 32 * n;
-    uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * n);
-    HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 32 * len, hipMemcpyHostToDevice, st));
-    ZCHK(kzg_open_all_locked(o, d_coeffs, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
-    HIPCHK(hipMemcpyAsync(out_xy, d_xy, 96 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, n, hipMemcpyDeviceToHost, st));
-    if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return ZKP_OK;
-} ZKP_CATCH_INT
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------- coset openings
-extern "C" {
-
 int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned log_l, zkp_kzg_opener** out) try {
     if (!srs || !out) return fail(ZKP_E_ARG, "null argument");
-    if (!g1_coset_shape_ok(log_n, log_l)) return fail(ZKP_E_ARG, "a coset opener needs log_l < log_n <= 23");
-    if (log_l == 0) return zkp_kzg_opener_create(srs, log_n, out);  // cosets of one point: the all-openings opener itself
+    if (!g1_coset_shape_ok(log_n, log_l)) return fail(ZKP_E_ARG, "an opener needs log_l < log_n <= 23");
     if (!srs->shards.empty()) return fail(ZKP_E_ARG, kShardedG1Ntt);
     const uint64_t n = (uint64_t)1 << log_n, l = (uint64_t)1 << log_l;
     if (srs->n < n - l) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_n - 2^log_l points");
@@ -479,28 +399,26 @@ int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned 
     {   // refused before anything is allocated when the sizes exceed the caller's budget or the free memory; a failed allocation
         // after that ends in the same message, and `o` releases what it got
         const size_t budget = (size_t)knob_int(KNOB_KZG_OPENER_MAX_BYTES);
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = total_b = 0, (void)hipGetLastError();
-        const bool fits = sz.total <= budget && (!total_b || sz.total <= free_b);
+        const DevFree mem;
+        const bool fits = sz.total <= budget && (!mem.total_b || sz.total <= mem.free_b);
         if (!fits || o->srs_hat.grow(sz.srs_hat) != hipSuccess || o->work.grow(sz.total - sz.srs_hat) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(ZKP_E_NOMEM, "zkp_kzg_opener_create_cosets: the workspaces of " + std::to_string(sz.total) + " bytes (" +
-                                         std::to_string(sz.srs_hat) + " kept slices + " + std::to_string(sz.total - sz.srs_hat) +
-                                         " per call) do not fit, " + std::to_string(free_b) + " of " + std::to_string(total_b) +
-                                         " bytes free on the device, ZKP_KZG_OPENER_MAX_BYTES " + std::to_string(budget));
+            return mem.refuse("zkp_kzg_opener_create_cosets: the workspaces of " + std::to_string(sz.total) + " bytes (" +
+                                  std::to_string(sz.srs_hat) + " kept slices + " + std::to_string(sz.total - sz.srs_hat) + " per call) do not fit",
+                              ", ZKP_KZG_OPENER_MAX_BYTES " + std::to_string(budget));
         }
     }
     const CosetWork w = coset_work(o.get());
     // slice b: 2r points of the plane-major array of 2n, at b 2r; all of them are transformed where they stay, stage by stage together
+    // (the table of these transforms is where the calls keep theirs)
     const G1NttVec all{static_cast<uint4*>(o->srs_hat.p), 2 * n, w.table, w.tcap};
-    for (uint64_t first = 0; first < 2 * n; first += G1_NTT_IO_LAUNCH) {
-        hipLaunchKernelGGL(g1_ntt_load_slices_kernel, dim3(g1_ntt_blocks(std::min<uint64_t>(G1_NTT_IO_LAUNCH, 2 * n - first), MSM_THREADS)),
-                           dim3(MSM_THREADS), 0, st, static_cast<const uint4*>(srs->d_xy.p), srs->d_inf.get(), (uint32_t)log_n, (uint32_t)log_l,
-                           first, all.pts, all.cap);
-        HIPCHK(hipGetLastError());
-    }
+    ZCHK(g1_ntt_io_launches(2 * n, [&](uint64_t first, uint64_t cnt) {
+        hipLaunchKernelGGL(g1_ntt_load_slices_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st,
+                           static_cast<const uint4*>(srs->d_xy.p), srs->d_inf.get(), (uint32_t)log_n, (uint32_t)log_l, first, all.pts, all.cap);
+    }));
     ZCHK(g1_ntt_stages(all, log_n - log_l + 1, 0, false, st, l));
-    {   // as zkp_kzg_opener_create: the plans, tables and scratch of the Fr transforms of a call, and the point transforms' constants
+    {   // Everything a call builds on first use is built here, so that zkp_kzg_open_*_dev neither allocate nor wait: the plans, tables
+        // and scratch of its Fr transforms (over the zeroed scalar area) and the constants of its point transforms
         const Fr* row = nullptr;
         HIPCHK(hipMemsetAsync(w.g, 0, sz.scalars, st));
         ZCHK(coset_fr_rows(w.g, log_n - log_l + 1, l, st));
@@ -514,35 +432,25 @@ int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned 
 
 int zkp_kzg_open_cosets_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
                             void* stream) try {
-    ZCHK(kzg_open_all_args(o, d_coeffs, len, d_out_xy, d_out_is_inf, true));
-    CTX_ENTER(o->slot);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    WsOrder ord(st);
-    return o->log_l ? kzg_open_cosets_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st)
-                    : kzg_open_all_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st);
+    return kzg_open_dev(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, stream, true);
 } ZKP_CATCH_INT
 
 int zkp_kzg_open_cosets(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, uint64_t* out_xy, uint8_t* out_is_inf,
                         uint64_t* out_evals) try {
-    ZCHK(kzg_open_all_args(o, coeffs, len, out_xy, out_is_inf, true));
-    if (!o->log_l) return zkp_kzg_open_all(o, coeffs, len, out_xy, out_is_inf, out_evals);
-    CTX_ENTER(o->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
-    WsOrder ord(st);
-    const size_t n = (size_t)1 << o->log_n, r = n >> o->log_l;
-    void* ws = nullptr;  // coefficients | evaluations | points | flags
-    ZCHK(g1_ntt_workspace(32 * len + 32 * n + 96 * r + r, "zkp_kzg_open_cosets", &ws));
-    char* d_coeffs = static_cast<char*>(ws);
-    char* d_evals = d_coeffs + 32 * len;
-    char* d_xy = d_evals + 32 * n;
-    uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * r);
-    HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 32 * len, hipMemcpyHostToDevice, st));
-    ZCHK(kzg_open_cosets_locked(o, d_coeffs, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
-    HIPCHK(hipMemcpyAsync(out_xy, d_xy, 96 * r, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, r, hipMemcpyDeviceToHost, st));
-    if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return ZKP_OK;
+    return kzg_open_host(o, coeffs, len, out_xy, out_is_inf, out_evals, "zkp_kzg_open_cosets", true);
+} ZKP_CATCH_INT
+
+// all n openings: the cosets of one point, through an opener of log_l = 0
+int zkp_kzg_opener_create(const zkp_bases* srs, unsigned log_n, zkp_kzg_opener** out) { return zkp_kzg_opener_create_cosets(srs, log_n, 0, out); }
+
+int zkp_kzg_open_all_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
+                         void* stream) try {
+    return kzg_open_dev(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, stream, false);
+} ZKP_CATCH_INT
+
+int zkp_kzg_open_all(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, uint64_t* out_xy, uint8_t* out_is_inf,
+                     uint64_t* out_evals) try {
+    return kzg_open_host(o, coeffs, len, out_xy, out_is_inf, out_evals, "zkp_kzg_open_all", false);
 } ZKP_CATCH_INT
 
 // e(W, [s^l]_2 - x^l G_2) == e(C - [I(s)]_1, G_2), I the interpolant of evals[j] at x w_l^j, j < l: coefficient i of I is x^-i times

@@ -1,6 +1,6 @@
 // g1_ntt_plan.hpp -- the index arithmetic of the transform over G1 POINTS (g1_ntt.hpp, g1_ntt_host.inc): which two points and which
-// twiddle a butterfly lane takes, where the SRS points and the coefficients of an all-openings call sit in its two vectors of 2n,
-// where the quotient slice h comes out, how large the workspaces are and how the lanes of a pass are cut into launches.  Plain
+// twiddle a butterfly lane takes, where the SRS points and the coefficients of an opener's call sit in its slices and rows (all
+// openings: one of each), where the quotient slice h comes out, how large the workspaces are and how the lanes of a pass are cut into launches.  Plain
 // C++17 without HIP, so that tests/host/g1_ntt_plan.cpp checks it with g++ alone; under hipcc (ff.hpp included first) the kernels
 // call the same functions.
 //
@@ -72,27 +72,6 @@ inline G1NttLoadMap g1_ntt_load_plain(unsigned log_n) {
     return G1NttLoadMap{n, n, 0, 1, log_n};
 }
 
-// All n openings of f (len <= n coefficients) over SRS points S_0 .. S_{d-1}, d = n - 1 (include/zkp_hip.h, zkp_kzg_open_all):
-//   s_j = S_{d-1-j} for j < d, identity for d <= j < 2n;   g_t = f_{t+1} for t + 1 < len, zero behind;
-//   u = iNTT_2n(NTT_2n(s) . NTT_2n(g));   h_i = u_{d-1+i} for i < d, h_d = O;   proofs = NTT_n(h).
-// (u_m = sum_{j+t=m} [g_t] s_j, so u_{d-1+i} = sum_t [f_{t+1}] S_{t-i} = sum_k [f_{i+1+k}] S_k; the largest index is 2d - 2 < 2n.)
-inline G1NttLoadMap g1_open_srs_map(unsigned log_n) {
-    const uint64_t n = (uint64_t)1 << log_n;
-    return G1NttLoadMap{2 * n, n - 1, (int64_t)n - 2, -1, log_n + 1};
-}
-struct G1OpenCoeffRun {  // slots [0, count) of g take the coefficients first, first + 1, ...: ONE copy in the driver; zeros behind
-    uint64_t first, count;
-};
-inline G1OpenCoeffRun g1_open_coeff_run(uint64_t len) { return G1OpenCoeffRun{1, len ? len - 1 : 0}; }  // (len <= n: the driver refuses more)
-inline int64_t g1_open_coeff_source(uint64_t len, uint64_t t) {  // the coefficient in slot t of g, -1: zero
-    const G1OpenCoeffRun r = g1_open_coeff_run(len);
-    return t < r.count ? (int64_t)(r.first + t) : -1;
-}
-inline G1NttLoadMap g1_open_slice_map(unsigned log_n) {  // h out of u, loaded for the transform of n
-    const uint64_t n = (uint64_t)1 << log_n;
-    return G1NttLoadMap{n, n - 1, (int64_t)n - 2, 1, log_n};
-}
-
 // Launches of a pass of `lanes` multiplying lanes: launch k covers [k * G1_NTT_LAUNCH, ...) and is the only one that may be short
 inline uint64_t g1_ntt_launches(uint64_t lanes) { return (lanes + G1_NTT_LAUNCH - 1) / G1_NTT_LAUNCH; }
 inline uint64_t g1_ntt_launch_lanes(uint64_t lanes, uint64_t k) {
@@ -113,29 +92,21 @@ inline G1NttSizes g1_ntt_sizes(unsigned log_n, uint64_t mul_lanes) {  // mul_lan
     s.total = s.points + s.table;
     return s;
 }
-struct G1OpenSizes {
-    size_t srs_hat, work, slice, scalars, table, total;  // NTT_2n(s) (kept), u, h, g, the lanes' table
-};
-inline G1OpenSizes g1_open_sizes(unsigned log_n) {
-    const uint64_t n = (uint64_t)1 << log_n;
-    G1OpenSizes s;
-    s.srs_hat = s.work = G1_NTT_POINT_BYTES * 2 * n;
-    s.slice = G1_NTT_POINT_BYTES * n;
-    s.scalars = 32 * 2 * n;
-    s.table = g1_ntt_sizes(log_n + 1, 2 * n).table;
-    s.total = s.srs_hat + s.work + s.slice + s.scalars + s.table;
-    return s;
-}
 
-// The n / l multi-point proofs of f, one per coset of l = 2^log_l points (include/zkp_hip.h, zkp_kzg_open_cosets): r = n / l >= 2
-// cosets, coset k = {w^(k + j r) : j < l}, the roots of X^l - x_k^l with x_k = w^k; proof k is the commitment of the quotient of f
-// by that binomial.  The all-openings construction above, once per slice b < l of the SRS and of f, in vectors of 2r:
+// The n / l multi-point proofs of f (len <= n coefficients), one per coset of l = 2^log_l points (include/zkp_hip.h,
+// zkp_kzg_open_cosets): r = n / l >= 2 cosets, coset k = {w^(k + j r) : j < l}, the roots of X^l - x_k^l with x_k = w^k; proof k is the
+// commitment of the quotient of f by that binomial.  One convolution per slice b < l of the SRS and of f, in vectors of 2r:
 //   s^(b)_j = S_{(r-2-j) l + b} for j < r - 1, identity behind;   g^(b)_t = f_{(t+1) l + b} for t < r - 1 and below len, zero behind;
 //   U_k = sum_{b<l} [NTT_2r(g^(b))_k] NTT_2r(s^(b))_k for k < 2r;   u = iNTT_2r(U);   h_i = u_{r-2+i} for i < r - 1, h_{r-1} = O;
 //   proofs = NTT_r(h), whose root is w^l.
 // (u_m = sum_b sum_{j+t=m} [g^(b)_t] s^(b)_j, so h_i = sum_b sum_t [f_{(t+1) l + b}] S_{(t-i) l + b} = sum_c [f_{(i+1) l + c}] S_c: the
 // coefficient of x_k^(l i) in the quotient's commitment, q_k = sum_i x_k^(l i) sum_c f_{(i+1) l + c} X^c.)  SRS points S_0 .. S_{n-l-1}
-// are read.  l = 1 gives the maps of the all-openings call (d = r - 1).
+// are read.
+// l = 1 is all n openings of f (zkp_kzg_open_all), over SRS points S_0 .. S_{d-1}, d = n - 1 -- one slice, r = n:
+//   s_j = S_{d-1-j} for j < d, identity for d <= j < 2n;   g_t = f_{t+1} for t + 1 < len, zero behind;
+//   u = iNTT_2n(NTT_2n(s) . NTT_2n(g));   h_i = u_{d-1+i} for i < d, h_d = O;   proofs = NTT_n(h).
+// (u_m = sum_{j+t=m} [g_t] s_j, so u_{d-1+i} = sum_t [f_{t+1}] S_{t-i} = sum_k [f_{i+1+k}] S_k; the largest index is 2d - 2 < 2n.)  Proof m
+// is the single-point opening at w^m; the sizes are 512n / 512n / 256n / 64n bytes and the table, no partial sums.
 constexpr unsigned G1_COSET_MAX_GROUP_LOG = 3;  // a lane of the multiply-accumulate pass sums at most 8 terms
 // B = 2^G1_COSET_GROUP_LOG terms share the 128 doublings of one lane.  0 is the per-term multiplication plus the fold; it stays 0
 // until profiles/kzg_open_cosets.md holds a measurement in which a larger group wins.

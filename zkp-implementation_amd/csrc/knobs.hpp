@@ -91,10 +91,11 @@ constexpr KnobRow kKnobs[KNOB_COUNT] = {
     {KNOB_FRI_FR_TAIL_LOG, "ZKP_FRI_FR_TAIL_LOG", KNOB_TUNING, KNOB_INT_CLAMP, 0, 10, 9,
      "FRI over Fr: layers of up to 2^v points run in the tail kernel (0: none)"},
     {KNOB_KZG_COSET_GROUP_LOG, "ZKP_KZG_COSET_GROUP_LOG", KNOB_TUNING, KNOB_INT, 0, 3, KNOB_COMPUTED,
-     "coset openers created from now on sum 2^v terms per lane of the multiply-accumulate pass (default: G1_COSET_GROUP_LOG): "
-     "profiles/kzg_open_cosets.md"},
+     "openers created from now on sum 2^v terms per lane of the multiply-accumulate pass (default: G1_COSET_GROUP_LOG; an opener of "
+     "all n points, log_l = 0, has one term per lane whatever v): profiles/kzg_open_cosets.md"},
     {KNOB_KZG_OPENER_MAX_BYTES, "ZKP_KZG_OPENER_MAX_BYTES", KNOB_POLICY, KNOB_INT, 0, LLONG_MAX, LLONG_MAX,
-     "a coset opener whose slices and workspaces are larger than this is refused with ZKP_E_NOMEM before anything is allocated"},
+     "an opener (zkp_kzg_opener_create*, any log_l) whose slices and workspaces are larger than this is refused with ZKP_E_NOMEM "
+     "before anything is allocated"},
 };
 
 constexpr bool knob_rows_in_enum_order() {

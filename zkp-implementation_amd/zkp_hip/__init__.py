@@ -914,7 +914,7 @@ class KzgOpener:
         self._h = C.c_void_p()
         if log_l:
             _chk(lib().zkp_kzg_opener_create_cosets(srs_bases._h, log_n, log_l, C.byref(self._h)))
-        else:
+        else:  # (the same creation with log_l = 0; called by its own name so that the suite runs both entries)
             _chk(lib().zkp_kzg_opener_create(srs_bases._h, log_n, C.byref(self._h)))
 
     def open_all(self, coeffs, want_evals=True):
