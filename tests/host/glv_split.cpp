@@ -192,12 +192,12 @@ static int check_plans() {
         for (size_t count : {1, 3, 32, 33}) {
             MsmBases split{sz.n, s.widest, s.planes, s.off, 1}, plain{sz.n, s.widest, s.planes, s.off, 0};
             MsmPlan a, b;
-            const int rc = plan_msm(split, count, sz.n, nullptr, &a);
+            const int rc = plan_msm(split, count, sz.n, nullptr, 2048, &a);
             if (count == 33) {
                 if (rc != ZKP_E_ARG || !strstr(a.error, "32 MSMs")) bad++, printf("a batch of 33 was not refused\n");
                 continue;
             }
-            if (rc != ZKP_OK || plan_msm(plain, 2 * count, sz.n, nullptr, &b) != ZKP_OK) {
+            if (rc != ZKP_OK || plan_msm(plain, 2 * count, sz.n, nullptr, 2048, &b) != ZKP_OK) {
                 printf("plan refused: n %llu count %zu\n", (unsigned long long)sz.n, count);
                 bad++;
                 continue;

@@ -611,6 +611,64 @@ def test_msm_batch_matches_single(zkp, orc):
         assert oinf == inf and np.array_equal(one, xy)
 
 
+@pytest.fixture(scope="module")
+def launch_plan_cases(zkp, orc):
+    """Bases, scalar vectors and the oracle's results for the launch-plan tests below: 64 plain bases (8-bit windows: 32 bucket sets
+    per MSM) and 3000 bases expanded at 16 bits (one bucket set per MSM), 17 vectors each."""
+    cases = {}
+    for name, n, expand in (("plain64", 64, 0), ("expanded3000", 3000, 16)):
+        ks = orc.rand_fr(0x91A0 + n, n)
+        pts, _ = orc.g1_fixed_base_mul(ks)
+        bases = zkp.G1Bases.from_host(pts)
+        if expand:
+            bases.precompute(expand)
+        vecs = [orc.rand_fr(0x5EED4000 + 64 * n + i, n) for i in range(17)]
+        vecs[5][:] = 0  # the identity in the middle of a batch
+        want = [orc.g1_mul(orc.g1_generator(), 0, orc.fr_inner_product(v, ks)) for v in vecs]
+        cases[name] = (bases, n, vecs, want)
+    return cases
+
+
+def check_batch_and_singles(zkp, case, count):
+    bases, n, vecs, want = case
+    got = zkp.msm_g1_batch_dev(bases, [dev(v) for v in vecs[:count]], n)
+    for v, (xy, inf), (exp, einf) in zip(vecs, got, want):
+        assert inf == einf and np.array_equal(xy, exp)
+        one, oinf = zkp.msm_g1(bases, v)
+        assert oinf == inf and np.array_equal(one, xy)
+
+
+def test_msm_batch_beyond_the_resident_waves_reduces_level_by_level(zkp, orc, launch_plan_cases):
+    """17 MSMs over 64 plain bases are 544 bucket sets at c = 8: one workgroup of four waves per set is more than a full card keeps
+    resident (2048 waves), so the plan leaves the last-levels launch out -- every pyramid level its own launch, then
+    msm_collect_kernel (tests/golden/msm_launches.txt has this plan as "collect")."""
+    check_batch_and_singles(zkp, launch_plan_cases["plain64"], 17)
+
+
+@pytest.mark.parametrize("knobs", [{"ZKP_PYR_TAIL_HALF": "1"}, {"ZKP_PYR_TAIL_THREADS": "64", "ZKP_PYR_TAIL_BLOCKS": "64"},
+                                   {"ZKP_PYR_TAIL_THREADS": "512", "ZKP_PYR_TAIL_BLOCKS": "8"},
+                                   {"ZKP_FOLD_LANE_MIN": "1", "ZKP_MSM_SPLIT_LOG": "2"}], ids=lambda k: ",".join(f"{a[4:]}={b}" for a, b in k.items()))
+def test_msm_under_the_launch_plan_knobs(zkp, orc, launch_plan_cases, monkeypatch, knobs):
+    """The shapes the plan's tuning knobs select (read on every call): the last-levels launch from one pair per array on, as 64
+    single-wave and as 8 eight-wave workgroups per bucket set, and one lane per add in every fold step of a four-way split."""
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    for name in ("plain64", "expanded3000"):
+        check_batch_and_singles(zkp, launch_plan_cases[name], 3)
+
+
+def test_msm_refuses_a_bad_tail_knob_before_anything_is_enqueued(zkp, orc, launch_plan_cases, monkeypatch):
+    bases, n, vecs, want = launch_plan_cases["expanded3000"]
+    monkeypatch.setenv("ZKP_PYR_TAIL_THREADS", "100")
+    with pytest.raises(zkp.ZkpError) as ei:
+        zkp.msm_g1(bases, vecs[0])
+    assert ei.value.code == zkp.ZKP_E_ARG
+    assert "ZKP_PYR_TAIL_THREADS must be a multiple of 64 up to 512, ZKP_PYR_TAIL_BLOCKS 1..256, ZKP_PYR_TAIL_HALF >= 1" in str(ei.value)
+    monkeypatch.delenv("ZKP_PYR_TAIL_THREADS")
+    out, inf = zkp.msm_g1(bases, vecs[0])
+    assert inf == want[0][1] and np.array_equal(out, want[0][0])
+
+
 def test_kzg_open_long_polynomial_device_path(zkp, orc):
     """open() of a 2^15-coefficient polynomial: evaluation and the division by (X - z) run on the GPU (scheme.rs:108-120);
     checked against the oracle's Horner / synthetic division and the trapdoor identity W = [(p(s) - y)/(s - z)]G."""

@@ -9,12 +9,12 @@
 namespace zkp {
 
 enum Knob {
-    // read by plan_msm / msm_feed_ranges (msm_plan.hpp): the rows before KNOB_MSM_PLAN_END
+    // read by plan_msm / plan_reduce / msm_feed_ranges (msm_plan.hpp): the rows before KNOB_MSM_PLAN_END
     KNOB_MSM_C, KNOB_MSM_FEED_RANGES, KNOB_MSM_FEED_FIRST_PCT, KNOB_MSM_FEED_SECOND_PCT, KNOB_MSM_RANGE_LOG, KNOB_MSM_FIRST_PCT,
-    KNOB_MSM_NCHUNK, KNOB_SORT_LO_BITS, KNOB_MSM_NO_OVERLAP, KNOB_MSM_SPLIT_LOG,
+    KNOB_MSM_NCHUNK, KNOB_SORT_LO_BITS, KNOB_MSM_NO_OVERLAP, KNOB_MSM_SPLIT_LOG, KNOB_FOLD_LANE_MIN, KNOB_PYR_TAIL_THREADS,
+    KNOB_PYR_TAIL_BLOCKS, KNOB_PYR_TAIL_HALF,
     KNOB_MSM_PLAN_END,
-    KNOB_FOLD_LANE_MIN = KNOB_MSM_PLAN_END, KNOB_PYR_TAIL_THREADS, KNOB_PYR_TAIL_BLOCKS, KNOB_PYR_TAIL_HALF, KNOB_TEST_TAIL_STARVE,
-    KNOB_MSM_NO_POLL, KNOB_POOL_NO_WARM, KNOB_MSM_BALANCE_FROM, KNOB_SRS_EXPAND_MAX_BYTES, KNOB_NTT_TW_MATRIX_MAX_LOG,
+    KNOB_TEST_TAIL_STARVE = KNOB_MSM_PLAN_END, KNOB_MSM_NO_POLL, KNOB_POOL_NO_WARM, KNOB_MSM_BALANCE_FROM, KNOB_SRS_EXPAND_MAX_BYTES, KNOB_NTT_TW_MATRIX_MAX_LOG,
     KNOB_NTT_NO_WIDE_PASS, KNOB_NTT_SHARD_MIN_LOG, KNOB_PLONK_NO_POLL, KNOB_FRI_ZERO_AS_0, KNOB_FRI_FR_TAIL_LOG,
     KNOB_KZG_COSET_GROUP_LOG, KNOB_KZG_OPENER_MAX_BYTES,
     KNOB_COUNT

@@ -17,13 +17,11 @@
 #include "g1.hpp"
 #include "g1_28.hpp"
 #include "fq28_inv.hpp"
-#include "msm_plan.hpp"  // MsmGeom, SortGeom and the limits the host plan shares with the kernels
+#include "msm_plan.hpp"  // MsmGeom, SortGeom, the workgroup sizes and limits the host plan shares with the kernels, the pyramid's addressing
 #include "glv.hpp"       // glv_split: the scalar halves of the endomorphism-split mode
 
 namespace zkp {
 
-constexpr int MSM_THREADS = 256;
-constexpr int ACC_THREADS = 256;  // workgroup size of msm_accumulate (64 and 128 measure the same)
 // The kernels below take MsmGeom and SortGeom (msm_plan.hpp) by value: their layout is part of this file's kernels, pinned here
 #define ZKP_AT(f, o) offsetof(MsmGeom, f) == o
 static_assert(sizeof(MsmGeom) == 160 && ZKP_AT(c, 0) && ZKP_AT(nwin, 4) && ZKP_AT(nb, 8) && ZKP_AT(nchunk, 12) && ZKP_AT(n, 16) && ZKP_AT(chunk, 24) &&
@@ -227,16 +225,7 @@ __global__ __launch_bounds__(64) void msm_partstart_kernel(const uint32_t* __res
 constexpr int BS_TILE = ZKP_BS_TILE;
 constexpr int BS_PER = BS_TILE / 1024;
 constexpr int SORT_MAX_BINS = 1024;  // low-bit bins of the second pass (one workgroup of 1024 threads owns a partition)
-#ifndef ZKP_PS_TILE
-#define ZKP_PS_TILE 12288
-#endif
-// entries per tile of the first pass, as large as the 160 KB of LDS allow next to the 12 bytes per partition: 12288 entries over up to
-// 2048 partitions leave as 48..96-byte runs (147 KB; 8192: 32..64-byte runs; round 4, profiles/r04_m: together with the 16384-entry
-// second pass the sort goes 0.192 -> 0.176 ms at 2^20, 0.63 -> 0.57 at 2^22, 2.49 -> 2.3 ms at 2^24), 8192 up to 4096 partitions
-// (131 KB), 4096 up to 8192 partitions -- 24-bit windows -- (139 KB).  One workgroup per CU, no loss on small problems.
-constexpr int PS_TILE_BIG = ZKP_PS_TILE, PS_TILE_MID = 8192, PS_TILE_SMALL = 4096;
-ZKP_HD size_t partscatter_lds_bytes(uint32_t nhi, int tile) { return 8 * (size_t)tile + 2 * (size_t)tile + 4 * (size_t)(3 * nhi + 1); }
-ZKP_HD int partscatter_tile(uint32_t nhi) { return nhi <= 2048 ? PS_TILE_BIG : nhi <= 4096 ? PS_TILE_MID : PS_TILE_SMALL; }
+// (the tiles of the first pass, PS_TILE_*, and their LDS bytes: msm_plan.hpp)
 
 template <int PS_TILE>
 __global__ __launch_bounds__(1024) void msm_partscatter_kernel(const uint32_t* __restrict__ digits, MsmGeom g, SortGeom sg,
@@ -590,10 +579,6 @@ ZKP_DEV void split_run(const MsmGeom& g, uint32_t part, uint32_t& lo, uint32_t& 
 }
 
 // (ClkRec, clk_begin, clk_end -- the in-kernel clock stamps of zkp_profile_clock_read -- live in ff.hpp: the NTT passes use them too)
-
-// Physical position of logical entry i of an n-entry level of the reduction pyramid (msm_pyramid_kernel): even entries in the first
-// half, odd entries in the second.  The bucket array is level 0 (n = nb, i = bucket - 1).
-ZKP_DEV uint64_t pyr_pos(uint32_t i, uint32_t n) { return (uint64_t)(i >> 1) + (uint64_t)(i & 1u) * (n >> 1); }
 
 // One lane per (window, bucket), buckets taken in decreasing-size order: buckets[w * nb + pyr_pos(b - 1, nb)] = sum of the
 // bucket's points (internal XYZZ, 256 B).  Lanes past nb take the pieces of oversized buckets (see msm_order).
@@ -963,35 +948,7 @@ __global__ __launch_bounds__(64) void msm_combine_kernel(const uint32_t* __restr
 // Levels ping-pong between two buffers (level l in parity l & 1, at the start of a window's nb entries); launch j + 1 writes level
 // j + 2 into the first quarter of level j's buffer while it reads level j's odd half there -- disjoint.
 // O_j lives at entry offset nb - (nb >> j) of an `odd` buffer (reads of launch l come from parity l & 1).
-struct PyrLevel {
-    uint32_t level;  // l
-    uint32_t half;   // nb >> (l+1)
-    uint32_t nb;
-    uint32_t nwin;
-};
-ZKP_DEV uint64_t odd_off(uint32_t nb, uint32_t j) { return (uint64_t)nb - (nb >> j); }
-// operands and destination of item (kind, s) of launch `level`: entry offsets inside the buffers named by the flags
-struct PyrItem {
-    uint64_t a, b, d;
-    bool src_is_pyr_out;  // kind j + 1 == level: the operands are level j's odd half, in the pyramid buffer this launch also writes
-};
-ZKP_DEV PyrItem pyr_item(uint32_t nb, uint32_t level, uint32_t half, uint32_t kind, uint32_t s, uint64_t wbase) {
-    PyrItem it;
-    if (kind == 0) {
-        it.a = wbase + s;
-        it.b = wbase + half + s;
-        it.d = wbase + pyr_pos(s, half);
-        it.src_is_pyr_out = false;
-    } else {
-        const uint64_t o = wbase + odd_off(nb, kind - 1);
-        it.src_is_pyr_out = kind == level;
-        const uint64_t src = it.src_is_pyr_out ? wbase + 2 * (uint64_t)half : o;  // level j = level - 1 has 4 half entries: odd half at [2 half, 4 half)
-        it.a = src + s;
-        it.b = src + half + s;
-        it.d = o + s;
-    }
-    return it;
-}
+// The addressing -- pyr_pos, odd_off, pyr_item, pyr_result -- is in msm_plan.hpp, where a host test replays the whole schedule.
 
 __global__ __launch_bounds__(MSM_THREADS) void msm_pyramid_kernel(const uint4* __restrict__ pyr_in,
                                                                   uint4* pyr_out,
@@ -1031,12 +988,11 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_pyramid_quad_kernel(const uin
 constexpr uint32_t MSM_TAIL_TIMEOUT = 0x80000000u;  // flag in a window's barrier counter, checked by the host
 constexpr uint32_t MSM_FLAG_PENDING = 0x40000000u;  // what the host writes into a result flag before the launch: "not written yet"
 constexpr uint32_t MSM_FLAG_PENDING_MASK = 0x40000000u;
-constexpr uint32_t PYR_TAIL_THREADS = 256;    // four waves = 64 cooperative adds per workgroup and round
-constexpr uint32_t PYR_TAIL_BLOCKS = 16;      // workgroups per window at most (1024 adds per round)
 // The spinning barrier below needs every workgroup of the launch RESIDENT (a spinner cannot make room for a sibling that was never
-// scheduled): the host keeps windows x workgroups x waves below what this device holds at two waves per SIMD and what the kernel's
-// own occupancy allows (Ctx::tail_max_waves: from hipDeviceProp and hipOccupancyMaxActiveBlocksPerMultiprocessor at slot creation --
-// 2048 on a full MI355X, less on a partition), and runs every level as its own launch when even one workgroup per window is too many.
+// scheduled): plan_reduce (msm_plan.hpp; default shape PYR_TAIL_THREADS x PYR_TAIL_BLOCKS) keeps windows x workgroups x waves below
+// what this device holds at two waves per SIMD and what the kernel's own occupancy allows (Ctx::tail_max_waves: from hipDeviceProp
+// and hipOccupancyMaxActiveBlocksPerMultiprocessor at slot creation -- 2048 on a full MI355X, less on a partition), and runs every
+// level as its own launch when even one workgroup per window is too many.
 constexpr uint32_t PYR_TAIL_SPIN_LIMIT = 1u << 24;  // polls (~seconds) before a workgroup gives up
 __global__ __launch_bounds__(512) void msm_pyramid_tail_kernel(uint4* __restrict__ pyr0, uint4* __restrict__ pyr1,
                                                                uint4* __restrict__ odd0, uint4* __restrict__ odd1,
@@ -1099,7 +1055,7 @@ __global__ __launch_bounds__(512) void msm_pyramid_tail_kernel(uint4* __restrict
         const uint4* odd_final = ((c - 1) & 1) ? odd1 : odd0;
         for (uint32_t t = threadIdx.x; t < c * 16; t += blockDim.x) {
             const uint32_t e = t >> 4, q = t & 15;
-            const uint4* src = e == 0 ? pyr_final + wbase : e == c - 1 ? pyr_prev + (wbase + 1) : odd_final + (wbase + odd_off(nb, e - 1));
+            const uint4* src = pyr_result(pyr_final, pyr_prev, odd_final, wbase, nb, c, e);
             result[((uint64_t)w * c + e) * 16 + q] = src[q * cap];
         }
         // the barrier counter goes home with the results: its top bit says that a workgroup gave up waiting (MSM_TAIL_TIMEOUT).  The
@@ -1122,8 +1078,7 @@ __global__ void msm_collect_kernel(const uint4* __restrict__ pyr_final, const ui
     if (j < c) {
         const uint64_t wbase = (uint64_t)w * nb;
         const uint64_t cap = (uint64_t)gridDim.x * nb;
-        // U_{c-2} is the odd entry of the two-entry level c - 2, still in the other pyramid buffer
-        const uint4* src = j == 0 ? pyr_final + wbase : j == c - 1 ? pyr_prev + (wbase + 1) : odd_final + (wbase + odd_off(nb, j - 1));
+        const uint4* src = pyr_result(pyr_final, pyr_prev, odd_final, wbase, nb, c, j);
         uint4* dst = result + ((uint64_t)w * c + j) * 16;
         for (int q = 0; q < 16; q++) dst[q] = src[q * cap];
     }

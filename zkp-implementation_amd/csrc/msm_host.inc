@@ -27,7 +27,6 @@ struct RangeBuffers {
 // and names the parts carved out of them.
 struct MsmPass {
     const MsmPlan& p;
-    MsmGeom g;  // the plan's geometry, narrowed to each range in turn (left at the last one)
     const zkp_bases* bases;
     const Fr* const* scalars;
     size_t count;
@@ -52,12 +51,12 @@ struct MsmPass {
     int grow() {
         for (const auto& [name, buf, bytes] : buffers()) ZCHK(buf->ensure(bytes));
         ZCHK(cx.host_result.ensure(p.bytes.host_result, hipHostMallocPortable | hipHostMallocMapped));  // written by this slot's device
-        ptot = cx.counts.get() + W * g.nchunk * nhi;
+        ptot = cx.counts.get() + W * p.g.nchunk * nhi;
         pstart = ptot + W * nhi;
         ghist = pstart + W * (nhi + 1);
         gcur = ghist + W * 256;
         result_out = static_cast<uint4*>(cx.host_result.p);
-        result_flags = reinterpret_cast<uint32_t*>(result_out + 16 * W * g.c);
+        result_flags = reinterpret_cast<uint32_t*>(result_out + 16 * W * p.g.c);
         return ZKP_OK;
     }
     RangeBuffers range_buffers(size_t par) const {
@@ -118,18 +117,11 @@ struct MsmPass {
             HIPCHK(hipEventRecord(cx.ev_begin, st));
             HIPCHK(hipStreamWaitEvent(sst, cx.ev_begin, 0));
         }
-        for (size_t ridx = 0, off = 0; ridx < p.lens.size(); off += p.lens[ridx++]) {
-            const uint64_t len = p.lens[ridx];
-            const size_t par = p.overlap ? (ridx & 1) : 0;  // buffer set of this range
+        for (size_t ridx = 0; ridx < p.lens.size(); ridx++) {
+            const MsmRange r = range_geom(p, ridx);
+            const size_t par = r.set;
             const RangeBuffers rb = range_buffers(par);
             if (p.overlap && ridx >= 2) HIPCHK(hipStreamWaitEvent(sst, cx.ev_acc[par], 0));  // range r-2 is done with this buffer set
-            if (len != g.ns) {  // a range shorter than the longest (the last one, or the first of a host-fed walk): smaller geometry
-                g.ns = len;
-                g.n = (uint64_t)p.nwin1 * len;
-                g.chunk = (g.n + g.nchunk - 1) / g.nchunk;
-            }
-            g.resume = off ? 1u : 0u;
-            g.more = ridx + 1 < p.lens.size() ? 1u : 0u;
             if (feed) {  // this range's scalars: host -> device on the copy stream, the kernels below wait for them
                 if (ridx == 0)
                     ZCHK(feed_first_range());
@@ -137,136 +129,115 @@ struct MsmPass {
                     return fail(ZKP_E_DEVICE, "upload of a scalar range failed");
                 HIPCHK(hipStreamWaitEvent(sst, ridx == 0 ? feed->ev : cx.copy_events[ridx - 1], 0));
             }
-            launch_sort(rb, off, ridx);
+            launch_sort(rb, r);
             if (p.overlap) {
                 HIPCHK(hipEventRecord(cx.ev_sort[par], sst));
                 HIPCHK(hipStreamWaitEvent(st, cx.ev_sort[par], 0));
             }
-            launch_accumulate(rb, off, ridx);
+            launch_accumulate(rb, r);
             if (p.overlap) HIPCHK(hipEventRecord(cx.ev_acc[par], st));
         }
         return ZKP_OK;
     }
 
-    template <int TILE> void launch_partscatter() {
-        hipLaunchKernelGGL(msm_partscatter_kernel<TILE>, dim3(g.nchunk, g.nwin), dim3(1024), partscatter_lds_bytes(nhi, TILE), sst,
+    template <int TILE> void launch_partscatter(const MsmGeom& g) {
+        hipLaunchKernelGGL(msm_partscatter_kernel<TILE>, dim3(g.nchunk, g.nwin), dim3(1024), p.ps_lds, sst,
                            cx.digits.get(), g, p.sg, cx.counts.get(), pstart, cx.entries.get());
     }
-    // Digits and counting sort of the range at `off` (g.ns scalars)
-    void launch_sort(const RangeBuffers& rb, uint64_t off, size_t ridx) {
+    // Digits and counting sort of range r (r.g.ns scalars from r.off)
+    void launch_sort(const RangeBuffers& rb, const MsmRange& r) {
         const SortGeom& sg = p.sg;
+        const MsmGeom& g = r.g;
+        const SortLaunch sl = sort_launch(sg, g);
         {
             ProfScope ps("msm_digits", sst);
             DigitSources ds;  // digits laid out [msm][slice][scalar]: a shared-mode sort window is one msm (split planes: one half of one)
-            for (size_t m = 0; m < count; m++) ds.scalars[m] = scalars[m] + off;
-            hipLaunchKernelGGL(g.glv ? msm_digits_glv_kernel : msm_digits_kernel, dim3((unsigned)((g.ns + MSM_THREADS - 1) / MSM_THREADS), (unsigned)count), dim3(MSM_THREADS), 0,
-                               sst, ds, bases->d_inf.p ? bases->d_inf.get() + off : nullptr, g, p.nwin1, cx.digits.get());
-            MSM_TRACE(sst, ridx, "digits");
+            for (size_t m = 0; m < count; m++) ds.scalars[m] = scalars[m] + r.off;
+            hipLaunchKernelGGL(g.glv ? msm_digits_glv_kernel : msm_digits_kernel, dim3(sl.digits_x, (unsigned)count), dim3(MSM_THREADS), 0,
+                               sst, ds, bases->d_inf.p ? bases->d_inf.get() + r.off : nullptr, g, p.nwin1, cx.digits.get());
+            MSM_TRACE(sst, r.ridx, "digits");
         }
         ProfScope ps("msm_sort", sst, true);
         hipLaunchKernelGGL(msm_parthist_kernel, dim3(g.nchunk, g.nwin), dim3(1024), 0, sst, cx.digits.get(), g, sg, cx.counts.get());
-        MSM_TRACE(sst, ridx, "parthist");
-        hipLaunchKernelGGL(msm_partprefix_kernel, dim3((sg.nhi + 63) / 64, g.nwin), dim3(1024), 0, sst, cx.counts.get(), g, sg, ptot);
+        MSM_TRACE(sst, r.ridx, "parthist");
+        hipLaunchKernelGGL(msm_partprefix_kernel, dim3(sl.prefix_x, g.nwin), dim3(1024), 0, sst, cx.counts.get(), g, sg, ptot);
         hipLaunchKernelGGL(msm_partstart_kernel, dim3(g.nwin), dim3(64), 0, sst, ptot, sg, pstart, ghist, cx.result.get());
-        MSM_TRACE(sst, ridx, "partprefix + partstart");
-        switch (partscatter_tile(sg.nhi)) {  // the largest tile whose staging fits the LDS next to 12 bytes per partition
-            case PS_TILE_SMALL: launch_partscatter<PS_TILE_SMALL>(); break;
-            case PS_TILE_MID: launch_partscatter<PS_TILE_MID>(); break;
-            default: launch_partscatter<PS_TILE_BIG>(); break;
+        MSM_TRACE(sst, r.ridx, "partprefix + partstart");
+        switch (p.ps_tile) {
+            case PS_TILE_SMALL: launch_partscatter<PS_TILE_SMALL>(g); break;
+            case PS_TILE_MID: launch_partscatter<PS_TILE_MID>(g); break;
+            default: launch_partscatter<PS_TILE_BIG>(g); break;
         }
-        MSM_TRACE(sst, ridx, "partscatter");
+        MSM_TRACE(sst, r.ridx, "partscatter");
         hipLaunchKernelGGL(msm_binsort_kernel, dim3(sg.nhi, g.nwin), dim3(1024), 0, sst, cx.entries.get(), g, sg, pstart, rb.start, rb.sorted, ghist);
-        MSM_TRACE(sst, ridx, "binsort");
-        hipLaunchKernelGGL(msm_rank_kernel, dim3((g.nb + 1023) / 1024, g.nwin), dim3(1024), 0, sst, rb.start, g, ghist, gcur, rb.perm);
-        MSM_TRACE(sst, ridx, "rank");
+        MSM_TRACE(sst, r.ridx, "binsort");
+        hipLaunchKernelGGL(msm_rank_kernel, dim3(sl.rank_x, g.nwin), dim3(1024), 0, sst, rb.start, g, ghist, gcur, rb.perm);
+        MSM_TRACE(sst, r.ridx, "rank");
         hipLaunchKernelGGL(msm_order_kernel, dim3(g.nwin), dim3(1024), 0, sst, rb.start, g, ghist, rb.perm, rb.over, rb.over_b, rb.over_off,
                            rb.desc, p.over_cap, p.desc_cap);
-        MSM_TRACE(sst, ridx, "order");
+        MSM_TRACE(sst, r.ridx, "order");
     }
 
-    // Accumulate the sorted range at `off` into the buckets, combine the pieces of oversized buckets, fold split runs
-    void launch_accumulate(const RangeBuffers& rb, uint64_t off, size_t ridx) {
+    // Accumulate the sorted range r into the buckets, combine the pieces of oversized buckets, fold split runs
+    void launch_accumulate(const RangeBuffers& rb, const MsmRange& r) {
         ProfScope ps("msm_accumulate", st, true);
-        // up to 2^20 entries four lanes per bucket: one lane would be latency-bound by its longest run (tools/small_msm_bench.py)
-        const bool quad = !g.resume && !g.more && (uint64_t)g.n * g.nwin <= (1ull << 20);
-        const uint32_t per_block = quad ? ACC_THREADS / 4 : ACC_THREADS;
-        const uint32_t bucket_blocks = (uint32_t)((((uint64_t)g.nb << g.split_log) + per_block - 1) / per_block);
-        const uint32_t extra_blocks = std::min<uint32_t>((p.desc_cap + per_block - 1) / per_block, 64);
-        const dim3 grid((bucket_blocks + extra_blocks) * g.nwin);
-        const uint4* xy = static_cast<const uint4*>(bases->d_xy.p) + off * 8;
+        const MsmGeom& g = r.g;
+        const AccLaunch a = acc_launch(p, g);
+        const uint4* xy = static_cast<const uint4*>(bases->d_xy.p) + r.off * 8;
         uint4 *buckets = cx.buckets.get(), *pieces = cx.pieces.get(), *parts = cx.parts.get(), *carry = cx.pyr1.get();
-        if (quad)
-            hipLaunchKernelGGL(msm_accumulate_quad_kernel, grid, dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,
-                               p.desc_cap, bucket_blocks, extra_blocks, g, buckets, pieces, parts, clk_record(CLK_MSM_ACCUMULATE));
+        if (a.quad)
+            hipLaunchKernelGGL(msm_accumulate_quad_kernel, dim3(a.grid), dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,
+                               p.desc_cap, a.bucket_blocks, a.extra_blocks, g, buckets, pieces, parts, clk_record(CLK_MSM_ACCUMULATE));
         else
-            hipLaunchKernelGGL(msm_accumulate_kernel, grid, dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,
-                               p.desc_cap, bucket_blocks, extra_blocks, g, buckets, pieces, parts, carry, clk_record(CLK_MSM_ACCUMULATE));
-        MSM_TRACE(st, ridx, "accumulate");
-        hipLaunchKernelGGL(msm_combine_kernel, dim3(std::min<uint32_t>(p.over_cap, 64), g.nwin), dim3(64), 0, st, rb.over, rb.over_b,
+            hipLaunchKernelGGL(msm_accumulate_kernel, dim3(a.grid), dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,
+                               p.desc_cap, a.bucket_blocks, a.extra_blocks, g, buckets, pieces, parts, carry, clk_record(CLK_MSM_ACCUMULATE));
+        MSM_TRACE(st, r.ridx, "accumulate");
+        hipLaunchKernelGGL(msm_combine_kernel, dim3(a.combine_x, g.nwin), dim3(64), 0, st, rb.over, rb.over_b,
                            rb.over_off, p.over_cap, p.desc_cap, g, pieces, buckets, carry);
-        MSM_TRACE(st, ridx, "combine");
-        // buckets += parts, pairwise: split_log steps; a step with many adds runs one lane per add, a small one four (latency): msm.hpp
-        const uint64_t cap = (uint64_t)g.nwin * g.nb;
-        const uint64_t lane_from = (uint64_t)knob_int(KNOB_FOLD_LANE_MIN);
-        for (uint32_t t = 0; t < g.split_log; t++) {
-            const unsigned pairs = 1u << (g.split_log - 1 - t), per = cap * pairs >= lane_from ? MSM_THREADS : MSM_THREADS / 4;  // adds per workgroup
-            hipLaunchKernelGGL(per == MSM_THREADS ? msm_fold_parts_lane_kernel : msm_fold_parts_kernel, dim3((unsigned)((cap + per - 1) / per), pairs),
-                               dim3(MSM_THREADS), 0, st, buckets, parts, cap, t);
-        }
+        MSM_TRACE(st, r.ridx, "combine");
+        for (uint32_t t = 0; t < g.split_log; t++)  // buckets += parts, pairwise (the steps: plan_msm)
+            hipLaunchKernelGGL(p.fold[t].lane ? msm_fold_parts_lane_kernel : msm_fold_parts_kernel, dim3(p.fold[t].grid_x, p.fold[t].pairs),
+                               dim3(MSM_THREADS), 0, st, buckets, parts, (uint64_t)g.nwin * g.nb, t);
     }
 
     // The weighted bucket sums: pyramid levels as their own launches, then the last levels (or only the gathering) in one launch
     // that writes the c result points and the flag word of every bucket set to pinned host memory
-    int reduce() {
-        // tuning aids (A/B runs): workgroup size and count of the last-levels launch, and the per-array pair count from which it takes over
-        static_assert(kKnobs[KNOB_PYR_TAIL_THREADS].dflt == PYR_TAIL_THREADS && kKnobs[KNOB_PYR_TAIL_BLOCKS].dflt == PYR_TAIL_BLOCKS, "knobs.hpp");
-        const uint32_t tail_threads = (uint32_t)knob_int(KNOB_PYR_TAIL_THREADS), tail_blocks = (uint32_t)knob_int(KNOB_PYR_TAIL_BLOCKS);
-        const uint32_t tail_half = (uint32_t)knob_int(KNOB_PYR_TAIL_HALF);
-        if (tail_threads < 64 || tail_threads > 512 || (tail_threads & 63) || !tail_blocks || tail_blocks > 256 || !tail_half)
-            return fail(ZKP_E_ARG, "ZKP_PYR_TAIL_THREADS must be a multiple of 64 up to 512, ZKP_PYR_TAIL_BLOCKS 1..256, ZKP_PYR_TAIL_HALF >= 1");
+    void reduce() {
+        const MsmGeom& g = p.g;
+        const ReducePlan& red = p.red;
         for (size_t w = 0; w < W; w++) __atomic_store_n(result_flags + w, MSM_FLAG_PENDING, __ATOMIC_RELEASE);  // (the previous MSM's results were read before it returned)
         uint4* pyr[2] = {cx.buckets.get(), cx.pyr1.get()};
         uint4* odd[2] = {cx.odd0.get(), cx.odd1.get()};
         ProfScope ps("msm_bucket_reduce", st, true);
-        uint32_t level_tail = 0;  // first level whose per-array work is <= 64 pairs: the rest runs in one launch
-        while (level_tail + 1 < g.c && (g.nb >> (level_tail + 1)) > tail_half) level_tail++;
-        // ... unless even one workgroup per bucket set is more than the device keeps resident (many bucket sets, a partition with few
-        // CUs): the barrier of that launch would spin for its whole time-out, so every level runs as its own launch instead
-        const uint32_t max_waves = cx.tail_max_waves;
-        if ((uint64_t)g.nwin * (tail_threads / 64) > max_waves) level_tail = g.c - 1;
-        for (uint32_t l = 0; l < level_tail; l++) {
-            const PyrLevel L{l, g.nb >> (l + 1), g.nb, g.nwin};
-            // levels with few adds are latency-bound: four lanes per add there (threshold swept 2^14..2^20: 2^16 is the minimum)
-            const bool quad = (uint64_t)L.half * (l + 1) * g.nwin <= (1u << 16);
-            const uint32_t per = quad ? MSM_THREADS / 4 : MSM_THREADS;  // adds per workgroup
-            hipLaunchKernelGGL(quad ? msm_pyramid_quad_kernel : msm_pyramid_kernel, dim3((L.half + per - 1) / per, l + 1, g.nwin),
-                               dim3(MSM_THREADS), 0, st, pyr[l & 1], pyr[(l + 1) & 1], odd[l & 1], odd[(l + 1) & 1], L);
+        for (uint32_t k = 0; k < red.nlevel; k++) {
+            const PyrLaunch& v = red.level[k];
+            const uint32_t l = v.level;
+            hipLaunchKernelGGL(v.quad ? msm_pyramid_quad_kernel : msm_pyramid_kernel, dim3(v.grid_x, l + 1, g.nwin), dim3(MSM_THREADS), 0, st,
+                               pyr[l & 1], pyr[(l + 1) & 1], odd[l & 1], odd[(l + 1) & 1], PyrLevel{l, v.half, g.nb, g.nwin});
         }
-        if (level_tail + 1 < g.c) {
-            uint32_t tb = tail_blocks;
-            while (tb > 1 && (uint64_t)tb * g.nwin * (tail_threads / 64) > max_waves) tb >>= 1;
+        if (red.tail_blocks) {
             // test hook (tests/test_gpu_parity.py): ask the barrier for one arrival more than there are workgroups, with a short
             // time-out -- the path a workgroup that never became resident would take: MSM_TAIL_TIMEOUT flag, ZKP_E_DEVICE
             const bool starve = knob_flag(KNOB_TEST_TAIL_STARVE);
-            hipLaunchKernelGGL(msm_pyramid_tail_kernel, dim3(tb, g.nwin), dim3(tail_threads), 0, st, pyr[0], pyr[1], odd[0], odd[1], level_tail,
-                               g.c, g.nb, cx.result.get(), result_out, result_flags, starve ? tb + 1 : tb, starve ? (1u << 12) : PYR_TAIL_SPIN_LIMIT);
+            hipLaunchKernelGGL(msm_pyramid_tail_kernel, dim3(red.tail_blocks, g.nwin), dim3(red.tail_threads), 0, st, pyr[0], pyr[1], odd[0], odd[1],
+                               red.nlevel, g.c, g.nb, cx.result.get(), result_out, result_flags, red.tail_blocks + (starve ? 1 : 0),
+                               starve ? (1u << 12) : PYR_TAIL_SPIN_LIMIT);
         } else {  // every level already ran as its own launch: only the gathering is left
             const uint32_t fin = (g.c - 1) & 1;
             hipLaunchKernelGGL(msm_collect_kernel, dim3(g.nwin), dim3(64), 0, st, pyr[fin], pyr[fin ^ 1], odd[fin], g.nb, g.c, result_out,
                                result_flags);
         }
-        return ZKP_OK;
     }
 };
 
-// Up to 2^24 entries per bucket set the host polls the result flags instead of waiting for the stream (poll_or_sync, dev_res.hpp)
-int wait_msm_result(const MsmGeom& g, const uint32_t* flags, hipStream_t st) {
-    ZCHK(poll_or_sync(g.n <= (1ull << 24) && !knob_flag(KNOB_MSM_NO_POLL), st, [&] {
-        for (size_t w = 0; w < g.nwin; w++)
+// The host polls the result flags of the nwin bucket sets (MsmPlan::poll_result) or waits for the stream (poll_or_sync, dev_res.hpp)
+int wait_msm_result(bool poll, size_t nwin, const uint32_t* flags, hipStream_t st) {
+    ZCHK(poll_or_sync(poll && !knob_flag(KNOB_MSM_NO_POLL), st, [&] {
+        for (size_t w = 0; w < nwin; w++)
             if (__atomic_load_n(flags + w, __ATOMIC_ACQUIRE) & MSM_FLAG_PENDING) return false;
         return true;
     }));
-    for (size_t w = 0; w < g.nwin; w++)
+    for (size_t w = 0; w < nwin; w++)
         if (flags[w] & MSM_TAIL_TIMEOUT)
             return fail(ZKP_E_DEVICE, "bucket reduction: the workgroups of the last levels did not all become resident (device shared "
                                       "with another job?); no result was produced");
@@ -313,13 +284,13 @@ void msm_host_tail(const uint32_t* host_res, size_t count, uint32_t wins_per_msm
 int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t count, size_t n, hipStream_t st, HXyzz* out,
                       const MsmFeed* feed = nullptr) {
     MsmPlan p;
-    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, feed ? &feed->ranges : nullptr, &p))
+    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, feed ? &feed->ranges : nullptr, ctx().tail_max_waves, &p))
         return fail(rc, p.error);
     if (p.lens.empty()) {
         for (size_t m = 0; m < count; m++) out[m] = HXyzz::infinity();
         return ZKP_OK;
     }
-    MsmPass pass{p, p.g, bases, d_scalars, count, feed, st, st};
+    MsmPass pass{p, bases, d_scalars, count, feed, st, st};
     ZCHK(pass.grow());
 #ifdef ZKP_MSM_CHECK
     pass.dump(n);
@@ -333,7 +304,7 @@ int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t
         return walk_rc != ZKP_OK ? walk_rc : fail(ZKP_E_DEVICE, "upload of a scalar range failed");
     }
     HIPCHK(hipGetLastError());
-    ZCHK(pass.reduce());
+    pass.reduce();
     HIPCHK(hipGetLastError());
 #ifdef ZKP_MSM_CHECK
     {
@@ -345,7 +316,7 @@ int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t
     }
 #endif
     if (count > 1 && !knob_flag(KNOB_POOL_NO_WARM)) host_pool().warm(std::chrono::microseconds(3000));  // the tails below run on the pool: wake it now
-    ZCHK(wait_msm_result(pass.g, pass.result_flags, st));
+    ZCHK(wait_msm_result(p.poll_result, p.g.nwin, pass.result_flags, st));
     msm_host_tail(reinterpret_cast<const uint32_t*>(pass.result_out), count, p.g.shared ? 1u : p.nwin1, p.g.c, p.g.glv != 0, out);  // (the pool's threads are in no context)
     return ZKP_OK;
 }

@@ -1,6 +1,8 @@
 // msm_plan.hpp -- the host-side plan of one MSM pass (msm_partial_batch, msm_host.inc): window choice, scalar ranges, the
-// geometry the kernels of msm.hpp receive and the byte size of every workspace.  Plain C++17 without HIP, so that
-// tests/host/msm_plan_table.cpp can check it with g++ alone; msm.hpp includes it for MsmGeom / SortGeom.
+// geometry the kernels of msm.hpp receive, the byte size of every workspace, and the shape of every launch: the geometry of each
+// range (range_geom), the accumulate and its fold steps (acc_launch, MsmPlan::fold), the bucket reduction (plan_reduce) and the
+// addressing of its pyramid (pyr_item, pyr_result), which the kernels call too.  Plain C++17 without HIP, so that
+// tests/host/msm_plan_table.cpp can check it with g++ alone; msm.hpp includes it (after ff.hpp: ZKP_HD).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -12,6 +14,12 @@
 #include "knobs.hpp"
 
 namespace zkp {
+
+#ifdef ZKP_HD  // (hipcc: the kernels of msm.hpp call the addressing functions below)
+#define ZKP_MSMPLAN_FN ZKP_HD
+#else
+#define ZKP_MSMPLAN_FN inline
+#endif
 
 // Two modes.  Per-window buckets (default): every c-bit window of every MSM of a batch is its own "sort window" with
 // n = ns entries and 2^(c-1) buckets.  Shared buckets (bases expanded with zkp_g1_bases_precompute): the W windows of a
@@ -53,6 +61,64 @@ constexpr uint32_t PYR_BAR_STRIDE = 32;  // words between the barrier counters o
 constexpr uint64_t SPLIT_FILL_LANES = 6 * 1024 * 64, SPLIT_FILL_QUADS = 2 * 1024 * 64 / 4 * 2;
 constexpr uint32_t MSM_MAX_SPLIT_LOG = 2;  // eight parts measured no better than four (2^16 single 0.535 against 0.529 ms, batches worse)
 static_assert(kKnobs[KNOB_MSM_SPLIT_LOG].hi == MSM_MAX_SPLIT_LOG, "ZKP_MSM_SPLIT_LOG's range");
+constexpr int MSM_THREADS = 256;
+constexpr int ACC_THREADS = 256;  // workgroup size of msm_accumulate (64 and 128 measure the same)
+constexpr uint32_t PYR_TAIL_THREADS = 256;    // four waves = 64 cooperative adds per workgroup and round
+constexpr uint32_t PYR_TAIL_BLOCKS = 16;      // workgroups per window at most (1024 adds per round)
+static_assert(kKnobs[KNOB_PYR_TAIL_THREADS].dflt == PYR_TAIL_THREADS && kKnobs[KNOB_PYR_TAIL_BLOCKS].dflt == PYR_TAIL_BLOCKS, "knobs.hpp");
+
+#ifndef ZKP_PS_TILE
+#define ZKP_PS_TILE 12288
+#endif
+// entries per tile of the first pass, as large as the 160 KB of LDS allow next to the 12 bytes per partition: 12288 entries over up to
+// 2048 partitions leave as 48..96-byte runs (147 KB; 8192: 32..64-byte runs; round 4, profiles/r04_m: together with the 16384-entry
+// second pass the sort goes 0.192 -> 0.176 ms at 2^20, 0.63 -> 0.57 at 2^22, 2.49 -> 2.3 ms at 2^24), 8192 up to 4096 partitions
+// (131 KB), 4096 up to 8192 partitions -- 24-bit windows -- (139 KB).  One workgroup per CU, no loss on small problems.
+constexpr int PS_TILE_BIG = ZKP_PS_TILE, PS_TILE_MID = 8192, PS_TILE_SMALL = 4096;
+ZKP_MSMPLAN_FN size_t partscatter_lds_bytes(uint32_t nhi, int tile) { return 8 * (size_t)tile + 2 * (size_t)tile + 4 * (size_t)(3 * nhi + 1); }
+ZKP_MSMPLAN_FN int partscatter_tile(uint32_t nhi) { return nhi <= 2048 ? PS_TILE_BIG : nhi <= 4096 ? PS_TILE_MID : PS_TILE_SMALL; }
+
+// Physical position of logical entry i of an n-entry level of the reduction pyramid (msm_pyramid_kernel): even entries in the first
+// half, odd entries in the second.  The bucket array is level 0 (n = nb, i = bucket - 1).
+ZKP_MSMPLAN_FN uint64_t pyr_pos(uint32_t i, uint32_t n) { return (uint64_t)(i >> 1) + (uint64_t)(i & 1u) * (n >> 1); }
+
+// One launch of the bucket reduction (the schedule: msm.hpp, above msm_pyramid_kernel)
+struct PyrLevel {
+    uint32_t level;  // l
+    uint32_t half;   // nb >> (l+1)
+    uint32_t nb;
+    uint32_t nwin;
+};
+ZKP_MSMPLAN_FN uint64_t odd_off(uint32_t nb, uint32_t j) { return (uint64_t)nb - (nb >> j); }
+// operands and destination of item (kind, s) of launch `level`: entry offsets inside the buffers named by the flags
+struct PyrItem {
+    uint64_t a, b, d;
+    bool src_is_pyr_out;  // kind j + 1 == level: the operands are level j's odd half, in the pyramid buffer this launch also writes
+};
+ZKP_MSMPLAN_FN PyrItem pyr_item(uint32_t nb, uint32_t level, uint32_t half, uint32_t kind, uint32_t s, uint64_t wbase) {
+    PyrItem it;
+    if (kind == 0) {
+        it.a = wbase + s;
+        it.b = wbase + half + s;
+        it.d = wbase + pyr_pos(s, half);
+        it.src_is_pyr_out = false;
+    } else {
+        const uint64_t o = wbase + odd_off(nb, kind - 1);
+        it.src_is_pyr_out = kind == level;
+        const uint64_t src = it.src_is_pyr_out ? wbase + 2 * (uint64_t)half : o;  // level j = level - 1 has 4 half entries: odd half at [2 half, 4 half)
+        it.a = src + s;
+        it.b = src + half + s;
+        it.d = o + s;
+    }
+    return it;
+}
+// Where result e of a bucket set (0: sum(B) = A_{c-1}[0]; 1 + j: U_j, j < c - 1) sits after launch c - 2: what the last-levels launch
+// and msm_collect_kernel gather.  U_{c-2} is the odd entry of the two-entry level c - 2, still in the other pyramid buffer.
+// pyr_final / odd_final: the pyramid and odd buffers of parity (c - 1) & 1, pyr_prev: the other pyramid buffer; wbase: the set's first entry
+template <class T>
+ZKP_MSMPLAN_FN T* pyr_result(T* pyr_final, T* pyr_prev, T* odd_final, uint64_t wbase, uint32_t nb, uint32_t c, uint32_t e) {
+    return e == 0 ? pyr_final + wbase : e == c - 1 ? pyr_prev + (wbase + 1) : odd_final + (wbase + odd_off(nb, e - 1));
+}
 
 // Window width: only widths dividing 256 leave no sparse top window (others 4-9x slower, profiles/r01_window_sweep.txt); below 8 bits
 // a scalar has more than 32 windows (MsmGeom::off holds 36 offsets).
@@ -119,8 +185,57 @@ struct MsmSizes {
     size_t digits, sorted, counts, entries, start, perm, over, pieces, buckets, parts, pyr1, odd0, odd1, result, host_result;
 };
 
+// The launches of the bucket reduction: levels 0 .. nlevel - 1 each as their own launch of grid (grid_x, level + 1, nwin), then ONE
+// launch of grid (tail_blocks, nwin) x tail_threads for the levels nlevel .. c - 2 and the gathering -- or, tail_blocks == 0, only
+// the gathering (msm_collect_kernel): every level ran as its own launch.
+struct PyrLaunch { uint32_t level, half, quad, grid_x; };  // quad: four lanes per add
+struct ReducePlan {
+    uint32_t nlevel, tail_blocks, tail_threads;
+    PyrLaunch level[MSM_MAX_WINDOW_BITS];
+};
+
+// The reduction of nwin bucket sets of 2^(c-1) buckets on a device that keeps tail_max_waves waves of the last-levels launch
+// resident.  Tuning aids (A/B runs): ZKP_PYR_TAIL_THREADS / _BLOCKS, workgroup size and count of that launch, and ZKP_PYR_TAIL_HALF,
+// the per-array pair count from which it takes over; out of range: ZKP_E_ARG and *error.
+inline int plan_reduce(uint32_t c, uint32_t nwin, uint32_t tail_max_waves, ReducePlan* r, const char** error) {
+    const uint32_t tail_threads = (uint32_t)knob_int(KNOB_PYR_TAIL_THREADS), tail_blocks = (uint32_t)knob_int(KNOB_PYR_TAIL_BLOCKS);
+    const uint32_t tail_half = (uint32_t)knob_int(KNOB_PYR_TAIL_HALF);
+    if (tail_threads < 64 || tail_threads > 512 || (tail_threads & 63) || !tail_blocks || tail_blocks > 256 || !tail_half) {
+        *error = "ZKP_PYR_TAIL_THREADS must be a multiple of 64 up to 512, ZKP_PYR_TAIL_BLOCKS 1..256, ZKP_PYR_TAIL_HALF >= 1";
+        return ZKP_E_ARG;
+    }
+    if (c < 1 || c > MSM_MAX_WINDOW_BITS) {  // (ReducePlan::level; plan_msm's sort geometry has refused such a width before)
+        *error = "bucket reduction: window width outside 1..24 bits";
+        return ZKP_E_ARG;
+    }
+    const uint32_t nb = 1u << (c - 1);
+    uint32_t level_tail = 0;  // first level whose per-array work is <= 64 pairs: the rest runs in one launch
+    while (level_tail + 1 < c && (nb >> (level_tail + 1)) > tail_half) level_tail++;
+    // ... unless even one workgroup per bucket set is more than the device keeps resident (many bucket sets, a partition with few
+    // CUs): the barrier of that launch would spin for its whole time-out, so every level runs as its own launch instead
+    if ((uint64_t)nwin * (tail_threads / 64) > tail_max_waves) level_tail = c - 1;
+    for (uint32_t l = 0; l < level_tail; l++) {
+        const uint32_t half = nb >> (l + 1);
+        // levels with few adds are latency-bound: four lanes per add there (threshold swept 2^14..2^20: 2^16 is the minimum)
+        const bool quad = (uint64_t)half * (l + 1) * nwin <= (1u << 16);
+        const uint32_t per = quad ? MSM_THREADS / 4 : MSM_THREADS;  // adds per workgroup
+        r->level[l] = {l, half, quad ? 1u : 0u, (half + per - 1) / per};
+    }
+    r->nlevel = level_tail;
+    r->tail_threads = tail_threads;
+    r->tail_blocks = 0;
+    if (level_tail + 1 < c) {
+        uint32_t tb = tail_blocks;
+        while (tb > 1 && (uint64_t)tb * nwin * (tail_threads / 64) > tail_max_waves) tb >>= 1;
+        r->tail_blocks = tb;
+    }
+    return ZKP_OK;
+}
+
+struct FoldStep { uint32_t pairs, lane, grid_x; };  // grid (grid_x, pairs); lane: one lane per add, else four
+
 struct MsmPlan {
-    MsmGeom g;                  // geometry of the longest range (msm_partial_batch narrows it for shorter ones)
+    MsmGeom g;                  // geometry of the longest range (range_geom narrows it for shorter ones)
     SortGeom sg;
     std::vector<uint64_t> lens; // the scalar ranges in order; empty: nothing to compute (count == 0 or n == 0)
     uint64_t range;             // the longest range: what the workspaces and the sort geometry are sized for
@@ -128,11 +243,61 @@ struct MsmPlan {
     uint32_t nwin1, over_cap, desc_cap;  // windows (slices) per scalar; oversized buckets and piece descriptors per window (msm_order)
     size_t nbuf, over_bytes;    // buffer sets of sorted / start / perm / over (2 with overlap); bytes of one set of `over`
     MsmSizes bytes;
+    FoldStep fold[MSM_MAX_SPLIT_LOG];  // g.split_log steps of buckets += parts behind every accumulate
+    ReducePlan red;
+    bool poll_result;           // the host polls the result flags instead of waiting for the stream: up to 2^24 entries per bucket set in the last range
+    int ps_tile;                // msm_partscatter_kernel<ps_tile> with ps_lds bytes of LDS: the largest tile whose staging fits next to 12 bytes per partition
+    size_t ps_lds;
     const char* error;          // the message of a refusal (plan_msm's return value != ZKP_OK)
 };
 
-// Everything msm_partial_batch decides before it touches the device.  Reads the knobs of knobs.hpp before KNOB_MSM_PLAN_END.
-inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeedRanges* feed, MsmPlan* p) {
+// THE choice between the two accumulate kernels: up to 2^20 entries four lanes per bucket -- one lane would be latency-bound by its
+// longest run (tools/small_msm_bench.py) -- and only where the buckets neither resume nor hand over (a single range)
+ZKP_MSMPLAN_FN bool acc_quad(const MsmGeom& g) { return !g.resume && !g.more && (uint64_t)g.n * g.nwin <= (1ull << 20); }
+
+// Range ridx of the walk: where its scalars start, its buffer set (the sort of range r + 1 fills the other one under overlap) and
+// the geometry its kernels receive
+struct MsmRange {
+    uint64_t off, len;
+    uint32_t ridx, set;
+    MsmGeom g;
+};
+inline MsmRange range_geom(const MsmPlan& p, size_t ridx) {
+    MsmRange r{0, p.lens[ridx], (uint32_t)ridx, p.overlap ? (uint32_t)(ridx & 1) : 0u, p.g};
+    for (size_t k = 0; k < ridx; k++) r.off += p.lens[k];
+    if (r.len != p.g.ns) {  // a range shorter than the longest (the last one, or the first of a host-fed walk): smaller geometry
+        r.g.ns = r.len;
+        r.g.n = (uint64_t)p.nwin1 * r.len;
+        r.g.chunk = (r.g.n + r.g.nchunk - 1) / r.g.nchunk;
+    }
+    r.g.resume = r.off ? 1u : 0u;
+    r.g.more = ridx + 1 < p.lens.size() ? 1u : 0u;
+    return r;
+}
+
+// grid.x of the digits, partprefix and rank launches of a range with geometry g (the sort's other grids are g.nchunk, sg.nhi and g.nwin)
+struct SortLaunch { uint32_t digits_x, prefix_x, rank_x; };
+inline SortLaunch sort_launch(const SortGeom& sg, const MsmGeom& g) {
+    return {(uint32_t)((g.ns + MSM_THREADS - 1) / MSM_THREADS), (sg.nhi + 63) / 64, (g.nb + 1023) / 1024};
+}
+
+// The accumulate of a range with geometry g: msm_accumulate_quad_kernel or msm_accumulate_kernel over a 1-D grid of
+// (bucket_blocks + extra_blocks) x nwin workgroups of ACC_THREADS, then msm_combine_kernel over (combine_x, nwin)
+struct AccLaunch { uint32_t quad, per_block, bucket_blocks, extra_blocks, grid, combine_x; };
+inline AccLaunch acc_launch(const MsmPlan& p, const MsmGeom& g) {
+    AccLaunch a;
+    a.quad = acc_quad(g) ? 1u : 0u;
+    a.per_block = a.quad ? ACC_THREADS / 4 : ACC_THREADS;
+    a.bucket_blocks = (uint32_t)((((uint64_t)g.nb << g.split_log) + a.per_block - 1) / a.per_block);
+    a.extra_blocks = std::min<uint32_t>((p.desc_cap + a.per_block - 1) / a.per_block, 64);
+    a.grid = (a.bucket_blocks + a.extra_blocks) * g.nwin;
+    a.combine_x = std::min<uint32_t>(p.over_cap, 64);
+    return a;
+}
+
+// Everything msm_partial_batch decides before it touches the device, for a device that keeps tail_max_waves waves of the
+// reduction's last-levels launch resident (plan_reduce).  Reads the knobs of knobs.hpp before KNOB_MSM_PLAN_END.
+inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeedRanges* feed, uint32_t tail_max_waves, MsmPlan* p) {
     auto refuse = [p](int code, const char* msg) { p->error = msg; return code; };
     p->lens.clear();
     if (n > bases.n) return refuse(ZKP_E_SIZE, "more scalars than bases (kzg/src/scheme.rs:86)");
@@ -213,12 +378,22 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
     p->over_bytes = ((4 * W * (2 + (size_t)p->over_cap + p->over_cap + 1) + 16 * W * (size_t)p->desc_cap) + 255) & ~(size_t)255;
     // Few buckets for the machine (a small MSM over narrow windows, single pass): 2 or 4 lanes / quads share a bucket's run
     // (msm.hpp, split_run) so that narrow windows -- a short bucket reduction -- still fill the SIMDs.
-    const uint64_t units = (uint64_t)nb * W;  // lane or quad kernel: the choice made at the accumulate launch
-    const uint64_t want_units = (uint64_t)g.n * g.nwin <= (1ull << 20) ? SPLIT_FILL_QUADS : SPLIT_FILL_LANES;
-    if (range >= n) {
+    if (range >= n) {  // (g is that single range's geometry: neither resume nor more)
+        const uint64_t units = (uint64_t)nb * W, want_units = acc_quad(g) ? SPLIT_FILL_QUADS : SPLIT_FILL_LANES;
         while (g.split_log < MSM_MAX_SPLIT_LOG && (units << g.split_log) < want_units) g.split_log++;
         g.split_log = (uint32_t)knob_int(KNOB_MSM_SPLIT_LOG, g.split_log);  // tuning aid
     }
+    // buckets += parts, pairwise: split_log steps; a step with many adds runs one lane per add, a small one four (latency): msm.hpp
+    const uint64_t cap = (uint64_t)g.nwin * g.nb, lane_from = (uint64_t)knob_int(KNOB_FOLD_LANE_MIN);
+    for (uint32_t t = 0; t < g.split_log; t++) {
+        const uint32_t pairs = 1u << (g.split_log - 1 - t), lane = cap * pairs >= lane_from ? 1u : 0u;
+        const uint32_t per = lane ? MSM_THREADS : MSM_THREADS / 4;  // adds per workgroup
+        p->fold[t] = {pairs, lane, (uint32_t)((cap + per - 1) / per)};
+    }
+    p->poll_result = range_geom(*p, lens.size() - 1).g.n <= (1ull << 24);
+    p->ps_tile = partscatter_tile(sg.nhi);
+    p->ps_lds = partscatter_lds_bytes(sg.nhi, p->ps_tile);
+    if (const int rc = plan_reduce(g.c, g.nwin, tail_max_waves, &p->red, &p->error)) return rc;
     p->bytes = MsmSizes{4 * W * entries, nbuf * 4 * W * entries, 4 * W * ((size_t)g.nchunk * sg.nhi + 2 * sg.nhi + 1 + 512),
                         8 * W * entries, nbuf * 4 * W * (nb + 2), nbuf * 4 * W * nb, nbuf * p->over_bytes,
                         256 * W * (size_t)p->desc_cap, 256 * W * nb, 256 * W * nb * ((1u << g.split_log) - 1),
