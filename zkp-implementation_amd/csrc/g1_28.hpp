@@ -76,17 +76,24 @@ ZKP_DEV void pmul2(const Fq28& a0, const Fq28& b0, const Fq28& a1, const Fq28& b
 }
 template <bool CHAIN>
 ZKP_DEV Fq28 psqr(const Fq28& a) { return CHAIN ? fq28_sqr_chain(a) : sqr(a); }
+// (xyzz_finish_neg takes 8p - S1 in any limb form below 2^30 where xyzz_finish takes S1, and R with limbs small enough for the
+// two-product reduction below -- g1_28_madd has both; the products see the same integers, so X3 and Y3 are the same limbs)
 template <bool CHAIN = false>
-ZKP_DEV void xyzz_finish(Fq28& x3, Fq28& y3, const Fq28& r, const Fq28& pp, const Fq28& ppp, const Fq28& u1,
-                         const Fq28& s1) {
+ZKP_DEV void xyzz_finish_neg(Fq28& x3, Fq28& y3, const Fq28& rn, const Fq28& pp, const Fq28& ppp, const Fq28& u1,
+                             const Fq28& ns1) {
     Fq28 q = pmul<CHAIN>(u1, pp);                       // tight
-    const Fq28 rn = normalise(r);                       // for the squaring and for the two-product reduction below
     Fq28 rr = psqr<CHAIN>(rn);                          // tight (r < 12p: 144 / 2520)
     x3 = normalise(sub8w(sub4(rr, ppp), q + q));        // limbs < 2^32 before, see fq28.hpp
     Fq28 t = sub16(q, x3);                              // < 18p, limbs < 2^30
     // Y3 = R t + (8p - S1) PPP with one reduction (fq28_mul2): limbs 2^28 x 2^30 and 2^30 x 2^28, (18 * 18 + 8 * 2) p^2 <= 2520 p^2;
     // the result is tight, which is inside the "< 6p, limbs < 2^28" contract of a stored Y
-    y3 = CHAIN ? fq28_mul2_chain(rn, t, sub8(Fq28::zero(), s1), ppp) : fq28_mul2(rn, t, sub8(Fq28::zero(), s1), ppp);
+    y3 = CHAIN ? fq28_mul2_chain(rn, t, ns1, ppp) : fq28_mul2(rn, t, ns1, ppp);
+}
+template <bool CHAIN = false>
+ZKP_DEV void xyzz_finish(Fq28& x3, Fq28& y3, const Fq28& r, const Fq28& pp, const Fq28& ppp, const Fq28& u1,
+                         const Fq28& s1) {
+    // R normalised: for the squaring and for the two-product reduction
+    xyzz_finish_neg<CHAIN>(x3, y3, normalise(r), pp, ppp, u1, sub8(Fq28::zero(), s1));
 }
 
 // 2 * (x, y) for an affine point (mdbl-2008-s-1, a = 0)
@@ -138,22 +145,34 @@ ZKP_DEV void g1_28_madd(X28& acc, const A28& q) {
     Fq28 u2, s2;
     pmul2<CHAIN>(q.x, acc.zz, q.y, acc.zzz, u2, s2);  // tight; 4 * 2 / 2520 -> tight
     Fq28 p = sub16(u2, acc.x);           // < 18p
-    Fq28 r = sub8(s2, acc.y);            // < 10p
+    // 8p - S1 once, for R = S2 + (8p - S1) and for the second product of Y3 (xyzz_finish_neg).  Pinned: left alone the compiler forms
+    // (S2 - S1) + 8p for R and 8p - S1 again for Y3, 42 instructions where 28 do.  neg8 and not sub8: the same integers -- hence the same
+    // RR, X3 and Y3, limb for limb -- with the limbs of R below 3 * 2^28, and R enters the products as it is, not normalised: its squaring
+    // takes limbs below 2^30, and a column of R t + (8p - S1) PPP stays below 14 (3 * 2^28 * 2^30 + 2^29 * 2^28 + 2^56) + 2^36 < 2^64
+    // (tests/test_acc_bounds_cpu.py; the normalisation was a chain of 39 dependent instructions per insertion).
+    Fq28 ns1 = pinned(neg8(acc.y));
+    Fq28 r = s2 + ns1;                   // < 10p, limbs < 3 * 2^28
     Fq28 pp = psqr<CHAIN>(p);            // 324 / 2520 -> tight
-    if (tight_is_zero_mod_p(pp)) {       // P == 0: same x
+    // P == 0: same x.  Every limb of P is positive (those of 16p in sub16 exceed 2^28 > limbs of a stored X), so P^2 > 0 and its
+    // reduced product -- an exact quotient of P^2 + m p -- is not the integer 0: only p itself is left to compare with.
+    if (tight_positive_is_zero_mod_p(pp)) {
         if (tight_is_zero_mod_p(sqr(r))) acc = g1_28_double_affine(q);
         else acc = X28::infinity();
         return;
     }
     Fq28 ppp = pmul<CHAIN>(p, pp);
     Fq28 x3, y3;
-    xyzz_finish<CHAIN>(x3, y3, r, pp, ppp, acc.x, acc.y);
+    xyzz_finish_neg<CHAIN>(x3, y3, r, pp, ppp, acc.x, ns1);
     acc.x = x3;
     acc.y = y3;
-    Fq28 zz3, zzz3;
-    pmul2<CHAIN>(acc.zz, pp, acc.zzz, ppp, zz3, zzz3);
-    acc.zz = zz3;
-    acc.zzz = zzz3;
+    if (CHAIN) {
+        fq28_mul_chain2_inplace(acc.zz, pp, acc.zzz, ppp);
+    } else {
+        Fq28 zz3, zzz3;
+        pmul2<CHAIN>(acc.zz, pp, acc.zzz, ppp, zz3, zzz3);
+        acc.zz = zz3;
+        acc.zzz = zzz3;
+    }
 }
 
 // acc += q where acc is still the AFFINE point the first insertion into an empty bucket left (ZZ = ZZZ = 1 implied, x canonical,

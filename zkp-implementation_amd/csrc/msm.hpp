@@ -598,15 +598,16 @@ ZKP_DEV void msm_accumulate_run(const uint4* __restrict__ bases28, const uint32_
         return;
     }
     X28 acc = resume ? X28::load_s(src, src_stride) : X28::infinity();
+    // entry = slice * ns + i  ->  plane `slice` of the expanded bases, point i: pt + slice * (plane_stride - ns), the slice by a
+    // multiply-high with the reciprocal made here, once per run of a wave (plane_div, msm_plan.hpp: pt, ns < 2^31)
+    const PlaneDiv pd = plane_div_make(g.shared ? (uint32_t)g.ns : 1u);
+    const uint64_t plane_gap = g.plane_stride - g.ns;
     auto locate = [&](uint32_t e) {
         uint64_t pt = e & 0x7fffffffu;
 #ifdef ZKP_MSM_CHECK
         if (pt >= g.n && msm_check_fail(2, e, (uint32_t)g.n)) pt = 0;
 #endif
-        if (g.shared) {  // entry = slice * ns + i  ->  plane `slice` of the expanded bases, point i (32-bit divide: ns < 2^31)
-            const uint32_t ns32 = (uint32_t)g.ns, s = (uint32_t)pt / ns32;
-            pt = (uint64_t)s * g.plane_stride + ((uint32_t)pt - s * ns32);
-        }
+        if (g.shared) pt += (uint64_t)plane_div(pd, (uint32_t)pt) * plane_gap;
         return bases28 + pt * 8;
     };
     uint32_t k = lo;

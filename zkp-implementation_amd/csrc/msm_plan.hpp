@@ -82,6 +82,20 @@ ZKP_MSMPLAN_FN int partscatter_tile(uint32_t nhi) { return nhi <= 2048 ? PS_TILE
 // half, odd entries in the second.  The bucket array is level 0 (n = nb, i = bucket - 1).
 ZKP_MSMPLAN_FN uint64_t pyr_pos(uint32_t i, uint32_t n) { return (uint64_t)(i >> 1) + (uint64_t)(i & 1u) * (n >> 1); }
 
+// Plane of a shared-mode entry (msm_accumulate_run): pt / ns for pt, ns < 2^31 with ONE multiply-high by m = floor((2^32 - 1) / ns),
+// made once per run, and a one-step correction: 7 instructions per insertion where the 32-bit division took 15 (two correction steps and
+// a remainder, its reciprocal already hoisted by the compiler; profiles/acc_insertion_overhead.md).
+// m ns >= 2^32 - ns, so pt m / 2^32 >= pt / ns - pt / 2^32 > pt / ns - 1/2: the estimate is floor(pt / ns) or one below it, never
+// above (m <= 2^32 / ns), and r = pt - q ns < 2 ns < 2^32 does not wrap.  tests/host/locate_div.cpp checks it against `/`.
+struct PlaneDiv {
+    uint32_t ns, m;
+};
+ZKP_MSMPLAN_FN PlaneDiv plane_div_make(uint32_t ns) { return PlaneDiv{ns, ns ? 0xffffffffu / ns : 0u}; }
+ZKP_MSMPLAN_FN uint32_t plane_div(const PlaneDiv& d, uint32_t pt) {
+    const uint32_t q = (uint32_t)(((uint64_t)pt * d.m) >> 32);
+    return q + (pt - q * d.ns >= d.ns ? 1u : 0u);
+}
+
 // One launch of the bucket reduction (the schedule: msm.hpp, above msm_pyramid_kernel)
 struct PyrLevel {
     uint32_t level;  // l
