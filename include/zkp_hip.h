@@ -354,7 +354,8 @@ int zkp_selftest_fq_inverse_dev(const void *d_in, size_t n, int form, void *d_ou
  * words (128 B per case, unused words zero); an operand fills the first words of its slot.  d_out must not be d_in.
  *   zkp_selftest_fq28_dev  14 x 28-bit limbs, radix 2^392: the six product forms (0 fq28_mul_inline, 1 fq28_mul_chain, 2 fq28_mul_chain2
  *                          = two products, 3 sqr, 4 fq28_sqr_chain, 5 fq28_mul2, 6 fq28_mul2_chain), 7 normalise, 8 sub4, 9 sub8, 10 sub16,
- *                          11 sub8w, 12 neg4, 13 tight_is_zero_mod_p (word 0), 14 fq28_from_sat (12 words in)
+ *                          11 sub8w, 12 neg4, 13 tight_is_zero_mod_p (word 0), 14 fq28_from_sat (12 words in), 15 fq28_mul_chain2_inplace
+ *                          = the two products of 2, each written over its first operand
  *   zkp_selftest_fr29_dev  9 x 29-bit limbs, radix 2^261: 0 operator*, 1 fr29_mul2 = two products, 2 fr29_to_canonical (8 words out),
  *                          3 the memory-form Fr operator* (8 words in and out), 4 sub_tight, 5 sub_wide8, 6 normalise, 7 fr29_pack_tight,
  *                          8 fr29_from_sat_shl5, 9 fr29_twiddle_from_mont, 10 fr29_from_sat

@@ -1,11 +1,22 @@
-"""A small interpreter for the generated asm statements of csrc/*_asm.inc (tools/gen_fq28_mul_asm.py, tools/gen_fr29_mul2_asm.py).
+"""A small interpreter for the generated asm statements of csrc/*_asm.inc (tools/gen_mont_asm.py).
 
 It executes the committed TEXT: the instruction lines with their %N operand numbers, bound to C expressions by the constraint lists at
-the end of the statement.  Seven opcodes occur; anything else is an error.  Every v_mad_u64_u32 whose exact result needs more than 64
+the end of the statement.  Seven opcodes and the constraints "=&v", "+v", "v", "s" occur; anything else is an error.  Every v_mad_u64_u32 whose exact result needs more than 64
 bits is counted in `overflows` (the hardware would drop the carry into vcc, which nothing reads)."""
 import re
 
 M32, M64 = (1 << 32) - 1, (1 << 64) - 1
+
+
+def bind(line, known):
+    """one constraint line -> [(constraint, C expression)]; every "..."(...) group on it must parse, with a constraint from `known`"""
+    ops = []
+    for group in line.strip().lstrip(":").strip().split(", "):
+        m = re.fullmatch(r'"([^"]*)"\(([^(),]+)\)', group)
+        if not m or m.group(1) not in known:
+            raise ValueError(f"operand outside the interpreter (constraints {known}): {group}")
+        ops.append(m.groups())
+    return ops
 
 
 class Asm:
@@ -13,13 +24,15 @@ class Asm:
         self.lines = re.findall(r'^\s*"([^"\\]+)\\n\\t"', text, flags=re.M)
         tail = text[text.rindex('\\n\\t"'):]
         outs, ins, _clob = [x for x in tail.split("\n") if x.strip().startswith(":")]
-        bind = lambda s: re.findall(r'"[=&a-z]+"\(([^)]*)\)', s)
-        self.outs, self.ins = bind(outs), bind(ins)
+        outs, ins = bind(outs, ("=&v", "+v")), bind(ins, ("v", "s"))
+        self.outs, self.ins = [e for _, e in outs], [e for _, e in ins]
+        self.inouts = [i for i, (con, _) in enumerate(outs) if con == "+v"]      # read-write: seeded from env, read back at the end
         assert self.lines and self.outs and self.ins
 
     def run(self, env, lines=None):
-        """env: C expression -> value for every input operand (e.g. "a.l[3]", "Fq28C::MOD[0]").  -> ({output expression: value}, overflows)"""
-        reg = {}
+        """env: C expression -> value for every input and read-write operand (e.g. "a.l[3]", "Fq28C::MOD[0]").
+        -> ({output expression: value}, overflows)"""
+        reg = {f"%{i}": env[self.outs[i]] & M32 for i in self.inouts}
         for i, e in enumerate(self.ins):
             reg[f"%{len(self.outs) + i}"] = env[e] & M32
         overflows = 0

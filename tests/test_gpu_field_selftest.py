@@ -58,12 +58,22 @@ def test_fq28_product(zkp, op):
     check(run_field(zkp, "fq28", op, cases), [L.fq28_mul(a, b) for a, b in cases], 14)
 
 
-def test_fq28_mul_chain2(zkp):
-    """fq28_mul_chain2: two interleaved products per lane"""
+def fq28_mul_quads():
     c = V.fq28_mul_cases()
     c = c + c[:1] if len(c) % 2 else c
-    quads = [(c[i][0], c[i][1], c[-1 - i][0], c[-1 - i][1]) for i in range(len(c))]
+    return [(c[i][0], c[i][1], c[-1 - i][0], c[-1 - i][1]) for i in range(len(c))]
+
+
+def test_fq28_mul_chain2(zkp):
+    """fq28_mul_chain2: two interleaved products per lane"""
+    quads = fq28_mul_quads()
     check(run_field(zkp, "fq28", "mul_chain2", quads), [(L.fq28_mul(a, b), L.fq28_mul(cc, d)) for a, b, cc, d in quads], 14, 14)
+
+
+def test_fq28_mul_chain2_inplace(zkp):
+    """fq28_mul_chain2_inplace: the same two products, each written over its first operand (slot 0 = a b, slot 1 = c d)"""
+    quads = fq28_mul_quads()
+    check(run_field(zkp, "fq28", "mul_chain2_inplace", quads), [(L.fq28_mul(a, b), L.fq28_mul(cc, d)) for a, b, cc, d in quads], 14, 14)
 
 
 @pytest.mark.parametrize("op", ["sqr", "sqr_chain"])

@@ -148,7 +148,9 @@ def test_curve_formulas_are_the_group_law_and_keep_the_invariants():
 
 
 # ------------------------------------------------------------------------------------------------ the generated asm text
-INC = {"mul": "fq28_mul_asm.inc", "mul2x": "fq28_mul2x_asm.inc", "sqr": "fq28_sqr_asm.inc", "mul2": "fq28_mul2_asm.inc", "fr": "fr29_mul2_asm.inc"}
+G = load(os.path.join(ROOT, "tools", "gen_mont_asm.py"), "gen_mont_asm")
+# kind -> file, one per generated statement: fq28_mul2x_asm.inc is "mul2x"; the one Fr statement, fr29_mul2_asm.inc, is "fr"
+INC = {"fr" if name.startswith("fr29_") else name[len("fq28_"):-len("_asm.inc")]: name for name in G.VARIANTS}
 
 
 def asm(kind):
@@ -160,58 +162,80 @@ def run_fq(prog, lines=None, **ops):
     return out, ov
 
 
+def run_fr(prog, lines=None, **ops):
+    return prog.run(A.env_of(L.FR, "Fr29C", **ops), lines)
+
+
+def pairs(cases):
+    return zip(cases[::2], cases[1::2])
+
+
+def wrong(result, **want):
+    """result of a run, the model's limbs per output name -> True when a multiply-add carried out or an output differs"""
+    out, ov = result
+    return ov != 0 or any(A.limbs_of(out, name, len(limbs)) != limbs for name, limbs in want.items())
+
+
+# kind -> (prog, lines) -> number of mismatching cases on the statement's vectors.  Every statement of VARIANTS needs an entry.
+COMPARE = {
+    "mul": lambda p, l: sum(wrong(run_fq(p, l, a=a, b=b), r=L.fq28_mul(a, b)) for a, b in V.fq28_mul_cases()),
+    "mul2x": lambda p, l: sum(wrong(run_fq(p, l, a0=a0, b0=b0, a1=a1, b1=b1), r0=L.fq28_mul(a0, b0), r1=L.fq28_mul(a1, b1))
+                              for (a0, b0), (a1, b1) in pairs(V.fq28_mul_cases())),
+    "mul2x_inplace": lambda p, l: sum(wrong(run_fq(p, l, a0=a0, b0=b0, a1=a1, b1=b1), a0=L.fq28_mul(a0, b0), a1=L.fq28_mul(a1, b1))
+                                      for (a0, b0), (a1, b1) in pairs(V.fq28_mul_cases())),
+    "sqr": lambda p, l: sum(wrong(run_fq(p, l, a=a), r=L.fq28_sqr(a)) for a in V.fq28_sqr_cases()),
+    "mul2": lambda p, l: sum(wrong(run_fq(p, l, a=a, b=b, c=c, d=d), r=L.fq28_mul2(a, b, c, d)) for a, b, c, d in V.fq28_mul2_cases()),
+    "fr": lambda p, l: sum(wrong(run_fr(p, l, a0=a0, b0=b0, a1=a1, b1=b1), r0=L.fr29_mul(a0, b0), r1=L.fr29_mul(a1, b1))
+                                  for (a0, b0), (a1, b1) in pairs(V.fr29_mul_cases())),
+}
+
+
 def compare_all(kinds=tuple(INC), lines=None):
     """The .inc files on their vectors against the model -> number of mismatching cases per file (0 for the committed text).
     lines: {kind: instruction lines to run instead of the file's own}"""
-    progs = {k: asm(k) for k in kinds}
-    lines = lines or {}
-    bad = dict.fromkeys(kinds, 0)
-    mul = V.fq28_mul_cases() if {"mul", "mul2x"} & set(kinds) else []
-    for a, b in mul if "mul" in kinds else []:
-        out, ov = run_fq(progs["mul"], lines.get("mul"), a=a, b=b)
-        bad["mul"] += ov != 0 or A.limbs_of(out, "r", 14) != L.fq28_mul(a, b)
-    for (a0, b0), (a1, b1) in zip(mul[::2], mul[1::2]) if "mul2x" in kinds else []:
-        out, ov = run_fq(progs["mul2x"], lines.get("mul2x"), a0=a0, b0=b0, a1=a1, b1=b1)
-        bad["mul2x"] += ov != 0 or A.limbs_of(out, "r0", 14) != L.fq28_mul(a0, b0) or A.limbs_of(out, "r1", 14) != L.fq28_mul(a1, b1)
-    for a in V.fq28_sqr_cases() if "sqr" in kinds else []:
-        out, ov = run_fq(progs["sqr"], lines.get("sqr"), a=a)
-        bad["sqr"] += ov != 0 or A.limbs_of(out, "r", 14) != L.fq28_sqr(a)
-    for a, b, c, d in V.fq28_mul2_cases() if "mul2" in kinds else []:
-        out, ov = run_fq(progs["mul2"], lines.get("mul2"), a=a, b=b, c=c, d=d)
-        bad["mul2"] += ov != 0 or A.limbs_of(out, "r", 14) != L.fq28_mul2(a, b, c, d)
-    fr = V.fr29_mul_cases() if "fr" in kinds else []
-    for (a0, b0), (a1, b1) in zip(fr[::2], fr[1::2]):
-        out, ov = progs["fr"].run(A.env_of(L.FR, "Fr29C", a0=a0, b0=b0, a1=a1, b1=b1), lines.get("fr"))
-        bad["fr"] += ov != 0 or A.limbs_of(out, "r0", 9) != L.fr29_mul(a0, b0) or A.limbs_of(out, "r1", 9) != L.fr29_mul(a1, b1)
-    return bad
+    return {k: COMPARE[k](asm(k), (lines or {}).get(k)) for k in kinds}
+
+
+def test_every_generated_statement_is_listed_once():
+    """the *_asm.inc files of csrc/, the generator's VARIANTS, what fq28.hpp and fr29.hpp include, and the comparisons above: one set"""
+    on_disk = {f for f in os.listdir(CSRC) if f.endswith("_asm.inc")}
+    included = {m for h in ("fq28.hpp", "fr29.hpp") for m in re.findall(r'#include "(\w+\.inc)"', open(os.path.join(CSRC, h)).read())}
+    assert on_disk == set(G.VARIANTS) == included
+    assert set(COMPARE) == set(INC) and len(INC) == len(G.VARIANTS)
 
 
 def test_asm_text_equals_the_model_bit_for_bit():
-    assert compare_all() == dict.fromkeys(INC, 0)
+    assert len(INC) >= 6 and compare_all() == dict.fromkeys(INC, 0)
 
 
 def test_no_multiply_add_carries_out_at_the_documented_limb_bounds():
-    m28, m29, m30, m31 = [(1 << k) - 1 for k in (28, 29, 30, 31)]
+    m28, m29, m30, m31, m32 = [(1 << k) - 1 for k in (28, 29, 30, 31, 32)]
     assert run_fq(asm("mul"), a=[m30] * 14, b=[m30] * 14)[1] == 0
     assert run_fq(asm("mul2x"), a0=[m30] * 14, b0=[m30] * 14, a1=[m30] * 14, b1=[m30] * 14)[1] == 0
+    assert run_fq(asm("mul2x_inplace"), a0=[m30] * 14, b0=[m30] * 14, a1=[m30] * 14, b1=[m30] * 14)[1] == 0
     assert run_fq(asm("sqr"), a=[m30] * 14)[1] == 0
     assert run_fq(asm("mul2"), a=[m28] * 14, b=[m30] * 14, c=[m30] * 14, d=[m28] * 14)[1] == 0
     assert run_fq(asm("mul2"), a=[m29] * 14, b=[m29] * 14, c=[m29] * 14, d=[m29] * 14)[1] == 0
-    assert asm("fr").run(A.env_of(L.FR, "Fr29C", a0=[m31] * 9, b0=[m29] * 9, a1=[m31] * 9, b1=[m29] * 9))[1] == 0
+    assert run_fr(asm("fr"), a0=[m31] * 9, b0=[m29] * 9, a1=[m31] * 9, b1=[m29] * 9)[1] == 0
     # and the count means something: one more bit on one side carries out
-    assert run_fq(asm("mul"), a=[(1 << 32) - 1] * 14, b=[m30] * 14)[1] > 0
+    assert run_fq(asm("mul"), a=[m32] * 14, b=[m30] * 14)[1] > 0
+    assert run_fq(asm("mul2x_inplace"), a0=[m32] * 14, b0=[m30] * 14, a1=[m30] * 14, b1=[m30] * 14)[1] > 0
     assert run_fq(asm("sqr"), a=[m31] * 14)[1] > 0
     assert run_fq(asm("mul2"), a=[m30] * 14, b=[m30] * 14, c=[m30] * 14, d=[m30] * 14)[1] > 0
-    assert asm("fr").run(A.env_of(L.FR, "Fr29C", a0=[(1 << 32) - 1] * 9, b0=[m31] * 9, a1=[m31] * 9, b1=[m29] * 9))[1] > 0
+    assert run_fr(asm("fr"), a0=[m32] * 9, b0=[m31] * 9, a1=[m31] * 9, b1=[m29] * 9)[1] > 0
 
 
 def test_committed_asm_is_what_the_generators_produce():
-    gq = load(os.path.join(ROOT, "tools", "gen_fq28_mul_asm.py"), "gen_fq28")
-    gr = load(os.path.join(ROOT, "tools", "gen_fr29_mul2_asm.py"), "gen_fr29")
-    want = {"mul": gq.gen(1, 164)[0], "mul2x": gq.gen(2, 164)[0], "sqr": gq.gen_special("sqr", 164)[0], "mul2": gq.gen_special("mul2", 164)[0],
-            "fr": gr.gen(2)[0]}
-    for kind, text in want.items():
-        assert open(os.path.join(CSRC, INC[kind]), "rb").read() == text.encode(), INC[kind]
+    for name, variant in G.VARIANTS.items():
+        assert open(os.path.join(CSRC, name), "rb").read() == G.statement(*variant)[0].encode(), name
+
+
+def test_the_interpreter_refuses_a_constraint_it_does_not_know():
+    text = open(os.path.join(CSRC, INC["mul2x_inplace"])).read()
+    for bad in (text.replace('"+v"(a1.l[3])', '"+&v"(a1.l[3])'), text.replace('"s"(Fq28C::INV)', '"n"(Fq28C::INV)')):
+        assert bad != text
+        with pytest.raises(ValueError):
+            A.Asm(bad)
 
 
 def _mutations(prog, mod_first, mask):

@@ -9,9 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libzkp_hip.so")
 SOURCES = ["api.hip", "selftest.hip"]
-DEPS = ["api.hip", "ff.hpp", "fq28.hpp", "fq28_inv.hpp", "fr29.hpp", "fr29_mul2_asm.inc", "fq28_mul_asm.inc", "fq28_mul2x_asm.inc", "fq28_mul2x_inplace_asm.inc", "fq28_sqr_asm.inc", "fq28_mul2_asm.inc", "g1.hpp", "g1_28.hpp", "msm.hpp", "ntt.hpp", "ntt_plan.hpp", "ntt_host.inc", "plonk.hpp",
-        "plonk_host.inc", "plonk_compile_host.inc", "ntt_sharded.inc", "ntt_shard_plan.hpp", "fri.hpp", "fri_host.inc", "fri_fr.hpp", "transcript_host.hpp", "pairing_host.hpp", "verify_host.inc", "host_ff.hpp", "kzg_host.hpp", "host_threads.hpp", "knobs.hpp", "msm_plan.hpp", "glv.hpp", "g1_check.hpp", "g1_check_host.inc", "g1_ntt.hpp", "g1_ntt_plan.hpp", "g1_ntt_host.inc", "msm_host.inc", "nova.hpp", "nova_host.inc", "dev_res.hpp", "selftest.hpp", "selftest.hip",
-        os.path.join("..", "..", "include", "zkp_hip.h")]
+# what the library is built from: every source file of csrc/ and the public header (paths relative to csrc/)
+DEPS = sorted(f for f in os.listdir(SRC) if f.endswith((".hip", ".hpp", ".inc"))) + [os.path.join("..", "..", "include", "zkp_hip.h")]
 
 
 STAMP = OUT + ".srchash"  # hash of the sources the library was built from (mtimes do not survive the copy to the GPU box)

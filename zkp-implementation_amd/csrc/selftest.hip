@@ -34,6 +34,11 @@ __global__ __launch_bounds__(ST_THREADS) void selftest_fq28_kernel(const uint4* 
         for (int w = 0; w < 12; w++) s.l[w] = a.l[w];
         r0 = fq28_from_sat(s);
     }
+    if constexpr (OP == ST_FQ28_MUL_CHAIN2_INPLACE) {
+        r0 = a;
+        r1 = c;
+        fq28_mul_chain2_inplace(r0, b, r1, d);
+    }
     r0.store(out + 8 * i);
     r1.store(out + 8 * i + 4);
 }

@@ -36,7 +36,8 @@ enum StFq28Op : int {
     ST_FQ28_NEG4 = 12,       // r0 = neg4(a)
     ST_FQ28_IS_ZERO = 13,    // r0 word 0 = tight_is_zero_mod_p(a)
     ST_FQ28_FROM_SAT = 14,   // r0 = fq28_from_sat(first 12 words of slot a)
-    ST_FQ28_OPS = 15
+    ST_FQ28_MUL_CHAIN2_INPLACE = 15,  // fq28_mul_chain2_inplace(a, b, c, d); r0 = a, r1 = c
+    ST_FQ28_OPS = 16
 };
 enum StFr29Op : int {
     ST_FR29_MUL = 0,            // r0 = a * b

@@ -459,7 +459,7 @@ def selftest_fq_inverse_dev(in_tensor, n, form, out_tensor, stream=None):
 # operation numbers of the lane-level self-tests (the enums of csrc/selftest.hpp; tests/test_limb_model_cpu.py compares the two)
 SELFTEST_OPS = {
     "fq28": {"mul_inline": 0, "mul_chain": 1, "mul_chain2": 2, "sqr": 3, "sqr_chain": 4, "mul2": 5, "mul2_chain": 6, "normalise": 7,
-             "sub4": 8, "sub8": 9, "sub16": 10, "sub8w": 11, "neg4": 12, "is_zero": 13, "from_sat": 14},
+             "sub4": 8, "sub8": 9, "sub16": 10, "sub8w": 11, "neg4": 12, "is_zero": 13, "from_sat": 14, "mul_chain2_inplace": 15},
     "fr29": {"mul": 0, "mul2": 1, "to_canonical": 2, "fr_mul": 3, "sub_tight": 4, "sub_wide8": 5, "normalise": 6, "pack_tight": 7,
              "from_sat_shl5": 8, "twiddle": 9, "from_sat": 10},
     "fp": {"add": 0, "sub": 1, "neg": 2, "dbl": 3, "mul": 4, "mont_mul": 5},
