@@ -40,7 +40,10 @@
  * tuning aid), ZKP_KZG_COSET_GROUP_LOG (0..3: log2 of the terms one lane of an opener's multiply-accumulate pass sums, read by
  * zkp_kzg_opener_create_cosets, default 0, without effect at log_l = 0; tuning aid), ZKP_KZG_OPENER_MAX_BYTES (zkp_kzg_opener_create
  * and zkp_kzg_opener_create_cosets refuse, with ZKP_E_NOMEM and the sizes in zkp_last_error(), an opener that needs more device
- * memory than this many bytes; default: no limit).
+ * memory than this many bytes; default: no limit), ZKP_KZG_RECOVER_LEAF_LOG (1..8: log2 of the factors of the vanishing polynomial
+ * a leaf workgroup of a recoverer multiplies, read by zkp_kzg_recoverer_create; tuning aid), ZKP_KZG_RECOVER_MAX_BYTES
+ * (zkp_kzg_recoverer_create refuses, with ZKP_E_NOMEM and the sizes in zkp_last_error(), a recoverer whose device workspace is larger
+ * than this many bytes; default: no limit).
  */
 #ifndef ZKP_HIP_H
 #define ZKP_HIP_H
@@ -332,6 +335,37 @@ int zkp_kzg_open_cosets_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_
 int zkp_kzg_verify_coset(const zkp_bases *srs, const uint64_t g2_sl_xy[24], const uint64_t commit_xy[12], uint8_t commit_is_inf,
                          const uint64_t w_xy[12], uint8_t w_is_inf, const uint64_t x[4], unsigned log_l, const uint64_t *evals,
                          int *accepted);
+/* Cell recovery: the polynomial f of `len` coefficients from the values of any (r - m) cosets with (r - m) l >= len, in the notation of
+ * the coset openings (n = 2^log_n, l = 2^log_l, r = n / l; coset k < r holds the indices k + j r of a natural-order evaluation
+ * vector).  Fr only, no SRS: with Zs(Y) = prod over the m missing cosets k of (Y - rho^k), rho = w^l, the vanishing polynomial of
+ * the missing points is Zs(X^l); the values times Zs(rho^(i mod r)), zero on the missing cosets, are those of f Zs(X^l), whose
+ * coefficients are divided by Zs((g X)^l) on the coset g = 7 of the domain.  Zs is built on the device as a product tree (leaves
+ * of 2^ZKP_KZG_RECOVER_LEAF_LOG factors in a workgroup, batched transforms above: O(m log^2 m) products), and a call costs two
+ * transforms of r and three of n (four with out_evals) besides.
+ * zkp_kzg_recoverer_create: a handle on the calling thread's slot (zkp_set_device; slot 0 by default) that owns every workspace
+ * (32 B x (n + 5 r) + 5 r bytes on the device, 5 r bytes pinned) and has built every plan and table a call uses.  1 <= log_n - log_l
+ * and log_n <= 23, else ZKP_E_ARG; a workspace larger than the device has free or than ZKP_KZG_RECOVER_MAX_BYTES is ZKP_E_NOMEM
+ * with the sizes in zkp_last_error() and nothing left allocated; no device: ZKP_E_DEVICE (there is no host path).
+ * zkp_kzg_recover_cosets: evals n x 4 limbs in natural order, present r bytes (0: the coset is missing; the 32 bytes at its
+ * positions are not read), out_coeffs len x 4 limbs, out_evals n x 4 limbs or NULL -- f on the whole domain, the missing cells filled
+ * in (the transform of the zero-padded result).  *consistent = 1 iff the present values are those of a polynomial of `len`
+ * coefficients (exact: no recovered coefficient at an index >= len is non-zero; with (r - m) l == len every input is consistent);
+ * out_coeffs is the low part of the interpolant either way.  Present values are used as given.  len == 0 is ZKP_E_ARG, len > n
+ * ZKP_E_SIZE, (r - m) l < len ZKP_E_SIZE naming the present cells, l and len.  m = 0 is one inverse transform and the check.
+ * zkp_kzg_recover_cosets_dev: d_evals, d_out_coeffs, d_out_evals (or NULL) and the word *d_inconsistent (set to 0 or 1) are memory
+ * of the recoverer's device, `present` is HOST memory (the schedule depends on m) and is read before the call returns.  It neither
+ * allocates nor waits for the device, except for the previous call's copy of the mask out of the handle's staging buffer; calls
+ * on one handle are serialised with its slot.  (The tables of its three shifted transforms sit in the slot's cache of 8 coset
+ * tables: a call that finds them evicted by other shifted transforms of the slot rebuilds them first.)  While profiling is on a call records the phases "kzg_recover_zs" (the vanishing
+ * polynomial and its values on both domains) and "kzg_recover_rest" (the transforms of n and the pointwise passes); the transforms
+ * record "ntt_fr_pass" inside both. */
+typedef struct zkp_kzg_recoverer zkp_kzg_recoverer;
+int zkp_kzg_recoverer_create(unsigned log_n, unsigned log_l, zkp_kzg_recoverer **out);
+void zkp_kzg_recoverer_destroy(zkp_kzg_recoverer *rc);
+int zkp_kzg_recover_cosets(const zkp_kzg_recoverer *rc, const uint64_t *evals, const uint8_t *present, size_t len,
+                           uint64_t *out_coeffs, uint64_t *out_evals, int *consistent);
+int zkp_kzg_recover_cosets_dev(const zkp_kzg_recoverer *rc, const void *d_evals, const uint8_t *present, size_t len,
+                               void *d_out_coeffs, void *d_out_evals, uint32_t *d_inconsistent, void *stream);
 
 /* ---- single scalar multiplication: KzgScheme::commit_para, kzg/src/scheme.rs:78-82 (`g1_0.mul(para)`),
  *      6x per proof at plonk/src/prover.rs:183-188.  Serial by nature: computed on the host. ---- */

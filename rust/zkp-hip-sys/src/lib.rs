@@ -19,6 +19,7 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_nova_r1cs { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_kzg_opener { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_kzg_recoverer { _private: [u8; 0] }
 
 /// how a bases handle is expanded (zkp_g1_bases_expansion); all zero when it is not
 #[repr(C)]
@@ -169,6 +170,10 @@ extern "C" {
     pub fn zkp_kzg_open_cosets(o: *const zkp_kzg_opener, coeffs: *const u64, len: usize, out_xy: *mut u64, out_is_inf: *mut u8, out_evals: *mut u64) -> i32;
     pub fn zkp_kzg_open_cosets_dev(o: *const zkp_kzg_opener, d_coeffs: *const c_void, len: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, d_out_evals: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_kzg_verify_coset(srs: *const zkp_bases, g2_sl_xy: *const u64, commit_xy: *const u64, commit_is_inf: u8, w_xy: *const u64, w_is_inf: u8, x: *const u64, log_l: u32, evals: *const u64, accepted: *mut i32) -> i32;
+    pub fn zkp_kzg_recoverer_create(log_n: u32, log_l: u32, out: *mut *mut zkp_kzg_recoverer) -> i32;
+    pub fn zkp_kzg_recoverer_destroy(rc: *mut zkp_kzg_recoverer);
+    pub fn zkp_kzg_recover_cosets(rc: *const zkp_kzg_recoverer, evals: *const u64, present: *const u8, len: usize, out_coeffs: *mut u64, out_evals: *mut u64, consistent: *mut i32) -> i32;
+    pub fn zkp_kzg_recover_cosets_dev(rc: *const zkp_kzg_recoverer, d_evals: *const c_void, present: *const u8, len: usize, d_out_coeffs: *mut c_void, d_out_evals: *mut c_void, d_inconsistent: *mut u32, stream: *mut c_void) -> i32;
     pub fn zkp_g1_mul(base_xy: *const u64, base_is_inf: u8, scalar: *const u64, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_g1_fixed_base_mul_dev(d_scalars: *const c_void, n: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_fq_inverse_dev(d_in: *const c_void, n: usize, form: i32, d_out: *mut c_void, stream: *mut c_void) -> i32;

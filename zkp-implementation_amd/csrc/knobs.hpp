@@ -16,7 +16,7 @@ enum Knob {
     KNOB_MSM_PLAN_END,
     KNOB_TEST_TAIL_STARVE = KNOB_MSM_PLAN_END, KNOB_MSM_NO_POLL, KNOB_POOL_NO_WARM, KNOB_MSM_BALANCE_FROM, KNOB_SRS_EXPAND_MAX_BYTES, KNOB_NTT_TW_MATRIX_MAX_LOG,
     KNOB_NTT_NO_WIDE_PASS, KNOB_NTT_SHARD_MIN_LOG, KNOB_PLONK_NO_POLL, KNOB_FRI_ZERO_AS_0, KNOB_FRI_FR_TAIL_LOG,
-    KNOB_KZG_COSET_GROUP_LOG, KNOB_KZG_OPENER_MAX_BYTES,
+    KNOB_KZG_COSET_GROUP_LOG, KNOB_KZG_OPENER_MAX_BYTES, KNOB_KZG_RECOVER_LEAF_LOG, KNOB_KZG_RECOVER_MAX_BYTES,
     KNOB_COUNT
 };
 
@@ -96,6 +96,12 @@ constexpr KnobRow kKnobs[KNOB_COUNT] = {
     {KNOB_KZG_OPENER_MAX_BYTES, "ZKP_KZG_OPENER_MAX_BYTES", KNOB_POLICY, KNOB_INT, 0, LLONG_MAX, LLONG_MAX,
      "an opener (zkp_kzg_opener_create*, any log_l) whose slices and workspaces are larger than this is refused with ZKP_E_NOMEM "
      "before anything is allocated"},
+    {KNOB_KZG_RECOVER_LEAF_LOG, "ZKP_KZG_RECOVER_LEAF_LOG", KNOB_TUNING, KNOB_INT, 1, 8, KNOB_COMPUTED,
+     "recoverers created from now on multiply 2^v factors of the vanishing polynomial per leaf workgroup before the transform levels "
+     "take over (default: KZG_RECOVER_LEAF_LOG): profiles/kzg_recover.md"},
+    {KNOB_KZG_RECOVER_MAX_BYTES, "ZKP_KZG_RECOVER_MAX_BYTES", KNOB_POLICY, KNOB_INT, 0, LLONG_MAX, LLONG_MAX,
+     "a recoverer (zkp_kzg_recoverer_create) whose device workspace is larger than this is refused with ZKP_E_NOMEM before anything "
+     "is allocated"},
 };
 
 constexpr bool knob_rows_in_enum_order() {

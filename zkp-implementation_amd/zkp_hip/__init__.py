@@ -68,6 +68,10 @@ _SIGS = {
     "zkp_kzg_open_cosets": ([_VP, _VP, _SZ, _VP, _U8P, _VP], C.c_int),
     "zkp_kzg_open_cosets_dev": ([_VP, _VP, _SZ, _VP, _U8P, _VP, _VP], C.c_int),
     "zkp_kzg_verify_coset": ([_VP, _VP, _VP, C.c_uint8, _VP, C.c_uint8, _VP, C.c_uint, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_kzg_recoverer_create": ([C.c_uint, C.c_uint, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_recoverer_destroy": ([_VP], None),
+    "zkp_kzg_recover_cosets": ([_VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_kzg_recover_cosets_dev": ([_VP, _VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1_batch_dev": ([_VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
@@ -960,6 +964,48 @@ class KzgOpener:
             pass
 
 
+class KzgRecoverer:
+    """zkp_kzg_recoverer: the polynomial behind the cells of KzgOpener.open_cosets from any cosets that determine it.  Made on the
+    calling thread's slot; needs no SRS."""
+
+    def __init__(self, log_n, log_l):
+        self.log_n, self.n, self.log_l = log_n, 1 << log_n, log_l
+        self.cosets = self.n >> log_l
+        self._h = C.c_void_p()
+        _chk(lib().zkp_kzg_recoverer_create(log_n, log_l, C.byref(self._h)))
+
+    def recover(self, evals, present, length, want_evals=False):
+        """evals: (n, 4) values in natural order (coset k at k::r; what stands at a missing coset is not read); present: (r,) bytes,
+        0 = missing -> ((length, 4) coefficients, (n, 4) evaluations on the whole domain or None, consistent)"""
+        evals = _np(evals, np.uint64, (self.n, 4))
+        present = _np(present, np.uint8, (self.cosets,))
+        coeffs = np.zeros((int(length), 4), dtype=np.uint64)
+        ev = np.zeros((self.n, 4), dtype=np.uint64) if want_evals else None
+        ok = C.c_int(0)
+        _chk(lib().zkp_kzg_recover_cosets(self._h, _ptr(evals), _ptr(present), int(length), _ptr(coeffs), _ptr(ev), C.byref(ok)))
+        return coeffs, ev, bool(ok.value)
+
+    def recover_dev(self, evals_tensor, present, length, out_coeffs_tensor, inconsistent_tensor, out_evals_tensor=None, stream=None):
+        """The same with everything but `present` (host bytes) resident on the recoverer's device; inconsistent_tensor: at least 4
+        bytes, its first 32-bit word becomes 0 or 1.  Nothing is synchronised."""
+        present = _np(present, np.uint8, (self.cosets,))
+        ev = _dev_ptr(out_evals_tensor, 32 * self.n) if out_evals_tensor is not None else None
+        _chk(lib().zkp_kzg_recover_cosets_dev(self._h, _dev_ptr(evals_tensor, 32 * self.n), _ptr(present), int(length),
+                                              _dev_ptr(out_coeffs_tensor, 32 * int(length)), ev, _dev_ptr(inconsistent_tensor, 4),
+                                              _stream_ptr(stream)))
+
+    def close(self):
+        if self._h:
+            lib().zkp_kzg_recoverer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Srs:
     """kzg/src/srs.rs: g1_points = [s^i]G for i < circuit_size + 3, generated on the GPU and kept resident."""
 
@@ -982,6 +1028,7 @@ class KzgScheme:
         self.srs = srs
         self._openers = {}  # log_n -> KzgOpener (open_all), released by close()
         self._coset_openers = {}  # (log_n, log_l) -> KzgOpener (open_cosets), released by close()
+        self._recoverers = {}  # (log_n, log_l) -> KzgRecoverer (recover_cosets), released by close()
         if expand_bases:  # the SRS is fixed for the life of the scheme: pay the one-off expansion here
             srs.bases.precompute(0)
 
@@ -1011,13 +1058,25 @@ class KzgScheme:
             self._coset_openers[log_n, log_l] = KzgOpener(self.srs.bases, log_n, log_l)
         return self._coset_openers[log_n, log_l].open_cosets(coeffs, evals=evals)
 
+    def recover_cosets(self, evals, present, length, log_n, log_l, proofs=False):
+        """The polynomial of `length` coefficients behind the present cosets of `evals`: KzgRecoverer.recover with the evaluations (the
+        recoverer is kept per shape) -> (coefficients, evaluations on the whole domain, consistent), and with proofs=True a fourth
+        item, the (points, flags) of open_cosets on the recovered coefficients."""
+        if (log_n, log_l) not in self._recoverers:
+            self._recoverers[log_n, log_l] = KzgRecoverer(log_n, log_l)
+        coeffs, ev, ok = self._recoverers[log_n, log_l].recover(evals, present, length, want_evals=True)
+        if not proofs:
+            return coeffs, ev, ok
+        return coeffs, ev, ok, self.open_cosets(coeffs, log_n, log_l)[0]
+
     def close(self):
         """Release the device memory of the openers open_all and open_cosets made (about 1.4 KB per point of a domain for open_all, about
         1.1 KB for open_cosets: 512 B of kept slices, 512 B of partial sums and 64 B of scalars, plus up to 64 MiB); the SRS stays."""
-        for op in list(self._openers.values()) + list(self._coset_openers.values()):
+        for op in list(self._openers.values()) + list(self._coset_openers.values()) + list(self._recoverers.values()):
             op.close()
         self._openers = {}
         self._coset_openers = {}
+        self._recoverers = {}
 
     def __del__(self):
         try:
