@@ -43,7 +43,8 @@
  * memory than this many bytes; default: no limit), ZKP_KZG_RECOVER_LEAF_LOG (1..8: log2 of the factors of the vanishing polynomial
  * a leaf workgroup of a recoverer multiplies, read by zkp_kzg_recoverer_create; tuning aid), ZKP_KZG_RECOVER_MAX_BYTES
  * (zkp_kzg_recoverer_create refuses, with ZKP_E_NOMEM and the sizes in zkp_last_error(), a recoverer whose device workspace is larger
- * than this many bytes; default: no limit).
+ * than this many bytes; default: no limit), ZKP_KZG_CELLS_CHUNK_LOG (0..16: log2 of the cells of a coset, or weights of a commitment,
+ * one lane of a cell verifier sums before the chunk sums are combined, read by zkp_kzg_cell_verifier_create, default 4; tuning aid).
  */
 #ifndef ZKP_HIP_H
 #define ZKP_HIP_H
@@ -366,6 +367,54 @@ int zkp_kzg_recover_cosets(const zkp_kzg_recoverer *rc, const uint64_t *evals, c
                            uint64_t *out_coeffs, uint64_t *out_evals, int *consistent);
 int zkp_kzg_recover_cosets_dev(const zkp_kzg_recoverer *rc, const void *d_evals, const uint8_t *present, size_t len,
                                void *d_out_coeffs, void *d_out_evals, uint32_t *d_inconsistent, void *stream);
+
+/* ---- batched cell verification: any number of cells of any number of commitments, one pairing check ----
+ * n = 2^log_n, l = 2^log_l, r = n / l as above; w the root zkp_ntt_fr uses for log_n.  Cell i < n_cells belongs to the commitment
+ * C_m, m = commit_index[i] < n_commits, and to the coset k = coset_index[i] < r: its l evaluations e_i[j] = f(w^k w_l^j), in the order
+ * zkp_kzg_verify_coset takes them, are evals[i l .. i l + l) (n_cells x l x 4 limbs, cell-major, Fr memory form), its proof W_i is
+ * proofs_xy[i], its weight rho_i is weights[i] (n_cells x 4 limbs).  With c_i = w^(k l) and I_i the interpolant of e_i on its coset,
+ * the batch is accepted iff
+ *   e( sum rho_i W_i , [s^l]_2 ) == e( sum_m (sum_{i: m_i = m} rho_i) C_m - [(sum rho_i I_i)(s)]_1 + sum rho_i c_i W_i , G_2 ),
+ * the equation of zkp_kzg_verify_coset summed with the weights: two Miller loops and one final exponentiation whatever n_cells.
+ * THE WEIGHTS ARE THE CALLER'S RANDOMNESS (as r_primes of zkp_kzg_batch_verify and r of zkp_srs_check): independent, unpredictable
+ * to whoever made the cells, 128 bits are enough.  A weight of 0 drops its cell from the check; equal (or otherwise related) weights
+ * let the errors of different cells cancel, so a batch with a wrong cell can be accepted.  A cell may appear more than once.
+ * Everything before the pairings runs on the device: the interpolant sum is one weighted scatter of the evaluations into a vector of
+ * n, one inverse transform of n and l products (sum_k (F mod (X^l - w^(k l))) = r (F mod X^l) for deg F < n); the G1 sums are one batch
+ * of two MSMs over the n_commits + n_cells points and one MSM of l terms over the SRS.  ALL commitments and proofs are validated on
+ * the device first (canonical, on the curve, in G1; the kernels of zkp_g1_validate): the batched equation is unsound on points
+ * outside G1, so this is not optional.  A bad point is ZKP_E_ARG and zkp_last_error() names the array ("commits" or "proofs"), the
+ * lowest bad index and the status word "canonical", "curve" or "subgroup".  is_inf arrays may be NULL (no identity among them).
+ * zkp_kzg_cell_verifier_create: g2_sl_xy = [s^l]_2 is validated (ZKP_E_ARG); log_l < log_n <= 23, max_cells and max_commits in
+ * 1 .. 2^30, else ZKP_E_ARG; a sharded SRS handle is ZKP_E_ARG, one with fewer than l points ZKP_E_SIZE.  THE SRS IS BORROWED: the
+ * handle must outlive the verifier (it may be expanded or not).  The verifier lives on the SRS's slot and owns every workspace sized
+ * by n, max_cells and max_commits (about 32 l bytes per cell); the plan and table of its transform are built here.  A workspace that
+ * does not fit is ZKP_E_NOMEM with the sizes in zkp_last_error() and nothing left allocated.  No device: ZKP_E_DEVICE; there is no
+ * host path.
+ * zkp_kzg_verify_cells / _dev: a null argument is ZKP_E_ARG, n_cells > max_cells or n_commits > max_commits ZKP_E_SIZE, a coset index
+ * >= r or a commitment index >= n_commits ZKP_E_ARG naming the cell -- all before anything is launched; n_cells == 0 accepts without
+ * touching the device.  Both end in host pairings, so both BLOCK; the _dev form differs only in where its inputs live: d_commits_xy,
+ * d_commits_is_inf, d_evals, d_proofs_xy, d_proofs_is_inf and d_weights are memory of the verifier's device, the two index arrays
+ * stay HOST memory (the grouping is planned on the host).  Either form may allocate: the transient point handle of the call, and the
+ * slot's MSM workspaces when they have to grow.  While profiling is on a call records the phases "kzg_cells_field",
+ * "kzg_cells_points" (validation and the MSMs) and "kzg_cells_pairing" (host).
+ * zkp_kzg_cells_aggregate_dev: the field half alone, exact to the bit: d_out_interp (l x 4 limbs) the coefficients of sum rho_i I_i,
+ * d_out_commit_weights (n_commits x 4) the sums of the weights per commitment, d_out_proof_scalars (n_cells x 4) rho_i c_i.  Same
+ * refusals.  It neither allocates nor waits for the device, except for the previous call's copy of the index tables out of the
+ * handle's staging buffer; calls on one handle are serialised with its slot. */
+typedef struct zkp_kzg_cell_verifier zkp_kzg_cell_verifier;
+int zkp_kzg_cell_verifier_create(const zkp_bases *srs, const uint64_t g2_sl_xy[24], unsigned log_n, unsigned log_l, size_t max_cells,
+                                 size_t max_commits, zkp_kzg_cell_verifier **out);
+void zkp_kzg_cell_verifier_destroy(zkp_kzg_cell_verifier *v);
+int zkp_kzg_verify_cells(const zkp_kzg_cell_verifier *v, const uint64_t *commits_xy, const uint8_t *commits_is_inf, size_t n_commits,
+                         size_t n_cells, const uint32_t *commit_index, const uint32_t *coset_index, const uint64_t *evals,
+                         const uint64_t *proofs_xy, const uint8_t *proofs_is_inf, const uint64_t *weights, int *accepted);
+int zkp_kzg_verify_cells_dev(const zkp_kzg_cell_verifier *v, const void *d_commits_xy, const uint8_t *d_commits_is_inf, size_t n_commits,
+                             size_t n_cells, const uint32_t *commit_index, const uint32_t *coset_index, const void *d_evals,
+                             const void *d_proofs_xy, const uint8_t *d_proofs_is_inf, const void *d_weights, void *stream, int *accepted);
+int zkp_kzg_cells_aggregate_dev(const zkp_kzg_cell_verifier *v, size_t n_commits, size_t n_cells, const uint32_t *commit_index,
+                                const uint32_t *coset_index, const void *d_evals, const void *d_weights, void *d_out_interp,
+                                void *d_out_commit_weights, void *d_out_proof_scalars, void *stream);
 
 /* ---- single scalar multiplication: KzgScheme::commit_para, kzg/src/scheme.rs:78-82 (`g1_0.mul(para)`),
  *      6x per proof at plonk/src/prover.rs:183-188.  Serial by nature: computed on the host. ---- */

@@ -1,13 +1,16 @@
 // SOURCE-ONLY (not compiled here, see ../README.md): the replacement for kzg/src/scheme.rs:22-47 and 84-96.
 // Everything else in scheme.rs (commit, commit_vector, open, open_vector, commit_para, verify, batch_verify) is unchanged: they
-// all funnel into evaluate_in_s.
+// all funnel into evaluate_in_s.  verify_cells at the end is an addition: the batched counterpart of batch_verify for the cells of
+// zkp_kzg_open_cosets (data-availability sampling), one pairing check for any number of cells.
 use ark_ec::AffineRepr;
 use ark_ff::{BigInt, Fp};
 use ark_poly::Polynomial;
 use zkp_hip_sys as sys;
 
 use crate::srs::Srs;
-use crate::types::{G1Point, Poly};
+use crate::types::{G1Point, G2Point, Poly};
+use ark_bls12_381::Fr;
+use rand::Rng;
 
 /// The SRS `Vec<G1Affine>` resident in HBM, uploaded ONCE (the reference clones the vector on every commit, srs.rs:78-80).
 /// With `zkp_init_devices` and more than one device the upload shards the points over the GPUs by contiguous chunk and every
@@ -85,5 +88,66 @@ impl KzgScheme {
         let limb = |o: usize| BigInt::<6>([xy[o], xy[o + 1], xy[o + 2], xy[o + 3], xy[o + 4], xy[o + 5]]);
         // the limbs ARE the Montgomery residues: construct the field elements without another conversion
         G1Point::new_unchecked(Fp::new_unchecked(limb(0)), Fp::new_unchecked(limb(6)))
+    }
+}
+
+/// One cell of zkp_kzg_open_cosets: the l values of `commitments[commit]` on coset `coset` of the domain of 2^log_n, and its proof.
+pub struct Cell {
+    pub commit: u32,
+    pub coset: u32,
+    pub evals: Vec<Fr>,
+    pub proof: G1Point,
+}
+
+fn g1_limbs(points: impl Iterator<Item = G1Point>) -> (Vec<u64>, Vec<u8>) {
+    let (mut xy, mut inf) = (Vec::new(), Vec::new());
+    for p in points {
+        xy.extend_from_slice(&p.x.0 .0);
+        xy.extend_from_slice(&p.y.0 .0);
+        inf.push(p.infinity as u8);
+    }
+    (xy, inf)
+}
+
+impl KzgScheme {
+    /// All `cells` in ONE pairing check (include/zkp_hip.h, "batched cell verification"): `g2_sl` = [s^l]_2, l = 2^log_l.  The
+    /// weights are drawn here as batch_verify draws its r_primes (scheme.rs:215-245: `Fr::from(rng.gen::<u128>())`); every
+    /// commitment and proof is validated on the device before it is used.  A long-lived caller keeps the verifier instead of
+    /// making one per call.
+    pub fn verify_cells(&self, g2_sl: &G2Point, commitments: &[G1Point], cells: &[Cell], log_n: u32, log_l: u32) -> bool {
+        let l = 1usize << log_l;
+        let mut g2 = [0u64; 24];
+        for (i, c) in [g2_sl.x.c0, g2_sl.x.c1, g2_sl.y.c0, g2_sl.y.c1].iter().enumerate() {
+            g2[6 * i..6 * i + 6].copy_from_slice(&c.0 .0);
+        }
+        let mut v = core::ptr::null_mut();
+        let rc = unsafe {
+            sys::zkp_kzg_cell_verifier_create(self.1.ptr, g2.as_ptr(), log_n, log_l, cells.len().max(1), commitments.len().max(1), &mut v)
+        };
+        assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
+        let (commits_xy, commits_inf) = g1_limbs(commitments.iter().copied());
+        let (proofs_xy, proofs_inf) = g1_limbs(cells.iter().map(|c| c.proof));
+        let commit_index: Vec<u32> = cells.iter().map(|c| c.commit).collect();
+        let coset_index: Vec<u32> = cells.iter().map(|c| c.coset).collect();
+        let mut evals: Vec<Fr> = Vec::with_capacity(cells.len() * l);
+        for c in cells {
+            assert_eq!(c.evals.len(), l);
+            evals.extend_from_slice(&c.evals);
+        }
+        let mut rng = rand::thread_rng();
+        let weights: Vec<Fr> = cells.iter().map(|_| Fr::from(rng.gen::<u128>())).collect();
+        let mut accepted = 0i32;
+        let rc = unsafe {
+            sys::zkp_kzg_verify_cells(v, commits_xy.as_ptr(), commits_inf.as_ptr(), commitments.len(), cells.len(), commit_index.as_ptr(),
+                                      coset_index.as_ptr(), evals.as_ptr() as *const u64, proofs_xy.as_ptr(), proofs_inf.as_ptr(),
+                                      weights.as_ptr() as *const u64, &mut accepted)
+        };
+        unsafe { sys::zkp_kzg_cell_verifier_destroy(v) };
+        // a point outside G1 is ZKP_E_ARG: for a verifier that is a rejection, any other failure is the caller's to see
+        if rc == sys::ZKP_E_ARG {
+            return false;
+        }
+        assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
+        accepted != 0
     }
 }

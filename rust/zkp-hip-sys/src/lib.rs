@@ -20,6 +20,7 @@ pub const ZKP_E_SIZE: i32 = -4;
 #[repr(C)] pub struct zkp_nova_transcript { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_kzg_opener { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_kzg_recoverer { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_kzg_cell_verifier { _private: [u8; 0] }
 
 /// how a bases handle is expanded (zkp_g1_bases_expansion); all zero when it is not
 #[repr(C)]
@@ -174,6 +175,11 @@ extern "C" {
     pub fn zkp_kzg_recoverer_destroy(rc: *mut zkp_kzg_recoverer);
     pub fn zkp_kzg_recover_cosets(rc: *const zkp_kzg_recoverer, evals: *const u64, present: *const u8, len: usize, out_coeffs: *mut u64, out_evals: *mut u64, consistent: *mut i32) -> i32;
     pub fn zkp_kzg_recover_cosets_dev(rc: *const zkp_kzg_recoverer, d_evals: *const c_void, present: *const u8, len: usize, d_out_coeffs: *mut c_void, d_out_evals: *mut c_void, d_inconsistent: *mut u32, stream: *mut c_void) -> i32;
+    pub fn zkp_kzg_cell_verifier_create(srs: *const zkp_bases, g2_sl_xy: *const u64, log_n: u32, log_l: u32, max_cells: usize, max_commits: usize, out: *mut *mut zkp_kzg_cell_verifier) -> i32;
+    pub fn zkp_kzg_cell_verifier_destroy(v: *mut zkp_kzg_cell_verifier);
+    pub fn zkp_kzg_verify_cells(v: *const zkp_kzg_cell_verifier, commits_xy: *const u64, commits_is_inf: *const u8, n_commits: usize, n_cells: usize, commit_index: *const u32, coset_index: *const u32, evals: *const u64, proofs_xy: *const u64, proofs_is_inf: *const u8, weights: *const u64, accepted: *mut i32) -> i32;
+    pub fn zkp_kzg_verify_cells_dev(v: *const zkp_kzg_cell_verifier, d_commits_xy: *const c_void, d_commits_is_inf: *const u8, n_commits: usize, n_cells: usize, commit_index: *const u32, coset_index: *const u32, d_evals: *const c_void, d_proofs_xy: *const c_void, d_proofs_is_inf: *const u8, d_weights: *const c_void, stream: *mut c_void, accepted: *mut i32) -> i32;
+    pub fn zkp_kzg_cells_aggregate_dev(v: *const zkp_kzg_cell_verifier, n_commits: usize, n_cells: usize, commit_index: *const u32, coset_index: *const u32, d_evals: *const c_void, d_weights: *const c_void, d_out_interp: *mut c_void, d_out_commit_weights: *mut c_void, d_out_proof_scalars: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_g1_mul(base_xy: *const u64, base_is_inf: u8, scalar: *const u64, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_g1_fixed_base_mul_dev(d_scalars: *const c_void, n: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_fq_inverse_dev(d_in: *const c_void, n: usize, form: i32, d_out: *mut c_void, stream: *mut c_void) -> i32;

@@ -30,6 +30,7 @@
 #include "ntt.hpp"
 #include "g1_ntt.hpp"
 #include "kzg_recover.hpp"
+#include "kzg_cells.hpp"
 #include "plonk.hpp"
 #include "nova.hpp"
 #include "fri.hpp"
@@ -1409,4 +1410,5 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "g1_check_host.inc"
 #include "g1_ntt_host.inc"
 #include "kzg_recover_host.inc"
+#include "kzg_cells_host.inc"
 #include "nova_host.inc"

@@ -17,6 +17,7 @@ enum Knob {
     KNOB_TEST_TAIL_STARVE = KNOB_MSM_PLAN_END, KNOB_MSM_NO_POLL, KNOB_POOL_NO_WARM, KNOB_MSM_BALANCE_FROM, KNOB_SRS_EXPAND_MAX_BYTES, KNOB_NTT_TW_MATRIX_MAX_LOG,
     KNOB_NTT_NO_WIDE_PASS, KNOB_NTT_SHARD_MIN_LOG, KNOB_PLONK_NO_POLL, KNOB_FRI_ZERO_AS_0, KNOB_FRI_FR_TAIL_LOG,
     KNOB_KZG_COSET_GROUP_LOG, KNOB_KZG_OPENER_MAX_BYTES, KNOB_KZG_RECOVER_LEAF_LOG, KNOB_KZG_RECOVER_MAX_BYTES,
+    KNOB_KZG_CELLS_CHUNK_LOG,
     KNOB_COUNT
 };
 
@@ -102,6 +103,9 @@ constexpr KnobRow kKnobs[KNOB_COUNT] = {
     {KNOB_KZG_RECOVER_MAX_BYTES, "ZKP_KZG_RECOVER_MAX_BYTES", KNOB_POLICY, KNOB_INT, 0, LLONG_MAX, LLONG_MAX,
      "a recoverer (zkp_kzg_recoverer_create) whose device workspace is larger than this is refused with ZKP_E_NOMEM before anything "
      "is allocated"},
+    {KNOB_KZG_CELLS_CHUNK_LOG, "ZKP_KZG_CELLS_CHUNK_LOG", KNOB_TUNING, KNOB_INT, 0, 16, KNOB_COMPUTED,
+     "cell verifiers created from now on sum at most 2^v cells of a coset (weights of a commitment) per lane before the sums of the "
+     "chunks are combined (default: KZG_CELLS_CHUNK_LOG): profiles/kzg_verify_cells.md"},
 };
 
 constexpr bool knob_rows_in_enum_order() {

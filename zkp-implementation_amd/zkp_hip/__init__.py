@@ -72,6 +72,11 @@ _SIGS = {
     "zkp_kzg_recoverer_destroy": ([_VP], None),
     "zkp_kzg_recover_cosets": ([_VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(C.c_int)], C.c_int),
     "zkp_kzg_recover_cosets_dev": ([_VP, _VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_cell_verifier_create": ([_VP, _VP, C.c_uint, C.c_uint, _SZ, _SZ, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_cell_verifier_destroy": ([_VP], None),
+    "zkp_kzg_verify_cells": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_kzg_verify_cells_dev": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _VP, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_kzg_cells_aggregate_dev": ([_VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1_batch_dev": ([_VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
@@ -1006,6 +1011,81 @@ class KzgRecoverer:
             pass
 
 
+def _points(p):
+    """(xy, is_inf) or xy alone -> ((count, 12) limbs, (count,) flags or None)"""
+    xy, inf = p if isinstance(p, tuple) else (p, None)
+    xy = _np(xy, np.uint64, (-1, 12))
+    return xy, (_np(inf, np.uint8, (xy.shape[0],)) if inf is not None else None)
+
+
+class KzgCellVerifier:
+    """zkp_kzg_cell_verifier: any number of cells of KzgOpener.open_cosets, of any number of commitments, behind one pairing check.
+    srs_bases is borrowed (kept alive here); g2_sl_xy = [s^l]_2.  The weights are the caller's randomness: see include/zkp_hip.h."""
+
+    def __init__(self, srs_bases, g2_sl_xy, log_n, log_l, max_cells, max_commits):
+        self.log_n, self.n, self.log_l, self.l = log_n, 1 << log_n, log_l, 1 << log_l
+        self.max_cells, self.max_commits = int(max_cells), int(max_commits)
+        self._srs = srs_bases
+        self._h = C.c_void_p()
+        g2 = _np(g2_sl_xy, np.uint64).reshape(24)
+        _chk(lib().zkp_kzg_cell_verifier_create(srs_bases._h, _ptr(g2), log_n, log_l, self.max_cells, self.max_commits, C.byref(self._h)))
+
+    @staticmethod
+    def _indices(commit_index, coset_index):
+        ci, ki = _np(commit_index, np.uint32), _np(coset_index, np.uint32)
+        if ci.shape != ki.shape or ci.ndim != 1:
+            raise ZkpError(ZKP_E_ARG, "commit_index and coset_index are two vectors of one length")
+        return ci, ki
+
+    def verify(self, commitments, commit_index, coset_index, evals, proofs, weights):
+        """commitments / proofs: (xy, is_inf) or xy alone; evals (n_cells, l, 4); weights (n_cells, 4) -> accepted"""
+        ci, ki = self._indices(commit_index, coset_index)
+        cells = ci.shape[0]
+        (cxy, cinf), (pxy, pinf) = _points(commitments), _points(proofs)
+        ev, wt = _np(evals, np.uint64, (cells, self.l, 4)), _np(weights, np.uint64, (cells, 4))
+        if pxy.shape[0] != cells:
+            raise ZkpError(ZKP_E_ARG, "one proof per cell")
+        acc = C.c_int(0)
+        _chk(lib().zkp_kzg_verify_cells(self._h, _ptr(cxy), _ptr(cinf), cxy.shape[0], cells, _ptr(ci), _ptr(ki), _ptr(ev), _ptr(pxy), _ptr(pinf),
+                                        _ptr(wt), C.byref(acc)))
+        return bool(acc.value)
+
+    def verify_dev(self, commits_tensor, n_commits, commit_index, coset_index, evals_tensor, proofs_tensor, weights_tensor,
+                   commits_inf_tensor=None, proofs_inf_tensor=None, stream=None):
+        """The same with everything but the two index vectors (host) resident on the verifier's device; blocks like verify."""
+        ci, ki = self._indices(commit_index, coset_index)
+        cells = ci.shape[0]
+        cinf = _dev_ptr(commits_inf_tensor, n_commits) if commits_inf_tensor is not None else None
+        pinf = _dev_ptr(proofs_inf_tensor, cells) if proofs_inf_tensor is not None else None
+        acc = C.c_int(0)
+        _chk(lib().zkp_kzg_verify_cells_dev(self._h, _dev_ptr(commits_tensor, 96 * n_commits), cinf, n_commits, cells, _ptr(ci), _ptr(ki),
+                                            _dev_ptr(evals_tensor, 32 * cells * self.l), _dev_ptr(proofs_tensor, 96 * cells), pinf,
+                                            _dev_ptr(weights_tensor, 32 * cells), _stream_ptr(stream), C.byref(acc)))
+        return bool(acc.value)
+
+    def aggregate_dev(self, n_commits, commit_index, coset_index, evals_tensor, weights_tensor, out_interp_tensor, out_commit_weights_tensor,
+                      out_proof_scalars_tensor, stream=None):
+        """zkp_kzg_cells_aggregate_dev: the field half alone -> the l coefficients of sum rho_i I_i, the n_commits sums of the weights,
+        the n_cells scalars rho_i c_i, in the three tensors.  Nothing is synchronised."""
+        ci, ki = self._indices(commit_index, coset_index)
+        cells = ci.shape[0]
+        _chk(lib().zkp_kzg_cells_aggregate_dev(self._h, n_commits, cells, _ptr(ci), _ptr(ki), _dev_ptr(evals_tensor, 32 * cells * self.l),
+                                               _dev_ptr(weights_tensor, 32 * cells), _dev_ptr(out_interp_tensor, 32 * self.l),
+                                               _dev_ptr(out_commit_weights_tensor, 32 * n_commits),
+                                               _dev_ptr(out_proof_scalars_tensor, 32 * cells), _stream_ptr(stream)))
+
+    def close(self):
+        if self._h:
+            lib().zkp_kzg_cell_verifier_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Srs:
     """kzg/src/srs.rs: g1_points = [s^i]G for i < circuit_size + 3, generated on the GPU and kept resident."""
 
@@ -1029,6 +1109,7 @@ class KzgScheme:
         self._openers = {}  # log_n -> KzgOpener (open_all), released by close()
         self._coset_openers = {}  # (log_n, log_l) -> KzgOpener (open_cosets), released by close()
         self._recoverers = {}  # (log_n, log_l) -> KzgRecoverer (recover_cosets), released by close()
+        self._cell_verifiers = {}  # (log_n, log_l) -> (g2_sl bytes, KzgCellVerifier) (verify_cells), released by close()
         if expand_bases:  # the SRS is fixed for the life of the scheme: pay the one-off expansion here
             srs.bases.precompute(0)
 
@@ -1069,11 +1150,31 @@ class KzgScheme:
             return coeffs, ev, ok
         return coeffs, ev, ok, self.open_cosets(coeffs, log_n, log_l)[0]
 
+    def verify_cells(self, g2_sl_xy, commitments, commit_index, coset_index, evals, proofs, log_n, log_l, weights=None):
+        """Cells of open_cosets, of any of `commitments`, in one pairing check: KzgCellVerifier.verify (the verifier is kept per
+        shape and grows with the batch).  weights=None draws a 128-bit weight per cell from `secrets`, the counterpart of
+        Fr::from(rng.gen::<u128>()) in kzg/src/scheme.rs:215-245; pass weights only to reproduce a run."""
+        ci = _np(commit_index, np.uint32)
+        cells, commits = ci.shape[0], _points(commitments)[0].shape[0]
+        g2 = _np(g2_sl_xy, np.uint64).reshape(24)
+        kept = self._cell_verifiers.get((log_n, log_l))
+        if kept is None or kept[0] != g2.tobytes() or kept[1].max_cells < cells or kept[1].max_commits < commits:
+            if kept is not None:
+                kept[1].close()
+            ver = KzgCellVerifier(self.srs.bases, g2, log_n, log_l, max(cells, 1), max(commits, 1))
+            kept = self._cell_verifiers[log_n, log_l] = (g2.tobytes(), ver)
+        if weights is None:
+            import secrets
+            weights = _fr_mont_rows([secrets.randbits(128) for _ in range(cells)])
+        return kept[1].verify(commitments, ci, coset_index, evals, proofs, weights)
+
     def close(self):
         """Release the device memory of the openers open_all and open_cosets made (about 1.4 KB per point of a domain for open_all, about
         1.1 KB for open_cosets: 512 B of kept slices, 512 B of partial sums and 64 B of scalars, plus up to 64 MiB); the SRS stays."""
-        for op in list(self._openers.values()) + list(self._coset_openers.values()) + list(self._recoverers.values()):
+        for op in (list(self._openers.values()) + list(self._coset_openers.values()) + list(self._recoverers.values()) +
+                   [ver for _, ver in self._cell_verifiers.values()]):
             op.close()
+        self._cell_verifiers = {}
         self._openers = {}
         self._coset_openers = {}
         self._recoverers = {}
