@@ -317,6 +317,9 @@ struct CtxScope {
     CtxScope ctx_scope_(slot);    \
     if (ctx_scope_.rc != ZKP_OK) return ctx_scope_.rc
 
+// The stream of a host-pointer entry, after CTX_ENTER: the null stream, or the slot's own once there are several slots
+hipStream_t host_stream() { return g_rt.multi ? ctx().stream : nullptr; }
+
 // See Ctx::ws_event.  Constructed by an entry after CTX_ENTER with the stream it is about to launch on.
 struct WsOrder {
     hipStream_t st;
@@ -663,7 +666,7 @@ void shard_range(size_t n, size_t i, size_t k, size_t* lo, size_t* hi) {
 // n points from host memory onto ONE slot
 int bases_create_single(int slot, const uint64_t* xy, const uint8_t* is_inf, size_t n, zkp_bases** out) {
     CTX_ENTER(slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     zkp_bases* b = nullptr;
     ZCHK(bases_alloc(n, is_inf != nullptr, &b));
@@ -731,7 +734,7 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool glv, bool check_o
     if (window_bits < 9 || window_bits > MSM_MAX_WINDOW_BITS) return fail(ZKP_E_ARG, "window_bits must be 0 (automatic) or in 9.." + std::to_string(MSM_MAX_WINDOW_BITS));
     if (b->pre_c) return b->pre_req == window_bits ? ZKP_OK : fail(ZKP_E_ARG, "bases already expanded with another width");
     CTX_ENTER(b->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     if (!b->n) return ZKP_OK;
     // Slices of a scalar (or of a scalar half): msm_slice_offsets, msm_plan.hpp
@@ -784,7 +787,7 @@ int precompute_single(zkp_bases* b, unsigned window_bits, bool glv, bool check_o
 int unexpand_single(zkp_bases* b) {
     if (!b->pre_c) return ZKP_OK;
     CTX_ENTER(b->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     DevBuf p;
     ZCHK(p.ensure(128 * std::max<size_t>(b->n, 1)));
@@ -953,7 +956,7 @@ const char* const kShardedDev = "bases are sharded over several devices: device-
 // sum_{i<n} scalars[i] * bases[i] for host scalars over ONE slot's bases, unnormalised
 int msm_host_scalars(const zkp_bases* bases, const uint64_t* scalars, size_t n, HXyzz* r) {
     CTX_ENTER(bases->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     if (n > bases->n) return fail(ZKP_E_SIZE, "more scalars than bases (kzg/src/scheme.rs:86)");
     *r = HXyzz::infinity();
@@ -1062,7 +1065,7 @@ int zkp_msm_g1_sharded_dev_after(const zkp_bases* bases, const void* const* d_sc
         if (n) {
             if (!d_scalars[0]) return fail(ZKP_E_ARG, "null scalar pointer");
             CTX_ENTER(bases->slot);
-            hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+            hipStream_t st = host_stream();
             // neither the slot's non-blocking stream nor the legacy null stream is ordered after a producer on a non-blocking
             // stream (torch's side streams are): wait for its event, or for the device (include/zkp_hip.h states this contract)
             ZCHK(order_after_producer(st, ready_events ? ready_events[0] : nullptr));
@@ -1408,6 +1411,7 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "fri_host.inc"
 #include "verify_host.inc"
 #include "g1_check_host.inc"
+#include "kzg_handle.inc"
 #include "g1_ntt_host.inc"
 #include "kzg_recover_host.inc"
 #include "kzg_cells_host.inc"

@@ -56,7 +56,7 @@ void g1_check_fill(const G1CheckReport& r, size_t n, zkp_g1_validation* out) {
 // the points of ONE slot's handle (plane 0 of an expansion is the points themselves); status: host memory or null
 int bases_validate_single(const zkp_bases* b, uint8_t* status, uint64_t first, G1CheckReport* out) {
     CTX_ENTER(b->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     *out = kEmptyReport;
     if (!b->n) return ZKP_OK;
@@ -95,7 +95,7 @@ int zkp_g1_validate(const uint64_t* xy, const uint8_t* is_inf, size_t n, uint8_t
     *out = zkp_g1_validation{};
     if (!n) return ZKP_OK;
     CTX_ENTER(-1);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     const size_t chunk = std::min(n, G1_CHECK_CHUNK);
     G1CheckReport* rep = nullptr;

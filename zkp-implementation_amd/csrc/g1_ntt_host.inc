@@ -50,22 +50,6 @@ G1NttVec g1_ntt_carve(void* base, unsigned log_n, const G1NttSizes& sz) {
 
 unsigned g1_ntt_blocks(uint64_t lanes, unsigned threads) { return (unsigned)((lanes + threads - 1) / threads); }
 
-// The slot's staging buffer grown to `need` bytes, or ZKP_E_NOMEM with the sizes (a failed growth leaves the buffer released)
-int g1_ntt_workspace(size_t need, const char* what, void** out) {
-    DevBuf& tmp = ctx().tmp;
-    if (need > tmp.cap) {
-        const DevFree mem;
-        const bool fits = !mem.total_b || need <= mem.free_b + tmp.cap;
-        if (!fits || tmp.grow(need) != hipSuccess) {
-            (void)hipGetLastError();
-            tmp.release();
-            return mem.refuse(std::string(what) + ": the workspace of " + std::to_string(need) + " bytes does not fit");
-        }
-    }
-    *out = tmp.p;
-    return ZKP_OK;
-}
-
 // launch(first, count) over the lanes [0, total) in pieces of at most G1_NTT_IO_LAUNCH, as the validation kernels: the load, store,
 // gather, split and fold kernels, which take `first` and bound their own lanes
 template <class Launch>
@@ -145,13 +129,11 @@ const char* const kShardedG1Ntt = "bases are sharded over several devices: a tra
 
 }  // namespace
 
-struct zkp_kzg_opener {
-    unsigned log_n = 0;
-    unsigned log_l = 0;      // one proof per coset of 2^log_l points; 0: all n openings
+// log_l: one proof per coset of 2^log_l points; 0: all n openings.  work: (the partial sums,) u, the slice h, the scalars g and the
+// lanes' table of one call
+struct zkp_kzg_opener : KzgHandle {
     unsigned group_log = 0;  // a lane of the multiply-accumulate pass sums 2^group_log terms (g1_coset_mac; one at most when l = 1)
-    int slot = 0, device = 0;
     DevBuf srs_hat;  // the l slices of the reversed SRS points, each transformed (NTT_2r): depends on the SRS, n and l only
-    DevBuf work;     // (the partial sums,) u, the slice h, the scalars g and the lanes' table of one call (entries of a slot are serialised)
 };
 
 extern "C" {
@@ -166,7 +148,7 @@ int zkp_g1_scale_dev(void* d_xy, uint8_t* d_is_inf, const void* d_scalars, size_
     WsOrder ord(st);
     const uint64_t step = std::min<uint64_t>(n, G1_NTT_LAUNCH);
     void* ws = nullptr;
-    ZCHK(g1_ntt_workspace(2 * G1_NTT_POINT_BYTES * step, "zkp_g1_scale_dev", &ws));
+    ZCHK(slot_workspace(2 * G1_NTT_POINT_BYTES * step, "zkp_g1_scale_dev", &ws));
     const G1NttVec v{static_cast<uint4*>(ws), step, static_cast<uint4*>(ws) + 16 * step, step};
     for (uint64_t off = 0; off < n; off += step) {
         const uint64_t cnt = std::min<uint64_t>(step, n - off);
@@ -188,7 +170,7 @@ int zkp_g1_ntt_dev(void* d_xy, uint8_t* d_is_inf, unsigned log_n, int inverse, v
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WsOrder ord(st);
     void* ws = nullptr;
-    ZCHK(g1_ntt_workspace(g1_ntt_sizes(log_n, ((uint64_t)1 << log_n) / 2).total, "zkp_g1_ntt_dev", &ws));
+    ZCHK(slot_workspace(g1_ntt_sizes(log_n, ((uint64_t)1 << log_n) / 2).total, "zkp_g1_ntt_dev", &ws));
     return g1_ntt_raw_locked(d_xy, d_is_inf, log_n, inverse, ws, st);
 } ZKP_CATCH_INT
 
@@ -196,12 +178,12 @@ int zkp_g1_ntt(uint64_t* xy, uint8_t* is_inf, unsigned log_n, int inverse) try {
     if (!xy || !is_inf) return fail(ZKP_E_ARG, "null argument");
     if (log_n > G1_NTT_MAX_LOG) return fail(ZKP_E_ARG, "log_n > 24");
     CTX_ENTER(-1);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     const size_t n = (size_t)1 << log_n;
     const size_t ws_bytes = g1_ntt_sizes(log_n, n / 2).total;
     void* ws = nullptr;
-    ZCHK(g1_ntt_workspace(ws_bytes + 96 * n + n, "zkp_g1_ntt", &ws));
+    ZCHK(slot_workspace(ws_bytes + 96 * n + n, "zkp_g1_ntt", &ws));
     char* d_xy = static_cast<char*>(ws) + ws_bytes;
     uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * n);
     HIPCHK(hipMemcpyAsync(d_xy, xy, 96 * n, hipMemcpyHostToDevice, st));
@@ -220,10 +202,10 @@ int zkp_g1_bases_lagrange(const zkp_bases* srs, unsigned log_n, zkp_bases** out)
     const size_t n = (size_t)1 << log_n;
     if (srs->n < n) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_n points");
     CTX_ENTER(srs->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     void* ws = nullptr;
-    ZCHK(g1_ntt_workspace(g1_ntt_sizes(log_n, n / 2).total, "zkp_g1_bases_lagrange", &ws));
+    ZCHK(slot_workspace(g1_ntt_sizes(log_n, n / 2).total, "zkp_g1_bases_lagrange", &ws));
     const G1NttVec v = g1_ntt_carve(ws, log_n, g1_ntt_sizes(log_n, n / 2));
     zkp_bases* raw = nullptr;
     ZCHK(bases_alloc(n, true, &raw));
@@ -236,13 +218,7 @@ int zkp_g1_bases_lagrange(const zkp_bases* srs, unsigned log_n, zkp_bases** out)
     return ZKP_OK;
 } ZKP_CATCH_INT
 
-void zkp_kzg_opener_destroy(zkp_kzg_opener* o) {
-    if (!o) return;
-    DeviceRestore restore;
-    (void)hipSetDevice(o->device);
-    (void)hipDeviceSynchronize();  // a call may still be running on the caller's stream
-    delete o;
-}
+void zkp_kzg_opener_destroy(zkp_kzg_opener* o) { handle_destroy(o); }
 
 }  // extern "C"
 
@@ -355,11 +331,11 @@ int kzg_open_host(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, u
                   const char* what, bool cosets) {
     ZCHK(kzg_open_all_args(o, coeffs, len, out_xy, out_is_inf, cosets));
     CTX_ENTER(o->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     const size_t n = (size_t)1 << o->log_n, r = n >> o->log_l;
     void* ws = nullptr;  // coefficients | evaluations | points | flags
-    ZCHK(g1_ntt_workspace(32 * len + 32 * n + 96 * r + r, what, &ws));
+    ZCHK(slot_workspace(32 * len + 32 * n + 96 * r + r, what, &ws));
     char* d_coeffs = static_cast<char*>(ws);
     char* d_evals = d_coeffs + 32 * len;
     char* d_xy = d_evals + 32 * n;
@@ -384,30 +360,18 @@ int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned 
     const uint64_t n = (uint64_t)1 << log_n, l = (uint64_t)1 << log_l;
     if (srs->n < n - l) return fail(ZKP_E_SIZE, "the SRS has fewer than 2^log_n - 2^log_l points");
     CTX_ENTER(srs->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
-    std::unique_ptr<zkp_kzg_opener, void (*)(zkp_kzg_opener*)> o(new (std::nothrow) zkp_kzg_opener(), zkp_kzg_opener_destroy);
+    auto o = handle_new<zkp_kzg_opener>(log_n, log_l);
     if (!o) return fail(ZKP_E_NOMEM, "host allocation failed");
-    o->log_n = log_n;
-    o->log_l = log_l;
     static_assert(kKnobs[KNOB_KZG_COSET_GROUP_LOG].hi == G1_COSET_MAX_GROUP_LOG && G1_COSET_GROUP_LOG <= G1_COSET_MAX_GROUP_LOG,
                   "knobs.hpp: g1_ntt_mac_kernel keeps the words of at most 2^G1_COSET_MAX_GROUP_LOG terms");
     o->group_log = (unsigned)knob_int(KNOB_KZG_COSET_GROUP_LOG, G1_COSET_GROUP_LOG);
-    o->slot = ctx().slot;
-    o->device = ctx().device;
     const G1CosetSizes sz = g1_coset_sizes(log_n, log_l, o->group_log);
-    {   // refused before anything is allocated when the sizes exceed the caller's budget or the free memory; a failed allocation
-        // after that ends in the same message, and `o` releases what it got
-        const size_t budget = (size_t)knob_int(KNOB_KZG_OPENER_MAX_BYTES);
-        const DevFree mem;
-        const bool fits = sz.total <= budget && (!mem.total_b || sz.total <= mem.free_b);
-        if (!fits || o->srs_hat.grow(sz.srs_hat) != hipSuccess || o->work.grow(sz.total - sz.srs_hat) != hipSuccess) {
-            (void)hipGetLastError();
-            return mem.refuse("zkp_kzg_opener_create_cosets: the workspaces of " + std::to_string(sz.total) + " bytes (" +
-                                  std::to_string(sz.srs_hat) + " kept slices + " + std::to_string(sz.total - sz.srs_hat) + " per call) do not fit",
-                              ", ZKP_KZG_OPENER_MAX_BYTES " + std::to_string(budget));
-        }
-    }
+    ZCHK(reserve_or_refuse(sz.total, KNOB_KZG_OPENER_MAX_BYTES,
+                           "zkp_kzg_opener_create_cosets: the workspaces of " + std::to_string(sz.total) + " bytes (" + std::to_string(sz.srs_hat) +
+                               " kept slices + " + std::to_string(sz.total - sz.srs_hat) + " per call) do not fit",
+                           [&] { return o->srs_hat.grow(sz.srs_hat) == hipSuccess && o->work.grow(sz.total - sz.srs_hat) == hipSuccess; }));
     const CosetWork w = coset_work(o.get());
     // slice b: 2r points of the plane-major array of 2n, at b 2r; all of them are transformed where they stay, stage by stage together
     // (the table of these transforms is where the calls keep theirs)

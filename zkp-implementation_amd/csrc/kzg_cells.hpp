@@ -4,14 +4,12 @@
 #pragma once
 #include "ff.hpp"
 #include "fr29.hpp"
+#include "fr_pow2.hpp"
 #include "kzg_cells_plan.hpp"
 
 namespace zkp {
 
-// (w^l)^(2^b), b < 23: c_i = (w^l)^(k_i) is the product over the set bits of k_i < r <= 2^23 (no squarings on the device)
-struct CellsRho {
-    Fr p[KZG_CELLS_MAX_LOG];
-};
+static_assert(KZG_CELLS_MAX_LOG == FR_POW2_BITS, "fr_pow2.hpp: a coset's index has KZG_CELLS_MAX_LOG bits");
 
 // Lane t < chunks l: row q = t / l of the chunk sums, element j = t % l.  Consecutive lanes read consecutive 32-byte elements of a
 // cell.  From l = 64 on a wave lies inside one chunk (`uniform`, a kernel argument): its chunk bounds, cell ids and weights are then
@@ -59,17 +57,13 @@ __global__ __launch_bounds__(KZG_CELLS_THREADS) void cells_tail_kernel(const Fr*
 // commitment, summed in the chunk's order.
 __global__ __launch_bounds__(KZG_CELLS_THREADS) void cells_scalars_kernel(const Fr* __restrict__ weights, const uint32_t* __restrict__ cell_coset,
                                                                           const uint32_t* __restrict__ by_commit,
-                                                                          const uint32_t* __restrict__ cchunk_start, CellsRho rho, uint64_t cells,
+                                                                          const uint32_t* __restrict__ cchunk_start, FrPow2 rho, uint64_t cells,
                                                                           uint64_t cchunks, Fr* __restrict__ proof_scalar,
                                                                           Fr* __restrict__ cpartial) {
     const uint64_t t = (uint64_t)blockIdx.x * KZG_CELLS_THREADS + threadIdx.x;
     if (t < cells) {
         const uint32_t k = cell_coset[t];
-        Fr v = weights[t];
-#pragma unroll 1
-        for (unsigned b = 0; b < KZG_CELLS_MAX_LOG && (k >> b) != 0; b++)
-            if ((k >> b) & 1) v = v * rho.p[b];
-        proof_scalar[t] = v;
+        proof_scalar[t] = fr_pow2_mul(weights[t], rho, k);
     } else if (t - cells < cchunks) {
         const uint64_t q = t - cells;
         const uint32_t first = cchunk_start[q], last = cchunk_start[q + 1];

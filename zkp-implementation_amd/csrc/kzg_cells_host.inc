@@ -3,21 +3,15 @@
 // grouping tables and every size are in kzg_cells_plan.hpp, the kernels in kzg_cells.hpp; the points are validated with the kernels
 // of g1_check.hpp and summed by the MSM driver; the two pairings are the host's (verify_host.inc).
 
-struct zkp_kzg_cell_verifier {
-    unsigned log_n = 0, log_l = 0;
+struct zkp_kzg_cell_verifier : KzgHandle {  // work: kzg_cells_sizes
     unsigned chunk_log = 0;  // ZKP_KZG_CELLS_CHUNK_LOG as it was at creation
     uint64_t max_cells = 0, max_commits = 0;
-    int slot = 0, device = 0;
     const zkp_bases* srs = nullptr;  // borrowed: [(sum rho_i I_i)(s)]_1 is an MSM of l terms over it
     G2Aff g2sl = G2Aff::infinity();  // [s^l]_2, validated at creation
-    CellsRho rho;                    // (w^l)^(2^b)
+    FrPow2 rho;                      // the powers of w^l
     Fr r_mont;                       // r = n / l as a residue
     KzgCellsSizes sz;
-    DevBuf work;                     // kzg_cells_sizes: entries of a slot are serialised, so one call uses it at a time
-    // the tables on their way to the device; a call waits for the previous call's copy out of the buffer only
-    mutable PinnedBuf stage;
-    mutable Event stage_free;
-    mutable bool stage_pending = false;
+    mutable HostStage stage;                // the tables on their way to the device
     mutable std::vector<uint32_t> scratch;  // where the sorts count (host)
 };
 
@@ -52,14 +46,12 @@ int kzg_cells_aggregate_locked(const zkp_kzg_cell_verifier* v, size_t n_commits,
     const unsigned log_l = v->log_l, log_r = v->log_n - log_l;
     const uint64_t n = (uint64_t)1 << v->log_n, l = (uint64_t)1 << log_l;
     char* base = static_cast<char*>(v->work.p);
-    if (v->stage_pending) HIPCHK(hipEventSynchronize(v->stage_free));
-    v->stage_pending = false;
-    uint32_t* table = static_cast<uint32_t*>(v->stage.p);
+    ZCHK(v->stage.acquire());
+    uint32_t* table = static_cast<uint32_t*>(v->stage.buf.p);
     const KzgCellsTables t = kzg_cells_tables(v->log_n, log_l, v->chunk_log, commit_index, coset_index, n_cells, n_commits, v->scratch.data(), table);
     if (t.words > v->sz.table_words) return fail(ZKP_E_DEVICE, "internal error: the tables of a call outgrew the verifier's");
     HIPCHK(hipMemcpyAsync(base + v->sz.table, table, 4 * t.words, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(v->stage_free, st));
-    v->stage_pending = true;
+    ZCHK(v->stage.sent(st));
     const uint32_t* d_table = reinterpret_cast<const uint32_t*>(base + v->sz.table);
     Fr* a = reinterpret_cast<Fr*>(base + v->sz.a);
     Fr* partial = reinterpret_cast<Fr*>(base + v->sz.partial);
@@ -167,13 +159,7 @@ int kzg_verify_cells_locked(const zkp_kzg_cell_verifier* v, const void* d_commit
 
 extern "C" {
 
-void zkp_kzg_cell_verifier_destroy(zkp_kzg_cell_verifier* v) {
-    if (!v) return;
-    DeviceRestore restore;
-    (void)hipSetDevice(v->device);
-    (void)hipDeviceSynchronize();  // a call may still be running on the caller's stream
-    delete v;
-}
+void zkp_kzg_cell_verifier_destroy(zkp_kzg_cell_verifier* v) { handle_destroy(v); }
 
 int zkp_kzg_cell_verifier_create(const zkp_bases* srs, const uint64_t g2_sl_xy[24], unsigned log_n, unsigned log_l, size_t max_cells,
                                  size_t max_commits, zkp_kzg_cell_verifier** out) try {
@@ -188,41 +174,27 @@ int zkp_kzg_cell_verifier_create(const zkp_bases* srs, const uint64_t g2_sl_xy[2
     G2Aff g2sl = G2Aff::infinity();
     ZCHK(g2_validate(g2_sl_xy, "[s^l]_2", &g2sl));
     CTX_ENTER(srs->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
-    std::unique_ptr<zkp_kzg_cell_verifier, void (*)(zkp_kzg_cell_verifier*)> v(new (std::nothrow) zkp_kzg_cell_verifier(),
-                                                                                  zkp_kzg_cell_verifier_destroy);
+    auto v = handle_new<zkp_kzg_cell_verifier>(log_n, log_l);
     if (!v) return fail(ZKP_E_NOMEM, "host allocation failed");
     static_assert(kKnobs[KNOB_KZG_CELLS_CHUNK_LOG].hi == KZG_CELLS_MAX_CHUNK_LOG && KZG_CELLS_CHUNK_LOG <= KZG_CELLS_MAX_CHUNK_LOG &&
                       kKnobs[KNOB_KZG_CELLS_CHUNK_LOG].lo == 0,
                   "knobs.hpp: the chunk log of kzg_cells_plan.hpp");
-    v->log_n = log_n;
-    v->log_l = log_l;
     v->chunk_log = (unsigned)knob_int(KNOB_KZG_CELLS_CHUNK_LOG, KZG_CELLS_CHUNK_LOG);
     v->max_cells = max_cells;
     v->max_commits = max_commits;
-    v->slot = ctx().slot;
-    v->device = ctx().device;
     v->srs = srs;
     v->g2sl = g2sl;
-    HFr rho = fr_root_of_unity(log_n - log_l);
-    for (unsigned b = 0; b < KZG_CELLS_MAX_LOG; b++, rho = rho.sqr()) v->rho.p[b] = HostField<Fr>::dev(rho);
+    v->rho = fr_pow2_table(fr_root_of_unity(log_n - log_l));
     v->r_mont = HostField<Fr>::dev(HFr::from_u64(r));
     v->sz = kzg_cells_sizes(log_n, log_l, v->chunk_log, max_cells, max_commits);
     const KzgCellsSizes& sz = v->sz;
-    {   // refused before anything is allocated when the device has not that much free; a failed allocation ends in the same message
-        const DevFree mem;
-        const bool fits = !mem.total_b || sz.total <= mem.free_b;
-        if (!fits || v->work.grow(sz.total) != hipSuccess || v->stage.grow(sz.stage_total) != hipSuccess) {
-            (void)hipGetLastError();
-            v->work.release();
-            v->stage.release();
-            return mem.refuse("zkp_kzg_cell_verifier_create: the workspace of " + std::to_string(sz.total) + " bytes (and " +
-                              std::to_string(sz.stage_total) + " pinned) does not fit");
-        }
-    }
+    ZCHK(reserve_or_refuse(sz.total, KNOB_COUNT,
+                           "zkp_kzg_cell_verifier_create: the workspace of " + std::to_string(sz.total) + " bytes (and " +
+                               std::to_string(sz.stage_total) + " pinned) does not fit",
+                           [&] { return v->work.grow(sz.total) == hipSuccess && v->stage.make(sz.stage_total) == ZKP_OK; }));
     v->scratch.resize(sz.scratch_words);
-    ZCHK(v->stage_free.ensure(hipEventDisableTiming));
     // the plan, table and scratch of the one transform are built here, not by the first call
     HIPCHK(hipMemsetAsync(v->work.p, 0, sz.partial, st));
     ZCHK(run_ntt<Fr>(reinterpret_cast<Fr*>(static_cast<char*>(v->work.p) + sz.a), log_n, 1, 1, nullptr, st));
@@ -273,11 +245,11 @@ int zkp_kzg_verify_cells(const zkp_kzg_cell_verifier* v, const uint64_t* commits
         return ZKP_OK;
     }
     CTX_ENTER(v->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     const size_t M = n_commits, N = n_cells, l = (size_t)1 << v->log_l;
     void* ws = nullptr;  // evaluations | weights | commitments | proofs | the flags of both
-    ZCHK(g1_ntt_workspace(32 * N * l + 32 * N + 96 * M + 96 * N + M + N, "zkp_kzg_verify_cells", &ws));
+    ZCHK(slot_workspace(32 * N * l + 32 * N + 96 * M + 96 * N + M + N, "zkp_kzg_verify_cells", &ws));
     char* d_evals = static_cast<char*>(ws);
     char* d_weights = d_evals + 32 * N * l;
     char* d_commits = d_weights + 32 * N;

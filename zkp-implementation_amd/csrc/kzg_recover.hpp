@@ -5,20 +5,18 @@
 #pragma once
 #include "ff.hpp"
 #include "fr29.hpp"
+#include "fr_pow2.hpp"
 #include "kzg_recover_plan.hpp"
 #include "plonk.hpp"  // fr_inverse
 
 namespace zkp {
 
-// rho^(2^b), b < 23: rho^k is the product over the set bits of k < r <= 2^23 (no squarings on the device)
-struct RecoverRho {
-    Fr p[KZG_RECOVER_MAX_LOG];
-};
+static_assert(KZG_RECOVER_MAX_LOG == FR_POW2_BITS, "fr_pow2.hpp: a root's index has KZG_RECOVER_MAX_LOG bits");
 
 // Workgroup q: the monic product of the factors (Y - root_j), j in [q per, (q + 1) per), per = 2^per_log <= blockDim.x <= 256 --
 // schoolbook, one lane per coefficient, one factor per step.  After s factors the product is Y^s + sum_{k<s} c[k] Y^k; the factor
 // (Y - a) makes c[k] <- c[k-1] - a c[k] for k <= s, with c[s] standing for the leading 1 and c[-1] = 0.  The pad root is 0.
-__global__ __launch_bounds__(256) void recover_leaf_kernel(const uint32_t* __restrict__ roots, RecoverRho rho, uint32_t per_log,
+__global__ __launch_bounds__(256) void recover_leaf_kernel(const uint32_t* __restrict__ roots, FrPow2 rho, uint32_t per_log,
                                                            Fr* __restrict__ x) {
     __shared__ Fr a[256];
     __shared__ Fr c[256];
@@ -29,9 +27,7 @@ __global__ __launch_bounds__(256) void recover_leaf_kernel(const uint32_t* __res
         Fr v = Fr::zero();
         if (idx != KZG_RECOVER_PAD_ROOT) {
             v = Fr::one();
-#pragma unroll 1
-            for (unsigned b = 0; b < KZG_RECOVER_MAX_LOG && (idx >> b) != 0; b++)
-                if ((idx >> b) & 1) v = v * rho.p[b];
+            v = fr_pow2_mul(v, rho, idx);
         }
         a[t] = v;
     }

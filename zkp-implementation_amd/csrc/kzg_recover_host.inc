@@ -2,19 +2,13 @@
 // its cosets (included at the end of api.hip, after g1_ntt_host.inc).  The kernels are in kzg_recover.hpp; the construction, every
 // launch, index and size in kzg_recover_plan.hpp: the driver walks kzg_recover_step and launches nothing else.
 
-struct zkp_kzg_recoverer {
-    unsigned log_n = 0, log_l = 0;
+struct zkp_kzg_recoverer : KzgHandle {  // work: kzg_recover_sizes
     unsigned leaf_log = 0;  // ZKP_KZG_RECOVER_LEAF_LOG as it was at creation
-    int slot = 0, device = 0;
     uint64_t g[4] = {}, gl[4] = {};  // the coset shift g = 7 and g^l, Montgomery
-    RecoverRho rho;                  // rho^(2^b), rho = w^l the root of the transforms of r
+    FrPow2 rho;                      // the powers of rho = w^l, the root of the transforms of r
     mutable Stream side;             // the inversions of a call run here, beside the transforms of n on the caller's stream
     mutable Event fork, join;        // ... after `fork` on the caller's stream; the divide pass waits for `join`
-    DevBuf work;                     // kzg_recover_sizes: entries of a slot are serialised, so one call uses it at a time
-    // the missing-index list and the mask on their way to the device; a call waits for the previous call's copy out of it only
-    mutable PinnedBuf stage;
-    mutable Event stage_free;
-    mutable bool stage_pending = false;
+    mutable HostStage stage;         // the missing-index list and the mask on their way to the device
 };
 
 namespace {
@@ -54,20 +48,17 @@ int kzg_recover_locked(const zkp_kzg_recoverer* rc, const void* d_evals, const u
     const Fr* evals = static_cast<const Fr*>(d_evals);
     HIPCHK(hipMemsetAsync(d_inconsistent, 0, sizeof(uint32_t), st));
     if (m) {
-        if (rc->stage_pending) HIPCHK(hipEventSynchronize(rc->stage_free));
-        rc->stage_pending = false;
-        uint32_t* roots = reinterpret_cast<uint32_t*>(static_cast<char*>(rc->stage.p) + plan.sz.stage_roots);
+        ZCHK(rc->stage.acquire());
+        uint32_t* roots = reinterpret_cast<uint32_t*>(static_cast<char*>(rc->stage.buf.p) + plan.sz.stage_roots);
         uint64_t at = 0;
         for (uint64_t k = 0; k < r; k++)
             if (!present[k]) roots[at++] = (uint32_t)k;
         for (; at < plan.roots; at++) roots[at] = KZG_RECOVER_PAD_ROOT;
-        uint8_t* mask = reinterpret_cast<uint8_t*>(rc->stage.p) + plan.sz.stage_mask;
+        uint8_t* mask = reinterpret_cast<uint8_t*>(rc->stage.buf.p) + plan.sz.stage_mask;
         for (uint64_t k = 0; k < r; k++) mask[k] = present[k] ? 1 : 0;
         HIPCHK(hipMemcpyAsync(base + plan.sz.roots, roots, 4 * plan.roots, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(base + plan.sz.mask, mask, r, hipMemcpyHostToDevice, st));
-        ZCHK(rc->stage_free.ensure(hipEventDisableTiming));
-        HIPCHK(hipEventRecord(rc->stage_free, st));
-        rc->stage_pending = true;
+        ZCHK(rc->stage.sent(st));
     }
     // two recorded phases while profiling is on: the vanishing polynomial (up to its values on both domains) and everything behind it
     std::unique_ptr<ProfScope> phase(new ProfScope(m ? "kzg_recover_zs" : "kzg_recover_rest", st));
@@ -130,48 +121,29 @@ int kzg_recover_locked(const zkp_kzg_recoverer* rc, const void* d_evals, const u
 
 extern "C" {
 
-void zkp_kzg_recoverer_destroy(zkp_kzg_recoverer* rc) {
-    if (!rc) return;
-    DeviceRestore restore;
-    (void)hipSetDevice(rc->device);
-    (void)hipDeviceSynchronize();  // a call may still be running on the caller's stream
-    delete rc;
-}
+void zkp_kzg_recoverer_destroy(zkp_kzg_recoverer* rc) { handle_destroy(rc); }
 
 int zkp_kzg_recoverer_create(unsigned log_n, unsigned log_l, zkp_kzg_recoverer** out) try {
     if (!out) return fail(ZKP_E_ARG, "null argument");
     if (!kzg_recover_shape_ok(log_n, log_l)) return fail(ZKP_E_ARG, "a recoverer needs log_l < log_n <= 23");
     CTX_ENTER(-1);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
-    std::unique_ptr<zkp_kzg_recoverer, void (*)(zkp_kzg_recoverer*)> rc(new (std::nothrow) zkp_kzg_recoverer(), zkp_kzg_recoverer_destroy);
+    auto rc = handle_new<zkp_kzg_recoverer>(log_n, log_l);
     if (!rc) return fail(ZKP_E_NOMEM, "host allocation failed");
     static_assert(kKnobs[KNOB_KZG_RECOVER_LEAF_LOG].hi == KZG_RECOVER_MAX_LEAF_LOG && KZG_RECOVER_LEAF_LOG <= KZG_RECOVER_MAX_LEAF_LOG &&
                       kKnobs[KNOB_KZG_RECOVER_LEAF_LOG].lo == 1,
                   "knobs.hpp: recover_leaf_kernel is one workgroup of at most 2^KZG_RECOVER_MAX_LEAF_LOG lanes");
-    rc->log_n = log_n;
-    rc->log_l = log_l;
     rc->leaf_log = (unsigned)knob_int(KNOB_KZG_RECOVER_LEAF_LOG, KZG_RECOVER_LEAF_LOG);
-    rc->slot = ctx().slot;
-    rc->device = ctx().device;
     const HFr g = HFr::from_u64(7);
     g.store(rc->g);
     g.pow_u64((uint64_t)1 << log_l).store(rc->gl);
-    HFr rho = fr_root_of_unity(log_n - log_l);
-    for (unsigned b = 0; b < KZG_RECOVER_MAX_LOG; b++, rho = rho.sqr()) rc->rho.p[b] = HostField<Fr>::dev(rho);
+    rc->rho = fr_pow2_table(fr_root_of_unity(log_n - log_l));
     const KzgRecoverSizes sz = kzg_recover_sizes(log_n, log_l);
-    {   // refused before anything is allocated when the sizes exceed the caller's budget or the free memory
-        const size_t budget = (size_t)knob_int(KNOB_KZG_RECOVER_MAX_BYTES);
-        const DevFree mem;
-        const bool fits = sz.total <= budget && (!mem.total_b || sz.total <= mem.free_b);
-        if (!fits || rc->work.grow(sz.total) != hipSuccess || rc->stage.grow(sz.stage_total) != hipSuccess) {
-            (void)hipGetLastError();
-            return mem.refuse("zkp_kzg_recoverer_create: the workspace of " + std::to_string(sz.total) + " bytes (and " +
-                                  std::to_string(sz.stage_total) + " pinned) does not fit",
-                              ", ZKP_KZG_RECOVER_MAX_BYTES " + std::to_string(budget));
-        }
-    }
-    ZCHK(rc->stage_free.ensure(hipEventDisableTiming));
+    ZCHK(reserve_or_refuse(sz.total, KNOB_KZG_RECOVER_MAX_BYTES,
+                           "zkp_kzg_recoverer_create: the workspace of " + std::to_string(sz.total) + " bytes (and " + std::to_string(sz.stage_total) +
+                               " pinned) does not fit",
+                           [&] { return rc->work.grow(sz.total) == hipSuccess && rc->stage.make(sz.stage_total) == ZKP_OK; }));
     ZCHK(rc->side.ensure(hipStreamNonBlocking));
     ZCHK(rc->fork.ensure(hipEventDisableTiming));
     ZCHK(rc->join.ensure(hipEventDisableTiming));
@@ -219,11 +191,11 @@ int zkp_kzg_recover_cosets(const zkp_kzg_recoverer* rc, const uint64_t* evals, c
     uint64_t m = 0;
     ZCHK(recover_args(rc, evals, present, len, out_coeffs, consistent, &m));
     CTX_ENTER(rc->slot);
-    hipStream_t st = g_rt.multi ? ctx().stream : nullptr;
+    hipStream_t st = host_stream();
     WsOrder ord(st);
     const size_t n = (size_t)1 << rc->log_n;
     void* ws = nullptr;  // evaluations in | coefficients | evaluations out | the word
-    ZCHK(g1_ntt_workspace(32 * n + 32 * len + 32 * n + 32, "zkp_kzg_recover_cosets", &ws));
+    ZCHK(slot_workspace(32 * n + 32 * len + 32 * n + 32, "zkp_kzg_recover_cosets", &ws));
     char* d_evals = static_cast<char*>(ws);
     char* d_coeffs = d_evals + 32 * n;
     char* d_out_evals = d_coeffs + 32 * len;

@@ -147,13 +147,7 @@ void zkp_nova_transcript_destroy(zkp_nova_transcript* t) { delete t; }
 
 int zkp_nova_transcript_feed(zkp_nova_transcript* t, const uint64_t xy[12], uint8_t is_inf) try {
     if (!t || (!is_inf && !xy)) return fail(ZKP_E_ARG, "null argument");
-    uint64_t x[6] = {0}, y[6] = {0};  // serialize_uncompressed takes the canonical coordinates
-    if (!is_inf) {
-        const HFq cx = HFq::load(xy).from_mont(), cy = HFq::load(xy + 6).from_mont();
-        std::memcpy(x, cx.l, 48);
-        std::memcpy(y, cy.l, 48);
-    }
-    t->gen.feed(x, y, is_inf != 0);
+    transcript_feed_g1(t->gen, xy, is_inf);
     return ZKP_OK;
 } ZKP_CATCH_INT
 

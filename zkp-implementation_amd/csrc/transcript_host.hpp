@@ -20,6 +20,8 @@
 #include <string>
 #include <vector>
 
+#include "host_ff.hpp"
+
 namespace zkp {
 
 class Sha256 {
@@ -288,5 +290,16 @@ private:
     std::array<uint8_t, 32> data_{};
     bool has_data_ = false, generated_ = false;
 };
+
+// A point as the C ABI carries it (Montgomery coordinates) fed to the generator: serialize_uncompressed takes the canonical ones
+inline void transcript_feed_g1(PlonkChallengeGenerator& gen, const uint64_t xy[12], uint8_t is_inf) {
+    uint64_t x[6] = {0}, y[6] = {0};
+    if (!is_inf) {
+        const host::HFq cx = host::HFq::load(xy).from_mont(), cy = host::HFq::load(xy + 6).from_mont();
+        std::memcpy(x, cx.l, 48);
+        std::memcpy(y, cy.l, 48);
+    }
+    gen.feed(x, y, is_inf != 0);
+}
 
 }  // namespace zkp

@@ -292,6 +292,24 @@ def _dev_ptr(t, min_bytes):
     return C.c_void_p(t.data_ptr())
 
 
+class _Handle:
+    """An opaque handle of the library in ``_h``, released once through the entry ``_destroy`` names; csrc/kzg_handle.inc is the other
+    side.  close() after close(), on a null handle or on an instance whose creation failed before ``_h`` was set does nothing."""
+
+    _destroy = None  # the zkp_*_destroy of the subclass
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            getattr(lib(), self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ----------------------------------------------------------------------------- bases / MSM
 class _BasesExpansion(C.Structure):  # zkp_bases_expansion in include/zkp_hip.h
     _fields_ = [("window_bits", C.c_uint), ("slices", C.c_uint), ("planes", C.c_uint), ("glv", C.c_uint), ("widest_slice_bits", C.c_uint),
@@ -342,8 +360,9 @@ def srs_check(bases, g2s, n, r):
     return int(ok.value)
 
 
-class G1Bases:
+class G1Bases(_Handle):
     """Base points resident in HBM (the SRS of kzg/src/srs.rs:14-21, uploaded once)."""
+    _destroy = "zkp_g1_bases_destroy"
 
     def __init__(self, handle):
         self._h = handle
@@ -407,17 +426,6 @@ class G1Bases:
 
     def __len__(self):
         return int(lib().zkp_g1_bases_len(self._h))
-
-    def close(self):
-        if self._h:
-            lib().zkp_g1_bases_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def msm_g1(bases, scalars):
@@ -841,8 +849,9 @@ def kzg_aggregate_commitments(commitments, challenge, is_inf=None):
     return out, int(oinf.value)
 
 
-class PlonkTranscript:
+class PlonkTranscript(_Handle):
     """ChallengeGenerator<Sha256> (plonk/src/challenge.rs:22-77)."""
+    _destroy = "zkp_plonk_transcript_destroy"
 
     def __init__(self):
         self._h = C.c_void_p()
@@ -856,13 +865,6 @@ class PlonkTranscript:
         out = np.zeros((n, 4), dtype=np.uint64)
         _chk(lib().zkp_plonk_transcript_challenges(self._h, n, _ptr(out)))
         return out
-
-    def close(self):
-        if self._h:
-            lib().zkp_plonk_transcript_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
 
 def poly_mul_fr(a, b):
@@ -913,9 +915,10 @@ def g1_ntt(xy, is_inf=None, inverse=False):
     return xy, inf
 
 
-class KzgOpener:
+class KzgOpener(_Handle):
     """zkp_kzg_opener: all n = 2^log_n openings of a polynomial at the roots of unity in one call (Feist-Khovratovich); with
     log_l > 0 the n / 2^log_l multi-point proofs, one per coset of 2^log_l points (open_cosets)."""
+    _destroy = "zkp_kzg_opener_destroy"
 
     def __init__(self, srs_bases, log_n, log_l=0):
         self.log_n, self.n, self.log_l = log_n, 1 << log_n, log_l
@@ -957,21 +960,11 @@ class KzgOpener:
         _chk(lib().zkp_kzg_open_cosets_dev(self._h, _dev_ptr(coeffs_tensor, 32 * length), length, _dev_ptr(out_xy_tensor, 96 * self.cosets),
                                            _dev_ptr(out_inf_tensor, self.cosets), ev, _stream_ptr(stream)))
 
-    def close(self):
-        if self._h:
-            lib().zkp_kzg_opener_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class KzgRecoverer:
+class KzgRecoverer(_Handle):
     """zkp_kzg_recoverer: the polynomial behind the cells of KzgOpener.open_cosets from any cosets that determine it.  Made on the
     calling thread's slot; needs no SRS."""
+    _destroy = "zkp_kzg_recoverer_destroy"
 
     def __init__(self, log_n, log_l):
         self.log_n, self.n, self.log_l = log_n, 1 << log_n, log_l
@@ -999,17 +992,6 @@ class KzgRecoverer:
                                               _dev_ptr(out_coeffs_tensor, 32 * int(length)), ev, _dev_ptr(inconsistent_tensor, 4),
                                               _stream_ptr(stream)))
 
-    def close(self):
-        if self._h:
-            lib().zkp_kzg_recoverer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _points(p):
     """(xy, is_inf) or xy alone -> ((count, 12) limbs, (count,) flags or None)"""
@@ -1018,9 +1000,10 @@ def _points(p):
     return xy, (_np(inf, np.uint8, (xy.shape[0],)) if inf is not None else None)
 
 
-class KzgCellVerifier:
+class KzgCellVerifier(_Handle):
     """zkp_kzg_cell_verifier: any number of cells of KzgOpener.open_cosets, of any number of commitments, behind one pairing check.
     srs_bases is borrowed (kept alive here); g2_sl_xy = [s^l]_2.  The weights are the caller's randomness: see include/zkp_hip.h."""
+    _destroy = "zkp_kzg_cell_verifier_destroy"
 
     def __init__(self, srs_bases, g2_sl_xy, log_n, log_l, max_cells, max_commits):
         self.log_n, self.n, self.log_l, self.l = log_n, 1 << log_n, log_l, 1 << log_l
@@ -1073,17 +1056,6 @@ class KzgCellVerifier:
                                                _dev_ptr(weights_tensor, 32 * cells), _dev_ptr(out_interp_tensor, 32 * self.l),
                                                _dev_ptr(out_commit_weights_tensor, 32 * n_commits),
                                                _dev_ptr(out_proof_scalars_tensor, 32 * cells), _stream_ptr(stream)))
-
-    def close(self):
-        if self._h:
-            lib().zkp_kzg_cell_verifier_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Srs:
@@ -1259,8 +1231,9 @@ class PlonkCircuit:
         return PlonkProver.from_gates(srs_bases, *self.gate_table())
 
 
-class PlonkProver:
+class PlonkProver(_Handle):
     """Round-by-round face of generate_proof (plonk/src/prover.rs:61-293); blinders and challenges are inputs."""
+    _destroy = "zkp_plonk_prover_destroy"
 
     def __init__(self, srs_bases, log_n, circuit_polys, k1, k2):
         """circuit_polys: dict name -> (len,4) uint64 coefficient array (names in CIRCUIT_POLYS)."""
@@ -1341,17 +1314,6 @@ class PlonkProver:
         acc = C.c_int(0)
         _chk(lib().zkp_plonk_verify(self._h, _ptr(g2s), C.byref(out), C.byref(acc)))
         return int(acc.value)
-
-    def close(self):
-        if self._h:
-            lib().zkp_plonk_prover_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _pts(xy, inf):

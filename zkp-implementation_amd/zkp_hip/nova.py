@@ -11,7 +11,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import G1Bases, KzgScheme, ZkpError, ZKP_E_ARG, _chk, _dev_ptr, _np, _ptr, _stream_ptr, kzg_commit, lib
+from . import G1Bases, KzgScheme, ZkpError, ZKP_E_ARG, _Handle, _chk, _dev_ptr, _np, _ptr, _stream_ptr, kzg_commit, lib
 
 _R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 FR_ONE = np.array([(((1 << 256) % _R) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)  # Fr::one()
@@ -73,8 +73,9 @@ def csr_from_triplets(rows, row_idx, cols, vals):
     return row_ptr, np.asarray(cols, dtype=np.uint32)[order], _np(vals, np.uint64, (-1, 4))[order]
 
 
-class NovaR1CS:
+class NovaR1CS(_Handle):
     """R1CS (r1cs/mod.rs:9-16) resident on the SRS's device as CSR (zkp_nova_r1cs_create)."""
+    _destroy = "zkp_nova_r1cs_destroy"
 
     def __init__(self, srs, rows, num_vars, num_io, a, b, c):
         """a, b, c: (row_ptr, cols, vals) CSR triples."""
@@ -123,13 +124,6 @@ class NovaR1CS:
         _chk(lib().zkp_nova_relaxed_residual_dev(self._h, _dev_ptr(w, 32 * self.num_vars), _ptr(x), _ptr(u), _dev_ptr(e, 32 * self.rows),
                                                  _stream_ptr(stream), C.byref(bad)))
         return int(bad.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().zkp_nova_r1cs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
 
 def _bases(srs):
@@ -215,8 +209,9 @@ class NifsProof:
                          ((_arr(s.open_w_xy), int(s.open_w_is_inf)), _arr(s.eval_w)))
 
 
-class NovaTranscript:
+class NovaTranscript(_Handle):
     """Transcript<Sha256> (nova/src/transcript.rs)."""
+    _destroy = "zkp_nova_transcript_destroy"
 
     def __init__(self):
         self._h = C.c_void_p()
@@ -237,13 +232,6 @@ class NovaTranscript:
         return out
 
     challenges = generate_challenges
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().zkp_nova_transcript_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
 
 # ----------------------------------------------------------------------------- NIFS
