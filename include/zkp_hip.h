@@ -327,6 +327,28 @@ int zkp_kzg_open_cosets(const zkp_kzg_opener *o, const uint64_t *coeffs, size_t 
                         uint64_t *out_evals);
 int zkp_kzg_open_cosets_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_t len, void *d_out_xy, uint8_t *d_out_is_inf,
                             void *d_out_evals, void *stream);
+/* The coset openings of a batch of polynomials in one call: every dependent step of zkp_kzg_open_cosets runs once for all of them,
+ * so a batch costs about what one polynomial costs until the device is full (profiles/kzg_open_cosets_batch.md).
+ * zkp_kzg_opener_create_cosets_batch makes an opener for up to max_polys (1 .. 4096, else ZKP_E_ARG) polynomials per call;
+ * zkp_kzg_opener_create_cosets is this creation with max_polys = 1, and every other condition and refusal is the same.  The opener
+ * owns the workspaces of a whole batch from creation on: per polynomial 256 B x 2n / B of partial sums (where a lane sums B < l
+ * terms), 768 B x r and 64 B x n of scalars -- with the committed B = 1 about 512 n + 768 r + 64 n bytes, 4.7 MiB at (log_n, log_l) =
+ * (13, 6), about 600 MiB at (20, 6) -- next to the 256 B x 2n of kept slices and a table of 256 B x min(max_polys 2n, 2^18).  What
+ * does not fit, ZKP_KZG_OPENER_MAX_BYTES included, is ZKP_E_NOMEM with the kept slices, the per-call bytes and max_polys in
+ * zkp_last_error() and nothing left allocated.  An opener of any max_polys serves zkp_kzg_open_cosets* (and zkp_kzg_open_all* at
+ * log_l = 0); one of log_l = 0 serves the batch entries: all n openings of each polynomial.
+ * zkp_kzg_open_cosets_batch: polynomial p < n_polys has its len coefficients at coeffs + 4 stride p; stride is in scalars, the
+ * scalars between len and stride are not read (a shorter polynomial of a batch is a row with trailing zeros).  Outputs are
+ * polynomial-major -- out_xy n_polys x r x 12 limbs, out_is_inf n_polys x r bytes, out_evals n_polys x n x 4 limbs or NULL -- and
+ * row p of each is byte for byte what zkp_kzg_open_cosets returns for polynomial p.  Refused before anything is launched: a null
+ * argument ZKP_E_ARG, len == 0 ZKP_E_ARG, len > n ZKP_E_SIZE, stride < len ZKP_E_ARG, n_polys > max_polys ZKP_E_SIZE (with both
+ * numbers in zkp_last_error()); n_polys == 0 is ZKP_OK without touching the device.  The device entry, like
+ * zkp_kzg_open_cosets_dev, neither allocates nor synchronises. */
+int zkp_kzg_opener_create_cosets_batch(const zkp_bases *srs, unsigned log_n, unsigned log_l, size_t max_polys, zkp_kzg_opener **out);
+int zkp_kzg_open_cosets_batch(const zkp_kzg_opener *o, const uint64_t *coeffs, size_t n_polys, size_t len, size_t stride,
+                              uint64_t *out_xy, uint8_t *out_is_inf, uint64_t *out_evals);
+int zkp_kzg_open_cosets_batch_dev(const zkp_kzg_opener *o, const void *d_coeffs, size_t n_polys, size_t len, size_t stride,
+                                  void *d_out_xy, uint8_t *d_out_is_inf, void *d_out_evals, void *stream);
 /* host + one commitment on the GPU: the check of one coset proof.  evals[j] = f(x w_l^j) for j < l = 2^log_l, w_l the root of
  * zkp_ntt_fr for log_l (for coset k of an opener: x = w^k, evals[j] = out_evals[k + j r]); g2_sl is [s^l]_2.  Accepts iff
  *   e(W, [s^l]_2 - [x^l]_2) == e(C - [I(s)]_1, G_2),

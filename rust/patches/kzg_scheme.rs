@@ -150,4 +150,39 @@ impl KzgScheme {
         assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
         accepted != 0
     }
+
+    /// The cells of a whole block: the coset openings of every polynomial of `polys` (rows of equal length, zero-padded by the
+    /// caller) in ONE call of zkp_kzg_open_cosets_batch -- every dependent step of the opener runs once for all of them.  Returns,
+    /// per polynomial, its n / l proofs and its n evaluations in natural order (the values of coset k are evals[k + j r]).  A
+    /// long-lived producer keeps the opener instead of making one per call.
+    pub fn open_cosets_batch(&self, polys: &[Vec<Fr>], log_n: u32, log_l: u32) -> Vec<(Vec<G1Point>, Vec<Fr>)> {
+        let (n, r) = (1usize << log_n, 1usize << (log_n - log_l));
+        if polys.is_empty() {
+            return Vec::new();
+        }
+        let len = polys[0].len();
+        assert!(polys.iter().all(|p| p.len() == len));
+        let coeffs: Vec<Fr> = polys.iter().flatten().copied().collect();
+        let mut o = core::ptr::null_mut();
+        let rc = unsafe { sys::zkp_kzg_opener_create_cosets_batch(self.1.ptr, log_n, log_l, polys.len(), &mut o) };
+        assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
+        let mut xy = vec![0u64; polys.len() * r * 12];
+        let mut inf = vec![0u8; polys.len() * r];
+        let mut evals = vec![Fr::from(0u64); polys.len() * n];
+        let rc = unsafe {
+            sys::zkp_kzg_open_cosets_batch(o, coeffs.as_ptr() as *const u64, polys.len(), len, len, xy.as_mut_ptr(), inf.as_mut_ptr(),
+                                           evals.as_mut_ptr() as *mut u64)
+        };
+        unsafe { sys::zkp_kzg_opener_destroy(o) };
+        assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
+        let limb = |o: usize| BigInt::<6>([xy[o], xy[o + 1], xy[o + 2], xy[o + 3], xy[o + 4], xy[o + 5]]);
+        (0..polys.len())
+            .map(|p| {
+                let proofs = (p * r..(p + 1) * r)
+                    .map(|i| if inf[i] != 0 { G1Point::zero() } else { G1Point::new_unchecked(Fp::new_unchecked(limb(12 * i)), Fp::new_unchecked(limb(12 * i + 6))) })
+                    .collect();
+                (proofs, evals[p * n..(p + 1) * n].to_vec())
+            })
+            .collect()
+    }
 }

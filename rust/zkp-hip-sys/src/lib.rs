@@ -170,6 +170,9 @@ extern "C" {
     pub fn zkp_kzg_opener_create_cosets(srs: *const zkp_bases, log_n: u32, log_l: u32, out: *mut *mut zkp_kzg_opener) -> i32;
     pub fn zkp_kzg_open_cosets(o: *const zkp_kzg_opener, coeffs: *const u64, len: usize, out_xy: *mut u64, out_is_inf: *mut u8, out_evals: *mut u64) -> i32;
     pub fn zkp_kzg_open_cosets_dev(o: *const zkp_kzg_opener, d_coeffs: *const c_void, len: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, d_out_evals: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_kzg_opener_create_cosets_batch(srs: *const zkp_bases, log_n: u32, log_l: u32, max_polys: usize, out: *mut *mut zkp_kzg_opener) -> i32;
+    pub fn zkp_kzg_open_cosets_batch(o: *const zkp_kzg_opener, coeffs: *const u64, n_polys: usize, len: usize, stride: usize, out_xy: *mut u64, out_is_inf: *mut u8, out_evals: *mut u64) -> i32;
+    pub fn zkp_kzg_open_cosets_batch_dev(o: *const zkp_kzg_opener, d_coeffs: *const c_void, n_polys: usize, len: usize, stride: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, d_out_evals: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_kzg_verify_coset(srs: *const zkp_bases, g2_sl_xy: *const u64, commit_xy: *const u64, commit_is_inf: u8, w_xy: *const u64, w_is_inf: u8, x: *const u64, log_l: u32, evals: *const u64, accepted: *mut i32) -> i32;
     pub fn zkp_kzg_recoverer_create(log_n: u32, log_l: u32, out: *mut *mut zkp_kzg_recoverer) -> i32;
     pub fn zkp_kzg_recoverer_destroy(rc: *mut zkp_kzg_recoverer);

@@ -7,7 +7,7 @@
 //   g1_ntt_load_kernel<RAW>   96-byte ABI points or the 128-byte points of a handle -> the workspace, bit-reversed when asked
 //   g1_ntt_butterfly_kernel   one lane per butterfly of a stage: (a, b) <- (a + [w]b, a - [w]b)
 //   g1_ntt_mul_kernel         one lane per point, in place: P_i <- [k_i] P_i (zkp_g1_scale_dev, the n^-1 of an inverse)
-//   g1_ntt_slice_kernel       a run of points of one workspace into another, identities behind it
+//   g1_ntt_slice_kernel       a run of points of u per polynomial of a batch into its h, identities behind it
 //   g1_ntt_store_kernel<RAW>  the workspace -> affine, one safegcd inversion per lane
 // and for the openers (zkp_kzg_open_cosets and, as its l = 1 case, zkp_kzg_open_all), at the end of this file:
 //   g1_ntt_load_slices_kernel the points of a handle -> the l slices of an opener, each bit-reversed
@@ -170,15 +170,16 @@ __global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mul_kernel(uint4* ws, u
     r.store_s(ws + i, cap);
 }
 
-// slot i of `map` <- src[source(i)], the identity where there is none
-__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_slice_kernel(const uint4* __restrict__ src, uint64_t scap, G1NttLoadMap map,
-                                                                  uint4* __restrict__ dst, uint64_t dcap) {
-    const uint64_t i = (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
-    if (i >= map.count) return;
-    const int64_t s = g1_ntt_load_source(map, i);
-    uint4* d = dst + (map.rev_log ? g1_ntt_bitrev((uint32_t)i, map.rev_log) : i);
+// slot i in [first, polys * map.count) of the slices h of a batch <- its source in the batch's u (g1_coset_batch_slice: slot
+// i mod r of polynomial i / r), the identity where there is none
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_slice_kernel(const uint4* __restrict__ src, uint64_t scap, G1NttLoadMap map, uint32_t log_m,
+                                                                  uint64_t polys, uint64_t first, uint4* __restrict__ dst, uint64_t dcap) {
+    const uint64_t i = first + (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= polys * map.count) return;
+    const G1CosetSlice c = g1_coset_batch_slice(map, log_m, i);
+    uint4* d = dst + c.dst;
 #pragma unroll
-    for (int q = 0; q < 16; q++) d[q * dcap] = s >= 0 ? src[q * scap + (uint64_t)s] : make_uint4(0u, 0u, 0u, 0u);
+    for (int q = 0; q < 16; q++) d[q * dcap] = c.src >= 0 ? src[q * scap + (uint64_t)c.src] : make_uint4(0u, 0u, 0u, 0u);
 }
 
 // points [first, n) of the workspace to affine (as many as the launch has lanes): RAW the ABI's 96 bytes (zeros for the identity), else a handle's 128 bytes, canonical
@@ -228,13 +229,14 @@ __global__ __launch_bounds__(MSM_THREADS) void g1_ntt_load_slices_kernel(const u
     p.store_s(ws + (b << log_m) + g1_ntt_bitrev((uint32_t)j, log_m), cap);
 }
 
-// the l rows of g, 2r slots each, out of the strided coefficients: slot i of the 2n in [first, ...)
-__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_gather_kernel(const Fr* __restrict__ coeffs, uint64_t len, uint32_t log_n, uint32_t log_l,
-                                                                   uint64_t first, Fr* __restrict__ g) {
+// the l rows of g of every polynomial of a batch, 2r slots each, out of the strided coefficients (rows of `len`, `stride` scalars
+// apart): slot i of the polys * 2n in [first, ...)
+__global__ __launch_bounds__(MSM_THREADS) void g1_ntt_gather_kernel(const Fr* __restrict__ coeffs, uint64_t len, uint64_t stride, uint64_t polys,
+                                                                   uint32_t log_n, uint32_t log_l, uint64_t first, Fr* __restrict__ g) {
     const uint64_t i = first + (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
-    if (i >> (log_n + 1)) return;
-    const uint32_t log_m = log_n - log_l + 1;
-    const int64_t s = g1_coset_coeff_source(log_n, log_l, len, i >> log_m, i & (((uint64_t)1 << log_m) - 1));
+    const G1CosetOf o = g1_coset_of(log_n + 1, i);
+    if (o.p >= polys) return;
+    const int64_t s = g1_coset_batch_coeff_source(log_n, log_l, len, stride, o.p, o.in);
     (s >= 0 ? Fr::load(coeffs + s) : Fr::zero()).store(g + i);
 }
 
@@ -258,15 +260,18 @@ __global__ __launch_bounds__(MSM_THREADS) void g1_ntt_split_kernel(Fr* g, const 
 // P_j + phi(P_j)} as in g1_28_mul_glv.  halves: what g1_ntt_split_kernel left, 8 words per element.  The lane keeps the current word
 // of every half in its column of `words` (indexed by j: registers cannot be), the rest stays in memory; P_j + phi(P_j) goes to entry
 // j * count + lane of the table, made by the loop's own addition in step -1.  Terms with a zero scalar or an identity point are
-// masked out before the loop.  The sum goes to dst[bitrev(k, rev_log)] when rev_log is given (one group per output), else to
-// dst[first + lane], the partial sums the fold takes.
+// masked out before the loop.  In a batch (g1_coset_batch) the 2^lanes_log lanes of polynomial p follow those of p - 1: the scalar
+// of a term is the element of the batch lane, which lies in p's rows of g, and the point it multiplies the element of the lane within
+// its polynomial -- the transformed SRS is the same for every p.  The sum goes to slot bitrev(k, rev_log) of p's u when rev_log is
+// given (one group per output), else to dst[first + lane], the partial sums the fold takes.
 __global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mac_kernel(const uint4* __restrict__ srs, uint64_t scap, const uint32_t* __restrict__ halves,
-                                                                    uint32_t log_m, uint32_t terms, uint64_t first, uint32_t count, uint4* dst,
-                                                                    uint64_t dcap, uint32_t rev_log, uint4* table, uint64_t tcap) {
+                                                                    uint32_t log_m, uint32_t terms, uint32_t lanes_log, uint64_t first,
+                                                                    uint32_t count, uint4* dst, uint64_t dcap, uint32_t rev_log, uint4* table,
+                                                                    uint64_t tcap) {
     __shared__ uint32_t words[2 << G1_COSET_MAX_GROUP_LOG][G1_NTT_THREADS];
     const uint32_t lane = blockIdx.x * G1_NTT_THREADS + threadIdx.x;
     if (lane >= count) return;
-    const uint64_t i = first + lane;
+    const uint64_t i = first + lane, in = g1_coset_of(lanes_log, i).in;  // the batch lane (scalars); the lane within its polynomial (points)
     uint32_t live = 0;
 #pragma unroll 1
     for (uint32_t j = 0; j < terms; j++) {
@@ -274,7 +279,7 @@ __global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mac_kernel(const uint4*
         const uint4* kk = reinterpret_cast<const uint4*>(halves + 8 * e);
         const uint4 a = kk[0], b = kk[1];
         const bool zero = (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0;
-        if (!zero && !Fq28::load_s(srs + e + 8 * scap, scap).all_zero()) live |= 1u << j;
+        if (!zero && !Fq28::load_s(srs + g1_coset_mac_element(log_m, terms, in, j) + 8 * scap, scap).all_zero()) live |= 1u << j;
     }
     const Fq28 beta = G1Check28::beta();
     X28 acc = X28::infinity();
@@ -296,7 +301,7 @@ __global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mac_kernel(const uint4*
 #pragma unroll 1
         for (uint32_t j = 0; j < terms; j++) {
             if (!((live >> j) & 1)) continue;
-            const uint4* p = srs + g1_coset_mac_element(log_m, terms, i, j);
+            const uint4* p = srs + g1_coset_mac_element(log_m, terms, in, j);
             uint4* t = table + (uint64_t)j * count + lane;
             uint32_t sel = 2;
             if (s < 0) acc = X28::load_s(p, scap);  // the step that makes the third table entry: P + phi(P)
@@ -313,20 +318,22 @@ __global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_mac_kernel(const uint4*
             }
         }
     }
-    acc.store_s(dst + (rev_log ? g1_ntt_bitrev((uint32_t)(i & (((uint64_t)1 << log_m) - 1)), rev_log) : i), dcap);
+    acc.store_s(dst + (rev_log ? g1_coset_batch_u(rev_log, g1_coset_of(lanes_log, i).p, in) : i), dcap);
 }
 
-// One step of the fold (g1_coset_fold_step): partial i += partial i + half_lanes for lane i in [first, half_lanes); the last step
-// (rev_log given, half_lanes = 2r) writes the sum to dst[bitrev(i, rev_log)] instead
-__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_fold_kernel(uint4* part, uint64_t pcap, uint64_t half_lanes, uint64_t first, uint4* dst,
-                                                                     uint64_t dcap, uint32_t rev_log) {
-    const uint64_t i = first + (uint64_t)blockIdx.x * G1_NTT_THREADS + threadIdx.x;
-    if (i >= half_lanes) return;
-    X28 a = X28::load_s(part + i, pcap);
-    const X28 b = X28::load_s(part + i + half_lanes, pcap);
+// One step of the fold (g1_coset_fold_step, g1_coset_fold_lane): lane j in [first, polys << step_log) adds, within the 2^lanes_log
+// partial sums of its polynomial, partial `hi` into partial `lo`; the last step (rev_log given, 2^step_log = 2r) writes the sum to
+// its slot of that polynomial's u instead
+__global__ __launch_bounds__(G1_NTT_THREADS) void g1_ntt_fold_kernel(uint4* part, uint64_t pcap, uint32_t lanes_log, uint32_t step_log, uint64_t polys,
+                                                                     uint64_t first, uint4* dst, uint64_t dcap, uint32_t rev_log) {
+    const uint64_t j = first + (uint64_t)blockIdx.x * G1_NTT_THREADS + threadIdx.x;
+    const G1CosetFoldLane f = g1_coset_fold_lane(lanes_log, step_log, j);
+    if (f.p >= polys) return;
+    X28 a = X28::load_s(part + f.lo, pcap);
+    const X28 b = X28::load_s(part + f.hi, pcap);
     g1_28_add(a, b);
-    if (rev_log) a.store_s(dst + g1_ntt_bitrev((uint32_t)i, rev_log), dcap);
-    else a.store_s(part + i, pcap);
+    if (rev_log) a.store_s(dst + g1_coset_batch_u(rev_log, f.p, f.in), dcap);
+    else a.store_s(part + f.lo, pcap);
 }
 
 }  // namespace zkp

@@ -1,5 +1,6 @@
-// g1_ntt_host.inc -- zkp_g1_scale_dev, zkp_g1_ntt*, zkp_g1_bases_lagrange, the openers zkp_kzg_opener_* with zkp_kzg_open_cosets* and
-// zkp_kzg_open_all* (one construction: all openings are the cosets of one point, log_l = 0) and the verifier zkp_kzg_verify_coset
+// g1_ntt_host.inc -- zkp_g1_scale_dev, zkp_g1_ntt*, zkp_g1_bases_lagrange, the openers zkp_kzg_opener_* with zkp_kzg_open_cosets*,
+// zkp_kzg_open_cosets_batch* and zkp_kzg_open_all* (one construction and one driver: all openings are the cosets of one point,
+// log_l = 0, and one polynomial is the batch of one) and the verifier zkp_kzg_verify_coset
 // (included at the end of api.hip, after verify_host.inc).  The kernels are in g1_ntt.hpp, every index and size in g1_ntt_plan.hpp.
 
 namespace {
@@ -130,9 +131,10 @@ const char* const kShardedG1Ntt = "bases are sharded over several devices: a tra
 }  // namespace
 
 // log_l: one proof per coset of 2^log_l points; 0: all n openings.  work: (the partial sums,) u, the slice h, the scalars g and the
-// lanes' table of one call
+// lanes' table of one call of up to max_polys polynomials
 struct zkp_kzg_opener : KzgHandle {
     unsigned group_log = 0;  // a lane of the multiply-accumulate pass sums 2^group_log terms (g1_coset_mac; one at most when l = 1)
+    uint64_t max_polys = 1;  // polynomials of one call (zkp_kzg_open_cosets_batch*); the other entries open one
     DevBuf srs_hat;  // the l slices of the reversed SRS points, each transformed (NTT_2r): depends on the SRS, n and l only
 };
 
@@ -233,7 +235,7 @@ int kzg_open_all_args(const zkp_kzg_opener* o, const void* coeffs, size_t len, c
     return ZKP_OK;
 }
 
-// the l rows of g, each of 2^log_m scalars, transformed in place (a batched transform takes at most 65535 rows)
+// `rows` rows of 2^log_m scalars each, transformed in place (a batched transform takes at most 65535 rows)
 int coset_fr_rows(Fr* g, unsigned log_m, uint64_t rows, hipStream_t st) {
     const uint64_t step = 32768;
     for (uint64_t first = 0; first < rows; first += step)
@@ -241,17 +243,17 @@ int coset_fr_rows(Fr* g, unsigned log_m, uint64_t rows, hipStream_t st) {
     return ZKP_OK;
 }
 
-// where the pieces of an opener's `work` begin (g1_coset_sizes)
+// where the pieces of an opener's `work` begin (g1_coset_sizes); every vector has room for max_polys polynomials
 struct CosetWork {
     G1CosetSizes sz;
-    G1CosetMac mac;
+    G1CosetMac mac;  // of one polynomial
     uint4 *partial, *u, *h, *table;
     Fr* g;
     uint64_t tcap;
 };
 CosetWork coset_work(const zkp_kzg_opener* o) {
     CosetWork w;
-    w.sz = g1_coset_sizes(o->log_n, o->log_l, o->group_log);
+    w.sz = g1_coset_sizes(o->log_n, o->log_l, o->group_log, o->max_polys);
     w.mac = g1_coset_mac(o->log_n, o->log_l, o->group_log);
     char* base = static_cast<char*>(o->work.p);
     w.partial = reinterpret_cast<uint4*>(base);
@@ -263,56 +265,72 @@ CosetWork coset_work(const zkp_kzg_opener* o) {
     return w;
 }
 
-// One call of an opener, log_l = 0 (all openings, r = n) as any other: everything on the device, on `st`; the caller is inside the
-// opener's slot
-int kzg_open_locked(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void* d_out_xy, uint8_t* d_out_is_inf, void* d_out_evals,
-                    hipStream_t st) {
+// the evaluations of `rows` polynomials on the whole domain: rows of n, natural order (coset k at k + j r)
+int coset_evals(const void* d_coeffs, uint64_t rows, size_t len, size_t stride, unsigned log_n, void* d_out_evals, hipStream_t st) {
+    const size_t n = (size_t)1 << log_n;
+    HIPCHK(hipMemsetAsync(d_out_evals, 0, 32 * n * rows, st));
+    if (rows == 1) HIPCHK(hipMemcpyAsync(d_out_evals, d_coeffs, 32 * len, hipMemcpyDeviceToDevice, st));
+    else HIPCHK(hipMemcpy2DAsync(d_out_evals, 32 * n, d_coeffs, 32 * stride, 32 * len, rows, hipMemcpyDeviceToDevice, st));
+    return coset_fr_rows(static_cast<Fr*>(d_out_evals), log_n, rows, st);
+}
+
+// One call of an opener over n_polys <= max_polys polynomials (rows of len coefficients, `stride` scalars apart), log_l = 0 (all
+// openings, r = n) as any other and one polynomial as any other number: every step runs once, for all polynomials together.
+// Everything on the device, on `st`; the caller is inside the opener's slot.  Outputs are polynomial-major.
+int kzg_open_locked(const zkp_kzg_opener* o, const void* d_coeffs, uint64_t n_polys, size_t len, size_t stride, void* d_out_xy,
+                    uint8_t* d_out_is_inf, void* d_out_evals, hipStream_t st) {
     const unsigned log_n = o->log_n, log_l = o->log_l, log_r = log_n - log_l, log_m = log_r + 1;
     const uint64_t n = (uint64_t)1 << log_n, r = (uint64_t)1 << log_r, l = (uint64_t)1 << log_l;
     const CosetWork w = coset_work(o);
-    const G1NttVec u{w.u, 2 * r, w.table, w.tcap}, h{w.h, r, w.table, w.tcap};
-    // the l rows of g, transformed as one batch; then every scalar times (2r)^-1, split
+    const G1CosetBatch bt = g1_coset_batch(log_n, log_l, o->group_log, n_polys, w.tcap);
+    const G1NttVec u{w.u, o->max_polys * 2 * r, w.table, w.tcap}, h{w.h, o->max_polys * r, w.table, w.tcap};
     const Fr* row = nullptr;
     ZCHK(g1_ntt_twiddle_row(log_m, 1, st, &row));
-    ZCHK(g1_ntt_io_launches(2 * n, [&](uint64_t first, uint64_t cnt) {
-        hipLaunchKernelGGL(g1_ntt_gather_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st,
-                           static_cast<const Fr*>(d_coeffs), (uint64_t)len, (uint32_t)log_n, (uint32_t)log_l, first, w.g);
-    }));
-    ZCHK(coset_fr_rows(w.g, log_m, l, st));
-    ZCHK(g1_ntt_io_launches(2 * n, [&](uint64_t first, uint64_t cnt) {
-        hipLaunchKernelGGL(g1_ntt_split_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st, w.g, row + G1_NTT_TW_NINV,
-                           first, 2 * n);
-    }));
-    // U_k = sum_b [g^_k] S^_k: the lanes' groups, then the fold of the partial sums into u (bit-reversed for the stages); one group per
-    // output (always so at l = 1) writes u itself
-    const bool folded = w.mac.groups > 1;
-    for (uint64_t k = 0; k < g1_coset_mac_launches(w.mac); k++) {
-        const uint64_t cnt = g1_coset_mac_launch_lanes(w.mac, k);
-        hipLaunchKernelGGL(g1_ntt_mac_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st,
-                           static_cast<const uint4*>(o->srs_hat.p), 2 * n, reinterpret_cast<const uint32_t*>(w.g), (uint32_t)log_m, w.mac.terms,
-                           k * w.mac.launch_lanes, (uint32_t)cnt, folded ? w.partial : u.pts, folded ? w.mac.lanes : u.cap,
-                           folded ? 0u : (uint32_t)log_m, w.table, w.tcap);
-        HIPCHK(hipGetLastError());
-    }
-    for (unsigned i = 0; i < g1_coset_fold_steps(w.mac); i++) {
-        const G1CosetFoldStep f = g1_coset_fold_step(log_n, log_l, w.mac, i);
-        ZCHK(g1_ntt_io_launches(f.lanes, [&](uint64_t first, uint64_t cnt) {
-            hipLaunchKernelGGL(g1_ntt_fold_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, w.partial, w.mac.lanes,
-                               f.lanes, first, u.pts, u.cap, f.last ? (uint32_t)log_m : 0u);
+    {   // the l rows of g of every polynomial, transformed as one batch; then every scalar times (2r)^-1, split
+        ProfScope ps("kzg_open_scalars", st);
+        ZCHK(g1_ntt_io_launches(n_polys * 2 * n, [&](uint64_t first, uint64_t cnt) {
+            hipLaunchKernelGGL(g1_ntt_gather_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st,
+                               static_cast<const Fr*>(d_coeffs), (uint64_t)len, (uint64_t)stride, n_polys, (uint32_t)log_n, (uint32_t)log_l, first, w.g);
+        }));
+        ZCHK(coset_fr_rows(w.g, log_m, n_polys * l, st));
+        ZCHK(g1_ntt_io_launches(n_polys * 2 * n, [&](uint64_t first, uint64_t cnt) {
+            hipLaunchKernelGGL(g1_ntt_split_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st, w.g, row + G1_NTT_TW_NINV,
+                               first, n_polys * 2 * n);
         }));
     }
-    ZCHK(g1_ntt_stages(u, log_m, 1, false, st));
-    // the proofs: NTT_r of the slice h
-    hipLaunchKernelGGL(g1_ntt_slice_kernel, dim3(g1_ntt_blocks(r, MSM_THREADS)), dim3(MSM_THREADS), 0, st, u.pts, u.cap,
-                       g1_coset_slice_map(log_n, log_l), h.pts, h.cap);
-    HIPCHK(hipGetLastError());
-    ZCHK(g1_ntt_stages(h, log_r, 0, false, st));
-    ZCHK(g1_ntt_store<true>(h, r, d_out_xy, d_out_is_inf, st));
-    if (d_out_evals) {  // f on the whole domain, natural order: coset k at k + j r
-        HIPCHK(hipMemsetAsync(d_out_evals, 0, 32 * n, st));
-        HIPCHK(hipMemcpyAsync(d_out_evals, d_coeffs, 32 * len, hipMemcpyDeviceToDevice, st));
-        ZCHK(run_ntt<Fr>(static_cast<Fr*>(d_out_evals), log_n, 1, 0, nullptr, st));
+    {   // U_k = sum_b [g^_k] S^_k: the lanes' groups, then the fold of the partial sums into u (bit-reversed for the stages); one group
+        // per output (always so at l = 1) writes u itself
+        ProfScope ps("kzg_open_mac", st);
+        const bool folded = w.mac.groups > 1;
+        const uint64_t pcap = o->max_polys << bt.lanes_log;
+        for (uint64_t k = 0; k < g1_coset_batch_launches(bt); k++) {
+            const uint64_t cnt = g1_coset_batch_launch_lanes(bt, k);
+            hipLaunchKernelGGL(g1_ntt_mac_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st,
+                               static_cast<const uint4*>(o->srs_hat.p), 2 * n, reinterpret_cast<const uint32_t*>(w.g), (uint32_t)log_m,
+                               w.mac.terms, (uint32_t)bt.lanes_log, k * bt.launch_lanes, (uint32_t)cnt, folded ? w.partial : u.pts, folded ? pcap : u.cap,
+                               folded ? 0u : (uint32_t)log_m, w.table, w.tcap);
+            HIPCHK(hipGetLastError());
+        }
+        for (unsigned i = 0; i < g1_coset_fold_steps(w.mac); i++) {
+            const G1CosetFoldStep f = g1_coset_fold_step(log_n, log_l, w.mac, i);
+            const unsigned step_log = g1_coset_fold_step_log(log_n, log_l, w.mac, i);
+            ZCHK(g1_ntt_io_launches(n_polys * f.lanes, [&](uint64_t first, uint64_t cnt) {
+                hipLaunchKernelGGL(g1_ntt_fold_kernel, dim3(g1_ntt_blocks(cnt, G1_NTT_THREADS)), dim3(G1_NTT_THREADS), 0, st, w.partial, pcap,
+                                   (uint32_t)bt.lanes_log, (uint32_t)step_log, n_polys, first, u.pts, u.cap, f.last ? (uint32_t)log_m : 0u);
+            }));
+        }
     }
+    {   // u of every polynomial stage by stage together; the proofs: NTT_r of the slices h, likewise
+        ProfScope ps("kzg_open_transforms", st);
+        ZCHK(g1_ntt_stages(u, log_m, 1, false, st, n_polys));
+        ZCHK(g1_ntt_io_launches(n_polys * r, [&](uint64_t first, uint64_t cnt) {
+            hipLaunchKernelGGL(g1_ntt_slice_kernel, dim3(g1_ntt_blocks(cnt, MSM_THREADS)), dim3(MSM_THREADS), 0, st, u.pts, u.cap,
+                               g1_coset_slice_map(log_n, log_l), (uint32_t)log_m, n_polys, first, h.pts, h.cap);
+        }));
+        ZCHK(g1_ntt_stages(h, log_r, 0, false, st, n_polys));
+        ZCHK(g1_ntt_store<true>(h, n_polys * r, d_out_xy, d_out_is_inf, st));
+    }
+    if (d_out_evals) ZCHK(coset_evals(d_coeffs, n_polys, len, stride, log_n, d_out_evals, st));
     return ZKP_OK;
 }
 
@@ -323,7 +341,7 @@ int kzg_open_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t len, void
     CTX_ENTER(o->slot);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     WsOrder ord(st);
-    return kzg_open_locked(o, d_coeffs, len, d_out_xy, d_out_is_inf, d_out_evals, st);
+    return kzg_open_locked(o, d_coeffs, 1, len, len, d_out_xy, d_out_is_inf, d_out_evals, st);
 }
 
 // the host entries (`what`: the entry's name), r = n / l proofs out
@@ -341,7 +359,7 @@ int kzg_open_host(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, u
     char* d_xy = d_evals + 32 * n;
     uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * r);
     HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 32 * len, hipMemcpyHostToDevice, st));
-    ZCHK(kzg_open_locked(o, d_coeffs, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
+    ZCHK(kzg_open_locked(o, d_coeffs, 1, len, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
     HIPCHK(hipMemcpyAsync(out_xy, d_xy, 96 * r, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, r, hipMemcpyDeviceToHost, st));
     if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n, hipMemcpyDeviceToHost, st));
@@ -349,12 +367,25 @@ int kzg_open_host(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t len, u
     return ZKP_OK;
 }
 
+// zkp_kzg_open_cosets_batch*: every refusal, before anything is launched; *none: an empty batch, nothing to do
+int kzg_open_batch_args(const zkp_kzg_opener* o, const void* coeffs, size_t n_polys, size_t len, size_t stride, const void* out_xy,
+                        const void* out_is_inf, bool* none) {
+    ZCHK(kzg_open_all_args(o, coeffs, len, out_xy, out_is_inf, true));
+    if (stride < len) return fail(ZKP_E_ARG, "stride < len: the rows of coefficients overlap");
+    if (n_polys > o->max_polys)
+        return fail(ZKP_E_SIZE, "a batch of " + std::to_string(n_polys) + " polynomials on an opener made for " + std::to_string(o->max_polys) +
+                                    " (max_polys of zkp_kzg_opener_create_cosets_batch)");
+    *none = n_polys == 0;
+    return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned log_l, zkp_kzg_opener** out) try {
+int zkp_kzg_opener_create_cosets_batch(const zkp_bases* srs, unsigned log_n, unsigned log_l, size_t max_polys, zkp_kzg_opener** out) try {
     if (!srs || !out) return fail(ZKP_E_ARG, "null argument");
+    if (max_polys == 0 || max_polys > G1_COSET_MAX_POLYS) return fail(ZKP_E_ARG, "an opener takes 1 .. 4096 polynomials per call (max_polys)");
     if (!g1_coset_shape_ok(log_n, log_l)) return fail(ZKP_E_ARG, "an opener needs log_l < log_n <= 23");
     if (!srs->shards.empty()) return fail(ZKP_E_ARG, kShardedG1Ntt);
     const uint64_t n = (uint64_t)1 << log_n, l = (uint64_t)1 << log_l;
@@ -367,10 +398,12 @@ int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned 
     static_assert(kKnobs[KNOB_KZG_COSET_GROUP_LOG].hi == G1_COSET_MAX_GROUP_LOG && G1_COSET_GROUP_LOG <= G1_COSET_MAX_GROUP_LOG,
                   "knobs.hpp: g1_ntt_mac_kernel keeps the words of at most 2^G1_COSET_MAX_GROUP_LOG terms");
     o->group_log = (unsigned)knob_int(KNOB_KZG_COSET_GROUP_LOG, G1_COSET_GROUP_LOG);
-    const G1CosetSizes sz = g1_coset_sizes(log_n, log_l, o->group_log);
+    o->max_polys = max_polys;
+    const G1CosetSizes sz = g1_coset_sizes(log_n, log_l, o->group_log, max_polys);
     ZCHK(reserve_or_refuse(sz.total, KNOB_KZG_OPENER_MAX_BYTES,
                            "zkp_kzg_opener_create_cosets: the workspaces of " + std::to_string(sz.total) + " bytes (" + std::to_string(sz.srs_hat) +
-                               " kept slices + " + std::to_string(sz.total - sz.srs_hat) + " per call) do not fit",
+                               " kept slices + " + std::to_string(sz.total - sz.srs_hat) + " per call of max_polys " + std::to_string(max_polys) +
+                               ") do not fit",
                            [&] { return o->srs_hat.grow(sz.srs_hat) == hipSuccess && o->work.grow(sz.total - sz.srs_hat) == hipSuccess; }));
     const CosetWork w = coset_work(o.get());
     // slice b: 2r points of the plane-major array of 2n, at b 2r; all of them are transformed where they stay, stage by stage together
@@ -383,14 +416,60 @@ int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned 
     ZCHK(g1_ntt_stages(all, log_n - log_l + 1, 0, false, st, l));
     {   // Everything a call builds on first use is built here, so that zkp_kzg_open_*_dev neither allocate nor wait: the plans, tables
         // and scratch of its Fr transforms (over the zeroed scalar area) and the constants of its point transforms
+        // (a call of one polynomial and a call of max_polys may take different plans of an Fr transform, and the larger needs the
+        // larger scratch: both are run)
         const Fr* row = nullptr;
         HIPCHK(hipMemsetAsync(w.g, 0, sz.scalars, st));
-        ZCHK(coset_fr_rows(w.g, log_n - log_l + 1, l, st));
-        ZCHK(run_ntt<Fr>(w.g, log_n, 1, 0, nullptr, st));
+        for (const uint64_t polys : {(uint64_t)1, (uint64_t)max_polys}) {
+            ZCHK(coset_fr_rows(w.g, log_n - log_l + 1, polys * l, st));
+            ZCHK(coset_fr_rows(w.g, log_n, polys, st));
+            if (max_polys == 1) break;
+        }
         ZCHK(g1_ntt_twiddle_row(log_n - log_l + 1, 1, st, &row));
     }
     HIPCHK(hipStreamSynchronize(st));
     *out = o.release();
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_kzg_opener_create_cosets(const zkp_bases* srs, unsigned log_n, unsigned log_l, zkp_kzg_opener** out) {
+    return zkp_kzg_opener_create_cosets_batch(srs, log_n, log_l, 1, out);
+}
+
+int zkp_kzg_open_cosets_batch_dev(const zkp_kzg_opener* o, const void* d_coeffs, size_t n_polys, size_t len, size_t stride, void* d_out_xy,
+                                  uint8_t* d_out_is_inf, void* d_out_evals, void* stream) try {
+    bool none = false;
+    ZCHK(kzg_open_batch_args(o, d_coeffs, n_polys, len, stride, d_out_xy, d_out_is_inf, &none));
+    if (none) return ZKP_OK;
+    CTX_ENTER(o->slot);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    return kzg_open_locked(o, d_coeffs, n_polys, len, stride, d_out_xy, d_out_is_inf, d_out_evals, st);
+} ZKP_CATCH_INT
+
+// the rows are packed on the way to the device: what lies between len and stride is not read
+int zkp_kzg_open_cosets_batch(const zkp_kzg_opener* o, const uint64_t* coeffs, size_t n_polys, size_t len, size_t stride, uint64_t* out_xy,
+                              uint8_t* out_is_inf, uint64_t* out_evals) try {
+    bool none = false;
+    ZCHK(kzg_open_batch_args(o, coeffs, n_polys, len, stride, out_xy, out_is_inf, &none));
+    if (none) return ZKP_OK;
+    CTX_ENTER(o->slot);
+    hipStream_t st = host_stream();
+    WsOrder ord(st);
+    const size_t n = (size_t)1 << o->log_n, r = n >> o->log_l, P = n_polys;
+    void* ws = nullptr;  // coefficients | evaluations | points | flags
+    ZCHK(slot_workspace(P * (32 * len + 32 * n + 96 * r + r), "zkp_kzg_open_cosets_batch", &ws));
+    char* d_coeffs = static_cast<char*>(ws);
+    char* d_evals = d_coeffs + 32 * len * P;
+    char* d_xy = d_evals + 32 * n * P;
+    uint8_t* d_inf = reinterpret_cast<uint8_t*>(d_xy + 96 * r * P);
+    if (stride == len || P == 1) HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 32 * len * P, hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemcpy2DAsync(d_coeffs, 32 * len, coeffs, 32 * stride, 32 * len, P, hipMemcpyHostToDevice, st));
+    ZCHK(kzg_open_locked(o, d_coeffs, P, len, len, d_xy, d_inf, out_evals ? d_evals : nullptr, st));
+    HIPCHK(hipMemcpyAsync(out_xy, d_xy, 96 * r * P, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_is_inf, d_inf, r * P, hipMemcpyDeviceToHost, st));
+    if (out_evals) HIPCHK(hipMemcpyAsync(out_evals, d_evals, 32 * n * P, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return ZKP_OK;
 } ZKP_CATCH_INT
 

@@ -174,19 +174,112 @@ inline G1CosetFoldStep g1_coset_fold_step(unsigned log_n, unsigned log_l, const 
     return f;
 }
 
+// A batch of n_polys polynomials in one call (zkp_kzg_open_cosets_batch): every vector of a call is max_polys times as long and
+// polynomial p has what one polynomial has, p times that vector's length further on -- its rows of g at p 2n, its partial sums at
+// p lanes1 (lanes1: G1CosetMac.lanes of one polynomial), its u at p 2r, its h at p r -- while the transformed SRS is shared.  Lanes
+// per polynomial, 2n, 2r and r are powers of two, so a lane finds its polynomial by a shift; n_polys is any number.  One polynomial
+// is the batch of one: p = 0 in everything below.
+constexpr uint64_t G1_COSET_MAX_POLYS = 4096;
+inline unsigned g1_coset_lanes_log(unsigned log_n, unsigned log_l, unsigned group_log) {  // log2 of lanes1
+    return log_n + 1 - (group_log < log_l ? group_log : log_l);
+}
+// Entries of the lanes' table of an opener for up to max_polys polynomials.  A launch of the multiply-accumulate pass parks one
+// entry per TERM, the transforms of u and h one per lane of a grid row: neither may be cut by G1_NTT_LAUNCH alone, since for small n
+// the table has fewer entries than that.
+inline uint64_t g1_coset_table_entries(unsigned log_n, uint64_t max_polys) {
+    const uint64_t terms = max_polys << (log_n + 1);
+    return terms < G1_NTT_LAUNCH ? terms : G1_NTT_LAUNCH;
+}
+// The multiply-accumulate pass of n_polys polynomials: lane L < lanes belongs to polynomial L / lanes1 and is lane L mod lanes1 of
+// it.  A launch takes as many lanes as the table of `tcap` entries holds terms for, G1_NTT_LAUNCH terms at most; with tcap of
+// g1_coset_table_entries(log_n, 1) and one polynomial these are the launches of g1_coset_mac.
+struct G1CosetBatch {
+    G1CosetMac one;         // of one polynomial
+    unsigned lanes_log;     // log2 one.lanes
+    uint64_t n_polys, lanes, launch_lanes;
+};
+inline G1CosetBatch g1_coset_batch(unsigned log_n, unsigned log_l, unsigned group_log, uint64_t n_polys, uint64_t tcap) {
+    G1CosetBatch b;
+    b.one = g1_coset_mac(log_n, log_l, group_log);
+    b.lanes_log = g1_coset_lanes_log(log_n, log_l, group_log);
+    b.n_polys = n_polys;
+    b.lanes = n_polys << b.lanes_log;
+    b.launch_lanes = (tcap < G1_NTT_LAUNCH ? tcap : G1_NTT_LAUNCH) / b.one.terms;
+    return b;
+}
+inline uint64_t g1_coset_batch_launches(const G1CosetBatch& b) { return b.launch_lanes ? (b.lanes + b.launch_lanes - 1) / b.launch_lanes : 0; }
+inline uint64_t g1_coset_batch_launch_lanes(const G1CosetBatch& b, uint64_t k) {
+    const uint64_t first = k * b.launch_lanes;
+    return first >= b.lanes ? 0 : b.lanes - first < b.launch_lanes ? b.lanes - first : b.launch_lanes;
+}
+// what the kernels take of a batch: lane L or slot i of a vector of 2^log per polynomial is slot `in` of polynomial p
+struct G1CosetOf {
+    uint64_t p, in;
+};
+ZKP_G1NTT_FN G1CosetOf g1_coset_of(unsigned log, uint64_t i) { return G1CosetOf{i >> log, i & (((uint64_t)1 << log) - 1)}; }
+// Term j of batch lane L = p lanes1 + i: since lanes1 terms = 2n, g1_coset_mac_element(log_m, terms, L, j) is p 2n + the element of
+// lane i of one polynomial -- the term's scalar in the batch's rows of g as it stands.  Its point, in the transformed SRS that all
+// polynomials share, is g1_coset_mac_element of lane i = g1_coset_of(lanes_log, L).in, which is that element mod 2n: the kernel
+// takes the former (the address of a point then advances with j as it does for one polynomial, and the compiler schedules the
+// loads of a point as it did: profiles/kzg_open_cosets_batch.md), tests/host/g1_coset_batch_plan.cpp pins the two against each other
+ZKP_G1NTT_FN uint64_t g1_coset_batch_srs(unsigned log_n, uint64_t e) { return e & (((uint64_t)2 << log_n) - 1); }
+// output k < 2r of polynomial p in the batch's u, where the stages expect it
+ZKP_G1NTT_FN uint64_t g1_coset_batch_u(unsigned log_m, uint64_t p, uint64_t k) { return (p << log_m) + g1_ntt_bitrev((uint32_t)k, log_m); }
+// slot t of g of polynomial p: where its coefficient sits in rows `stride` scalars apart, -1: zero
+ZKP_G1NTT_FN int64_t g1_coset_batch_coeff_source(unsigned log_n, unsigned log_l, uint64_t len, uint64_t stride, uint64_t p, uint64_t t) {
+    const unsigned log_m = log_n - log_l + 1;
+    const int64_t s = g1_coset_coeff_source(log_n, log_l, len, t >> log_m, t & (((uint64_t)1 << log_m) - 1));
+    return s < 0 ? s : (int64_t)(p * stride) + s;
+}
+// Lane j < n_polys f.lanes of fold step f (f.lanes = 2^step_log per polynomial): partial `lo` += partial `lo + f.lanes`, both inside
+// polynomial p's lanes1 partial sums; the last step writes to g1_coset_batch_u(log_m, p, in)
+struct G1CosetFoldLane {
+    uint64_t p, in, lo, hi;
+};
+ZKP_G1NTT_FN G1CosetFoldLane g1_coset_fold_lane(unsigned lanes_log, unsigned step_log, uint64_t j) {
+    const G1CosetOf o = g1_coset_of(step_log, j);
+    G1CosetFoldLane f;
+    f.p = o.p;
+    f.in = o.in;
+    f.lo = (o.p << lanes_log) + o.in;
+    f.hi = f.lo + ((uint64_t)1 << step_log);
+    return f;
+}
+inline unsigned g1_coset_fold_step_log(unsigned log_n, unsigned log_l, const G1CosetMac& m, unsigned i) {  // log2 of g1_coset_fold_step(..).lanes
+    unsigned g = 0;
+    while (((uint64_t)1 << g) < m.groups) g++;
+    return g - (i + 1) + (log_n - log_l + 1);
+}
+// Slot i < n_polys r of the batch's h (all polynomials contiguous, r apart, each bit-reversed for its transform of r): its source in
+// the batch's u, -1: the identity
+struct G1CosetSlice {
+    int64_t src;
+    uint64_t dst;
+};
+ZKP_G1NTT_FN G1CosetSlice g1_coset_batch_slice(const G1NttLoadMap& map, unsigned log_m, uint64_t i) {  // map: g1_coset_slice_map, count = 2^rev_log
+    const G1CosetOf o = g1_coset_of(map.rev_log, i);
+    const int64_t s = g1_ntt_load_source(map, o.in);
+    G1CosetSlice c;
+    c.src = s < 0 ? s : (int64_t)(o.p << log_m) + s;
+    c.dst = (o.p << map.rev_log) + g1_ntt_bitrev((uint32_t)o.in, map.rev_log);
+    return c;
+}
+
+// Per polynomial of a batch: 256 B x lanes1 of partial sums (where there is a fold; 512 n at the committed group size), 768 r of u and
+// h, 64 n of scalars.
 struct G1CosetSizes {
     size_t srs_hat, partial, work, slice, scalars, table, total;  // the l transformed slices (kept); the partial sums, u, h, g, the lanes' table
 };
-inline G1CosetSizes g1_coset_sizes(unsigned log_n, unsigned log_l, unsigned group_log) {
+inline G1CosetSizes g1_coset_sizes(unsigned log_n, unsigned log_l, unsigned group_log, uint64_t max_polys = 1) {
     const uint64_t n = (uint64_t)1 << log_n, r = n >> log_l;
     const G1CosetMac m = g1_coset_mac(log_n, log_l, group_log);
     G1CosetSizes s;
     s.srs_hat = G1_NTT_POINT_BYTES * 2 * n;
-    s.partial = m.groups > 1 ? G1_NTT_POINT_BYTES * m.lanes : 0;
-    s.work = G1_NTT_POINT_BYTES * 2 * r;
-    s.slice = G1_NTT_POINT_BYTES * r;
-    s.scalars = 32 * 2 * n;
-    s.table = g1_ntt_sizes(log_n + 1, 2 * n).table;  // one entry per term of the longest launch; the stages need fewer
+    s.partial = m.groups > 1 ? G1_NTT_POINT_BYTES * m.lanes * max_polys : 0;
+    s.work = G1_NTT_POINT_BYTES * 2 * r * max_polys;
+    s.slice = G1_NTT_POINT_BYTES * r * max_polys;
+    s.scalars = 32 * 2 * n * max_polys;
+    s.table = G1_NTT_POINT_BYTES * g1_coset_table_entries(log_n, max_polys);  // one entry per term of the longest launch; the stages need fewer
     s.total = s.srs_hat + s.partial + s.work + s.slice + s.scalars + s.table;
     return s;
 }

@@ -67,6 +67,9 @@ _SIGS = {
     "zkp_kzg_opener_create_cosets": ([_VP, C.c_uint, C.c_uint, C.POINTER(_VP)], C.c_int),
     "zkp_kzg_open_cosets": ([_VP, _VP, _SZ, _VP, _U8P, _VP], C.c_int),
     "zkp_kzg_open_cosets_dev": ([_VP, _VP, _SZ, _VP, _U8P, _VP, _VP], C.c_int),
+    "zkp_kzg_opener_create_cosets_batch": ([_VP, C.c_uint, C.c_uint, _SZ, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_open_cosets_batch": ([_VP, _VP, _SZ, _SZ, _SZ, _VP, _U8P, _VP], C.c_int),
+    "zkp_kzg_open_cosets_batch_dev": ([_VP, _VP, _SZ, _SZ, _SZ, _VP, _U8P, _VP, _VP], C.c_int),
     "zkp_kzg_verify_coset": ([_VP, _VP, _VP, C.c_uint8, _VP, C.c_uint8, _VP, C.c_uint, _VP, C.POINTER(C.c_int)], C.c_int),
     "zkp_kzg_recoverer_create": ([C.c_uint, C.c_uint, C.POINTER(_VP)], C.c_int),
     "zkp_kzg_recoverer_destroy": ([_VP], None),
@@ -917,14 +920,17 @@ def g1_ntt(xy, is_inf=None, inverse=False):
 
 class KzgOpener(_Handle):
     """zkp_kzg_opener: all n = 2^log_n openings of a polynomial at the roots of unity in one call (Feist-Khovratovich); with
-    log_l > 0 the n / 2^log_l multi-point proofs, one per coset of 2^log_l points (open_cosets)."""
+    log_l > 0 the n / 2^log_l multi-point proofs, one per coset of 2^log_l points (open_cosets); with max_polys > 1 those of up to
+    max_polys polynomials in one call (open_cosets_batch), for which the opener owns the workspaces from creation on."""
     _destroy = "zkp_kzg_opener_destroy"
 
-    def __init__(self, srs_bases, log_n, log_l=0):
-        self.log_n, self.n, self.log_l = log_n, 1 << log_n, log_l
+    def __init__(self, srs_bases, log_n, log_l=0, max_polys=1):
+        self.log_n, self.n, self.log_l, self.max_polys = log_n, 1 << log_n, log_l, max_polys
         self.cosets = self.n >> log_l
         self._h = C.c_void_p()
-        if log_l:
+        if max_polys != 1:
+            _chk(lib().zkp_kzg_opener_create_cosets_batch(srs_bases._h, log_n, log_l, max_polys, C.byref(self._h)))
+        elif log_l:
             _chk(lib().zkp_kzg_opener_create_cosets(srs_bases._h, log_n, log_l, C.byref(self._h)))
         else:  # (the same creation with log_l = 0; called by its own name so that the suite runs both entries)
             _chk(lib().zkp_kzg_opener_create(srs_bases._h, log_n, C.byref(self._h)))
@@ -959,6 +965,28 @@ class KzgOpener(_Handle):
         ev = _dev_ptr(out_evals_tensor, 32 * self.n) if out_evals_tensor is not None else None
         _chk(lib().zkp_kzg_open_cosets_dev(self._h, _dev_ptr(coeffs_tensor, 32 * length), length, _dev_ptr(out_xy_tensor, 96 * self.cosets),
                                            _dev_ptr(out_inf_tensor, self.cosets), ev, _stream_ptr(stream)))
+
+    def open_cosets_batch(self, coeffs, evals=False):
+        """open_cosets of P <= max_polys polynomials in one call: coeffs (P, len, 4) -> ((P, r, 12) proof points, (P, r) flags),
+        (P, n, 4) evaluations (None without evals); row p is what open_cosets returns for coeffs[p]."""
+        coeffs = _np(coeffs, np.uint64)
+        if coeffs.ndim != 3 or coeffs.shape[2] != 4:
+            raise ValueError("open_cosets_batch takes a (P, len, 4) array of coefficients")
+        polys, length = coeffs.shape[0], coeffs.shape[1]
+        xy = np.zeros((polys, self.cosets, 12), dtype=np.uint64)
+        inf = np.zeros((polys, self.cosets), dtype=np.uint8)
+        ev = np.zeros((polys, self.n, 4), dtype=np.uint64) if evals else None
+        _chk(lib().zkp_kzg_open_cosets_batch(self._h, _ptr(coeffs), polys, length, length, _ptr(xy), _ptr(inf), _ptr(ev)))
+        return (xy, inf), ev
+
+    def open_cosets_batch_dev(self, coeffs_tensor, n_polys, length, stride, out_xy_tensor, out_inf_tensor, out_evals_tensor=None, stream=None):
+        """The same with everything resident on the opener's device: polynomial p at `stride` scalars times p, `length` of them read;
+        nothing is allocated, nothing synchronised."""
+        ev = _dev_ptr(out_evals_tensor, 32 * self.n * n_polys) if out_evals_tensor is not None else None
+        need = 32 * (stride * (n_polys - 1) + length) if n_polys else 0
+        _chk(lib().zkp_kzg_open_cosets_batch_dev(self._h, _dev_ptr(coeffs_tensor, need), n_polys, length, stride,
+                                                 _dev_ptr(out_xy_tensor, 96 * self.cosets * n_polys), _dev_ptr(out_inf_tensor, self.cosets * n_polys),
+                                                 ev, _stream_ptr(stream)))
 
 
 class KzgRecoverer(_Handle):
@@ -1110,6 +1138,17 @@ class KzgScheme:
         if (log_n, log_l) not in self._coset_openers:
             self._coset_openers[log_n, log_l] = KzgOpener(self.srs.bases, log_n, log_l)
         return self._coset_openers[log_n, log_l].open_cosets(coeffs, evals=evals)
+
+    def open_cosets_batch(self, polys, log_n, log_l, evals=False):
+        """open_cosets of every polynomial of `polys` ((P, len, 4)) in one call: KzgOpener.open_cosets_batch (the opener is kept per
+        shape and replaced by a larger one when a batch outgrows it; open_cosets of that shape uses it too)."""
+        polys = _np(polys, np.uint64)
+        kept = self._coset_openers.get((log_n, log_l))
+        if kept is None or kept.max_polys < polys.shape[0]:
+            if kept is not None:
+                kept.close()
+            self._coset_openers[log_n, log_l] = KzgOpener(self.srs.bases, log_n, log_l, max(polys.shape[0], 1))
+        return self._coset_openers[log_n, log_l].open_cosets_batch(polys, evals=evals)
 
     def recover_cosets(self, evals, present, length, log_n, log_l, proofs=False):
         """The polynomial of `length` coefficients behind the present cosets of `evals`: KzgRecoverer.recover with the evaluations (the
