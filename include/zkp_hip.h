@@ -389,6 +389,33 @@ int zkp_kzg_recover_cosets(const zkp_kzg_recoverer *rc, const uint64_t *evals, c
                            uint64_t *out_coeffs, uint64_t *out_evals, int *consistent);
 int zkp_kzg_recover_cosets_dev(const zkp_kzg_recoverer *rc, const void *d_evals, const uint8_t *present, size_t len,
                                void *d_out_coeffs, void *d_out_evals, uint32_t *d_inconsistent, void *stream);
+/* Recovery of a batch: every blob of a block misses the same cosets, so the vanishing polynomial, its values and their inverses
+ * are built once per call and everything behind them -- the masked multiply, the three transforms of n, the divide, the tail -- runs
+ * once over all rows (profiles/kzg_recover_batch.md).
+ * zkp_kzg_recoverer_create_batch makes a handle for up to max_polys (1 .. 4096, else ZKP_E_ARG) polynomials per call;
+ * zkp_kzg_recoverer_create is this creation with max_polys = 1, and every other condition and refusal is the same.  Only the
+ * n-element vector of the workspace grows, to max_polys x n; the refusal of a workspace that does not fit names max_polys too.
+ * A handle of any max_polys serves zkp_kzg_recover_cosets*.
+ * zkp_kzg_recover_cosets_batch: evals n_polys x n x 4 limbs, contiguous rows; ONE mask of r bytes and one len for all rows;
+ * out_coeffs n_polys x len x 4 limbs, out_evals n_polys x n x 4 limbs or NULL, consistent one byte (1 or 0) per row -- a bad row
+ * does not taint its neighbours.  layout applies to evals and out_evals: ZKP_KZG_LAYOUT_NATURAL, value j of coset k at k + j r of
+ * its row as above; ZKP_KZG_LAYOUT_CELLS, at k l + j -- a row is r cells of l contiguous values, what zkp_kzg_verify_cells takes.
+ * The slots of missing cells are not read in either layout; the coefficients do not depend on it.  Row p of every output is byte
+ * for byte what zkp_kzg_recover_cosets returns for row p (in cell layout: its transposition).  Refused before anything is launched:
+ * whatever zkp_kzg_recover_cosets refuses, with the same codes and texts; stride < len and an unknown layout (ZKP_E_ARG);
+ * n_polys > max_polys (ZKP_E_SIZE, both numbers in zkp_last_error()); n_polys == 0 is ZKP_OK without touching the device.
+ * zkp_kzg_recover_cosets_batch_dev: as zkp_kzg_recover_cosets_dev -- `present` is host memory read before the call returns, it
+ * neither allocates nor synchronises.  Row p of d_out_coeffs begins at `stride` scalars times p and the scalars between len and
+ * stride are not written, so that the buffer feeds zkp_kzg_open_cosets_batch_dev with the same stride; d_inconsistent is n_polys
+ * words, each set to 0 or 1 for its own row. */
+#define ZKP_KZG_LAYOUT_NATURAL 0
+#define ZKP_KZG_LAYOUT_CELLS 1
+int zkp_kzg_recoverer_create_batch(unsigned log_n, unsigned log_l, size_t max_polys, zkp_kzg_recoverer **out);
+int zkp_kzg_recover_cosets_batch(const zkp_kzg_recoverer *rc, const uint64_t *evals, size_t n_polys, const uint8_t *present,
+                                 size_t len, int layout, uint64_t *out_coeffs, uint64_t *out_evals, uint8_t *consistent);
+int zkp_kzg_recover_cosets_batch_dev(const zkp_kzg_recoverer *rc, const void *d_evals, size_t n_polys, const uint8_t *present,
+                                     size_t len, size_t stride, int layout, void *d_out_coeffs, void *d_out_evals,
+                                     uint32_t *d_inconsistent, void *stream);
 
 /* ---- batched cell verification: any number of cells of any number of commitments, one pairing check ----
  * n = 2^log_n, l = 2^log_l, r = n / l as above; w the root zkp_ntt_fr uses for log_n.  Cell i < n_cells belongs to the commitment

@@ -185,4 +185,33 @@ impl KzgScheme {
             })
             .collect()
     }
+
+    /// The blobs of a whole block from the cells a node holds: every row of `cells` (r cells of l values each, as they travel on
+    /// the wire; the cells whose `present` byte is 0 are not read) misses the same cosets, so ONE call of
+    /// zkp_kzg_recover_cosets_batch builds the vanishing polynomial once and recovers all rows behind it.  Returns, per row, its
+    /// `len` coefficients, all its r cells (the missing ones filled in) and whether the present cells were those of a polynomial
+    /// of `len` coefficients.  A long-lived node keeps the recoverer instead of making one per call.
+    pub fn recover_cosets_batch(&self, cells: &[Vec<Fr>], present: &[u8], len: usize, log_n: u32, log_l: u32) -> Vec<(Vec<Fr>, Vec<Fr>, bool)> {
+        let (n, r) = (1usize << log_n, 1usize << (log_n - log_l));
+        if cells.is_empty() {
+            return Vec::new();
+        }
+        assert!(present.len() == r && cells.iter().all(|c| c.len() == n));
+        let evals: Vec<Fr> = cells.iter().flatten().copied().collect();
+        let mut rc_handle = core::ptr::null_mut();
+        let rc = unsafe { sys::zkp_kzg_recoverer_create_batch(log_n, log_l, cells.len(), &mut rc_handle) };
+        assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
+        let mut coeffs = vec![Fr::from(0u64); cells.len() * len];
+        let mut filled = vec![Fr::from(0u64); cells.len() * n];
+        let mut consistent = vec![0u8; cells.len()];
+        let rc = unsafe {
+            sys::zkp_kzg_recover_cosets_batch(rc_handle, evals.as_ptr() as *const u64, cells.len(), present.as_ptr(), len, sys::ZKP_KZG_LAYOUT_CELLS,
+                                              coeffs.as_mut_ptr() as *mut u64, filled.as_mut_ptr() as *mut u64, consistent.as_mut_ptr())
+        };
+        unsafe { sys::zkp_kzg_recoverer_destroy(rc_handle) };
+        assert_eq!(rc, sys::ZKP_OK, "{}", sys::last_error());
+        (0..cells.len())
+            .map(|p| (coeffs[p * len..(p + 1) * len].to_vec(), filled[p * n..(p + 1) * n].to_vec(), consistent[p] != 0))
+            .collect()
+    }
 }

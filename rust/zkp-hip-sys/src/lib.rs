@@ -12,6 +12,9 @@ pub const ZKP_E_ARG: i32 = -1;
 pub const ZKP_E_NOMEM: i32 = -2;
 pub const ZKP_E_DEVICE: i32 = -3;
 pub const ZKP_E_SIZE: i32 = -4;
+/// layout of the evaluations of zkp_kzg_recover_cosets_batch*: value j of coset k at k + j r, or at k l + j (cells)
+pub const ZKP_KZG_LAYOUT_NATURAL: i32 = 0;
+pub const ZKP_KZG_LAYOUT_CELLS: i32 = 1;
 
 #[repr(C)] pub struct zkp_bases { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_plonk_prover { _private: [u8; 0] }
@@ -178,6 +181,9 @@ extern "C" {
     pub fn zkp_kzg_recoverer_destroy(rc: *mut zkp_kzg_recoverer);
     pub fn zkp_kzg_recover_cosets(rc: *const zkp_kzg_recoverer, evals: *const u64, present: *const u8, len: usize, out_coeffs: *mut u64, out_evals: *mut u64, consistent: *mut i32) -> i32;
     pub fn zkp_kzg_recover_cosets_dev(rc: *const zkp_kzg_recoverer, d_evals: *const c_void, present: *const u8, len: usize, d_out_coeffs: *mut c_void, d_out_evals: *mut c_void, d_inconsistent: *mut u32, stream: *mut c_void) -> i32;
+    pub fn zkp_kzg_recoverer_create_batch(log_n: u32, log_l: u32, max_polys: usize, out: *mut *mut zkp_kzg_recoverer) -> i32;
+    pub fn zkp_kzg_recover_cosets_batch(rc: *const zkp_kzg_recoverer, evals: *const u64, n_polys: usize, present: *const u8, len: usize, layout: i32, out_coeffs: *mut u64, out_evals: *mut u64, consistent: *mut u8) -> i32;
+    pub fn zkp_kzg_recover_cosets_batch_dev(rc: *const zkp_kzg_recoverer, d_evals: *const c_void, n_polys: usize, present: *const u8, len: usize, stride: usize, layout: i32, d_out_coeffs: *mut c_void, d_out_evals: *mut c_void, d_inconsistent: *mut u32, stream: *mut c_void) -> i32;
     pub fn zkp_kzg_cell_verifier_create(srs: *const zkp_bases, g2_sl_xy: *const u64, log_n: u32, log_l: u32, max_cells: usize, max_commits: usize, out: *mut *mut zkp_kzg_cell_verifier) -> i32;
     pub fn zkp_kzg_cell_verifier_destroy(v: *mut zkp_kzg_cell_verifier);
     pub fn zkp_kzg_verify_cells(v: *const zkp_kzg_cell_verifier, commits_xy: *const u64, commits_is_inf: *const u8, n_commits: usize, n_cells: usize, commit_index: *const u32, coset_index: *const u32, evals: *const u64, proofs_xy: *const u64, proofs_is_inf: *const u8, weights: *const u64, accepted: *mut i32) -> i32;

@@ -1,7 +1,8 @@
 // kzg_recover.hpp -- the kernels of zkp_kzg_recover_cosets* (driver: kzg_recover_host.inc; every launch, index and size:
 // kzg_recover_plan.hpp, whose header comment states the construction).  The transforms are run_ntt<Fr>; what is here is the product
-// tree's leaves and pointwise passes, the masked multiply, the inversion and divide passes and the tail.  Fr elements are Montgomery
-// residues in memory and in LDS.
+// tree's leaves and pointwise passes, the masked multiply, the inversion and divide passes and the tail, and behind them the forms
+// of the multiply, the divide and the tail that take the rows of a batch (zkp_kzg_recover_cosets_batch*) with the transposition
+// between natural order and cell layout.  Fr elements are Montgomery residues in memory and in LDS.
 #pragma once
 #include "ff.hpp"
 #include "fr29.hpp"
@@ -133,6 +134,139 @@ __global__ __launch_bounds__(KZG_RECOVER_THREADS) void recover_tail_kernel(const
         }
     }
     if (__any(nz) && (threadIdx.x & 63) == 0) atomicOr(inconsistent, 1u);
+}
+
+// ---- a batch of `polys` rows of n (zkp_kzg_recover_cosets_batch*) ----
+// The pointwise passes as above with a row index: blockIdx.x covers the n indices, blockIdx.y a group of KZG_RECOVER_ROWS rows, and
+// what depends on the index alone -- present[k], Zs(rho^k), Zs(g rho^k)^-1 -- is loaded once for the rows of the group.
+
+__global__ __launch_bounds__(KZG_RECOVER_THREADS) void recover_mul_batch_kernel(const Fr* __restrict__ evals, const uint8_t* __restrict__ present,
+                                                                                const Fr* __restrict__ zs, uint32_t log_r, uint32_t log_n,
+                                                                                uint32_t polys, Fr* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * KZG_RECOVER_THREADS + threadIdx.x;
+    if (i >> log_n) return;
+    const uint64_t k = i & (((uint64_t)1 << log_r) - 1);
+    const uint32_t p0 = blockIdx.y * KZG_RECOVER_ROWS, p1 = min(p0 + KZG_RECOVER_ROWS, polys);
+    if (!present[k]) {
+        for (uint32_t p = p0; p < p1; p++) out[kzg_recover_offset(KZG_RECOVER_NATURAL, log_n, log_n - log_r, p, i)] = Fr::zero();
+        return;
+    }
+    const Fr z = zs[k];
+#pragma unroll 1
+    for (uint32_t p = p0; p < p1; p++) {
+        const uint64_t at = kzg_recover_offset(KZG_RECOVER_NATURAL, log_n, log_n - log_r, p, i);
+        out[at] = evals[at] * z;
+    }
+}
+
+// One tile of a row between the layouts through LDS: `v` of the lane's element on the side it was read goes in, the value of the
+// lane's element on the other side comes out.  Fr is eight 32-bit limbs; a plane per pair of limbs.
+__device__ __forceinline__ Fr recover_tile_turn(uint64_t (*tile)[KZG_RECOVER_TILE_SLOTS], bool active, const Fr& v, uint32_t slot_in,
+                                                uint32_t slot_out) {
+    static_assert(sizeof(Fr) == 32, "a tile plane holds a quarter of an element");
+    __syncthreads();  // the previous row's reads are done
+    if (active) {
+#pragma unroll
+        for (int w = 0; w < 4; w++) tile[w][slot_in] = (uint64_t)v.l[2 * w] | ((uint64_t)v.l[2 * w + 1] << 32);
+    }
+    __syncthreads();
+    Fr o = Fr::zero();
+    if (active) {
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const uint64_t x = tile[w][slot_out];
+            o.l[2 * w] = (uint32_t)x;
+            o.l[2 * w + 1] = (uint32_t)(x >> 32);
+        }
+    }
+    return o;
+}
+
+// The masked multiply with the evaluations in cell layout (row p: r cells of l contiguous values), transposed on the way: workgroup
+// blockIdx.x takes tile q of the rows of its group, reads it cell side (value times Zs(rho^k), zero for a missing cell, whose bytes
+// are not read) and stores it natural side.  zs == nullptr: the plain transposition (m = 0).
+__global__ __launch_bounds__(KZG_RECOVER_THREADS) void recover_mul_cells_kernel(const Fr* __restrict__ evals, const uint8_t* __restrict__ present,
+                                                                                const Fr* __restrict__ zs, uint32_t log_n, uint32_t log_l,
+                                                                                uint32_t polys, Fr* __restrict__ out) {
+    __shared__ uint64_t tile[4][KZG_RECOVER_TILE_SLOTS];
+    const KzgRecoverTile tl = kzg_recover_tile(log_n, log_l);
+    const uint32_t t = threadIdx.x;
+    const bool active = t < (1u << (tl.tk_log + tl.tj_log));
+    const KzgRecoverTileAt c = kzg_recover_tile_at(log_n, log_l, blockIdx.x, t, true), d = kzg_recover_tile_at(log_n, log_l, blockIdx.x, t, false);
+    const unsigned log_r = log_n - log_l;
+    const bool have = active && (!zs || present[c.k]);
+    Fr z = Fr::one();
+    if (have && zs) z = zs[c.k];
+    const uint32_t p0 = blockIdx.y * KZG_RECOVER_ROWS, p1 = min(p0 + KZG_RECOVER_ROWS, polys);
+#pragma unroll 1
+    for (uint32_t p = p0; p < p1; p++) {
+        Fr v = Fr::zero();
+        if (have) {
+            v = evals[kzg_recover_offset(KZG_RECOVER_CELLS, log_n, log_l, p, c.k + (c.j << log_r))];
+            if (zs) v = v * z;
+        }
+        const Fr o = recover_tile_turn(tile, active, v, c.slot, d.slot);
+        if (active) out[kzg_recover_offset(KZG_RECOVER_NATURAL, log_n, log_l, p, d.k + (d.j << log_r))] = o;
+    }
+}
+
+// KZG_RECOVER_CELLS_OUT: rows in natural order -> the caller's rows in cell layout, the same tiles the other way round
+__global__ __launch_bounds__(KZG_RECOVER_THREADS) void recover_cells_out_kernel(const Fr* __restrict__ in, uint32_t log_n, uint32_t log_l,
+                                                                                uint32_t polys, Fr* __restrict__ out) {
+    __shared__ uint64_t tile[4][KZG_RECOVER_TILE_SLOTS];
+    const KzgRecoverTile tl = kzg_recover_tile(log_n, log_l);
+    const uint32_t t = threadIdx.x;
+    const bool active = t < (1u << (tl.tk_log + tl.tj_log));
+    const KzgRecoverTileAt c = kzg_recover_tile_at(log_n, log_l, blockIdx.x, t, true), d = kzg_recover_tile_at(log_n, log_l, blockIdx.x, t, false);
+    const unsigned log_r = log_n - log_l;
+    const uint32_t p0 = blockIdx.y * KZG_RECOVER_ROWS, p1 = min(p0 + KZG_RECOVER_ROWS, polys);
+#pragma unroll 1
+    for (uint32_t p = p0; p < p1; p++) {
+        Fr v = Fr::zero();
+        if (active) v = in[kzg_recover_offset(KZG_RECOVER_NATURAL, log_n, log_l, p, d.k + (d.j << log_r))];
+        const Fr o = recover_tile_turn(tile, active, v, d.slot, c.slot);
+        if (active) out[kzg_recover_offset(KZG_RECOVER_CELLS, log_n, log_l, p, c.k + (c.j << log_r))] = o;
+    }
+}
+
+__global__ __launch_bounds__(KZG_RECOVER_THREADS) void recover_div_batch_kernel(Fr* __restrict__ a, const Fr* __restrict__ zinv, uint32_t log_r,
+                                                                                uint32_t log_n, uint32_t polys) {
+    const uint64_t i = (uint64_t)blockIdx.x * KZG_RECOVER_THREADS + threadIdx.x;
+    if (i >> log_n) return;
+    const Fr z = zinv[i & (((uint64_t)1 << log_r) - 1)];
+    const uint32_t p0 = blockIdx.y * KZG_RECOVER_ROWS, p1 = min(p0 + KZG_RECOVER_ROWS, polys);
+#pragma unroll 1
+    for (uint32_t p = p0; p < p1; p++) {
+        const uint64_t at = ((uint64_t)p << log_n) + i;
+        a[at] = a[at] * z;
+    }
+}
+
+// The tail of every row: len of the `stride` scalars of row p of out_coeffs (the rest is not written), the zero-padded row of
+// out_padded where asked for (it may be `a` itself: a lane writes only what it has read), and the row's own word (one atomic per
+// wave that saw a non-zero coefficient of that row)
+__global__ __launch_bounds__(KZG_RECOVER_THREADS) void recover_tail_batch_kernel(const Fr* a, uint32_t log_n, uint64_t len, uint64_t stride,
+                                                                                 uint32_t polys, Fr* __restrict__ out_coeffs, Fr* out_padded,
+                                                                                 uint32_t* __restrict__ inconsistent) {
+    const uint64_t i = (uint64_t)blockIdx.x * KZG_RECOVER_THREADS + threadIdx.x;
+    const bool in = !(i >> log_n);
+    const uint32_t p0 = blockIdx.y * KZG_RECOVER_ROWS, p1 = min(p0 + KZG_RECOVER_ROWS, polys);
+#pragma unroll 1
+    for (uint32_t p = p0; p < p1; p++) {
+        bool nz = false;
+        if (in) {
+            const uint64_t at = ((uint64_t)p << log_n) + i;
+            const Fr v = a[at];
+            if (i < len) {
+                out_coeffs[(uint64_t)p * stride + i] = v;
+                if (out_padded && out_padded != a) out_padded[at] = v;
+            } else {
+                nz = !v.is_zero();
+                if (out_padded) out_padded[at] = Fr::zero();
+            }
+        }
+        if (__any(nz) && (threadIdx.x & 63) == 0) atomicOr(inconsistent + p, 1u);
+    }
 }
 
 }  // namespace zkp

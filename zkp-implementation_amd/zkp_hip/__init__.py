@@ -75,6 +75,9 @@ _SIGS = {
     "zkp_kzg_recoverer_destroy": ([_VP], None),
     "zkp_kzg_recover_cosets": ([_VP, _VP, _VP, _SZ, _VP, _VP, C.POINTER(C.c_int)], C.c_int),
     "zkp_kzg_recover_cosets_dev": ([_VP, _VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_recoverer_create_batch": ([C.c_uint, C.c_uint, _SZ, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_recover_cosets_batch": ([_VP, _VP, _SZ, _VP, _SZ, C.c_int, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_recover_cosets_batch_dev": ([_VP, _VP, _SZ, _VP, _SZ, _SZ, C.c_int, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_kzg_cell_verifier_create": ([_VP, _VP, C.c_uint, C.c_uint, _SZ, _SZ, C.POINTER(_VP)], C.c_int),
     "zkp_kzg_cell_verifier_destroy": ([_VP], None),
     "zkp_kzg_verify_cells": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _VP, C.POINTER(C.c_int)], C.c_int),
@@ -990,15 +993,19 @@ class KzgOpener(_Handle):
 
 
 class KzgRecoverer(_Handle):
-    """zkp_kzg_recoverer: the polynomial behind the cells of KzgOpener.open_cosets from any cosets that determine it.  Made on the
-    calling thread's slot; needs no SRS."""
+    """zkp_kzg_recoverer: the polynomial behind the cells of KzgOpener.open_cosets from any cosets that determine it; with
+    max_polys > 1 those of up to max_polys polynomials that miss the same cosets in one call (recover_batch).  Made on the calling
+    thread's slot; needs no SRS."""
     _destroy = "zkp_kzg_recoverer_destroy"
 
-    def __init__(self, log_n, log_l):
-        self.log_n, self.n, self.log_l = log_n, 1 << log_n, log_l
+    def __init__(self, log_n, log_l, max_polys=1):
+        self.log_n, self.n, self.log_l, self.max_polys = log_n, 1 << log_n, log_l, max_polys
         self.cosets = self.n >> log_l
         self._h = C.c_void_p()
-        _chk(lib().zkp_kzg_recoverer_create(log_n, log_l, C.byref(self._h)))
+        if max_polys != 1:
+            _chk(lib().zkp_kzg_recoverer_create_batch(log_n, log_l, max_polys, C.byref(self._h)))
+        else:  # (the same creation with max_polys = 1; called by its own name so that the suite runs both entries)
+            _chk(lib().zkp_kzg_recoverer_create(log_n, log_l, C.byref(self._h)))
 
     def recover(self, evals, present, length, want_evals=False):
         """evals: (n, 4) values in natural order (coset k at k::r; what stands at a missing coset is not read); present: (r,) bytes,
@@ -1019,6 +1026,36 @@ class KzgRecoverer(_Handle):
         _chk(lib().zkp_kzg_recover_cosets_dev(self._h, _dev_ptr(evals_tensor, 32 * self.n), _ptr(present), int(length),
                                               _dev_ptr(out_coeffs_tensor, 32 * int(length)), ev, _dev_ptr(inconsistent_tensor, 4),
                                               _stream_ptr(stream)))
+
+    def recover_batch(self, evals, present, length, want_evals=False, cells=False):
+        """recover of P <= max_polys rows that miss the same cosets in one call: evals (P, n, 4) in natural order, or (P, r, l, 4)
+        with cells=True (row p: r cells of l values, as KzgCellVerifier.verify takes them); present (r,) bytes for all rows ->
+        ((P, length, 4) coefficients, the evaluations on the whole domain in the layout of `evals` or None, (P,) bool consistent);
+        row p is what recover returns for evals[p]."""
+        evals = _np(evals, np.uint64)
+        shape = (self.cosets, self.n // self.cosets, 4) if cells else (self.n, 4)
+        if evals.ndim != len(shape) + 1 or evals.shape[1:] != shape:
+            raise ValueError("recover_batch takes a (P, n, 4) array of evaluations, or (P, r, l, 4) with cells=True")
+        polys = evals.shape[0]
+        present = _np(present, np.uint8, (self.cosets,))
+        coeffs = np.zeros((polys, int(length), 4), dtype=np.uint64)
+        ev = np.zeros((polys,) + shape, dtype=np.uint64) if want_evals else None
+        ok = np.zeros(polys, dtype=np.uint8)
+        _chk(lib().zkp_kzg_recover_cosets_batch(self._h, _ptr(evals), polys, _ptr(present), int(length), 1 if cells else 0, _ptr(coeffs),
+                                                _ptr(ev), _ptr(ok)))
+        return coeffs, ev, ok.astype(bool)
+
+    def recover_batch_dev(self, evals_tensor, n_polys, present, length, stride, out_coeffs_tensor, inconsistent_tensor, out_evals_tensor=None,
+                          cells=False, stream=None):
+        """The same with everything but `present` (host bytes) resident on the recoverer's device: row p of the coefficients at
+        `stride` scalars times p, `length` of them written; inconsistent_tensor: n_polys 32-bit words, each becomes 0 or 1.  `cells`
+        may be a bool or a ZKP_KZG_LAYOUT_* number.  Nothing is allocated, nothing synchronised."""
+        present = _np(present, np.uint8, (self.cosets,))
+        ev = _dev_ptr(out_evals_tensor, 32 * self.n * n_polys) if out_evals_tensor is not None else None
+        need = 32 * (int(stride) * (n_polys - 1) + int(length)) if n_polys else 0
+        _chk(lib().zkp_kzg_recover_cosets_batch_dev(self._h, _dev_ptr(evals_tensor, 32 * self.n * n_polys), n_polys, _ptr(present), int(length),
+                                                    int(stride), int(cells), _dev_ptr(out_coeffs_tensor, need), ev,
+                                                    _dev_ptr(inconsistent_tensor, 4 * n_polys), _stream_ptr(stream)))
 
 
 def _points(p):
@@ -1160,6 +1197,22 @@ class KzgScheme:
         if not proofs:
             return coeffs, ev, ok
         return coeffs, ev, ok, self.open_cosets(coeffs, log_n, log_l)[0]
+
+    def recover_cosets_batch(self, evals, present, length, log_n, log_l, proofs=False, cells=False):
+        """recover_cosets of every row of `evals` ((P, n, 4), or (P, r, l, 4) with cells=True), all missing the cosets of `present`,
+        in one call: KzgRecoverer.recover_batch with the evaluations (the recoverer is kept per shape and replaced by a larger one
+        when a batch outgrows it; recover_cosets of that shape uses it too) -> (coefficients, evaluations, (P,) consistent), and
+        with proofs=True a fourth item, the (points, flags) of open_cosets_batch on the recovered rows."""
+        evals = _np(evals, np.uint64)
+        kept = self._recoverers.get((log_n, log_l))
+        if kept is None or kept.max_polys < evals.shape[0]:
+            if kept is not None:
+                kept.close()
+            self._recoverers[log_n, log_l] = KzgRecoverer(log_n, log_l, max(evals.shape[0], 1))
+        coeffs, ev, ok = self._recoverers[log_n, log_l].recover_batch(evals, present, length, want_evals=True, cells=cells)
+        if not proofs:
+            return coeffs, ev, ok
+        return coeffs, ev, ok, self.open_cosets_batch(coeffs, log_n, log_l)[0]
 
     def verify_cells(self, g2_sl_xy, commitments, commit_index, coset_index, evals, proofs, log_n, log_l, weights=None):
         """Cells of open_cosets, of any of `commitments`, in one pairing check: KzgCellVerifier.verify (the verifier is kept per
