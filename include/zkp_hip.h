@@ -510,6 +510,40 @@ int zkp_selftest_g1_dev(int op, const void *d_a, const void *d_b, size_t n, size
  * d_scalars holds n Fr in memory form (Montgomery, 8 words), d_out receives 8 words per case, k1 = k mod lambda then k2 = k div lambda,
  * canonical, low word first. */
 int zkp_selftest_glv_split_dev(const void *d_scalars, size_t n, void *d_out, void *stream);
+/* Self-test hooks for the polynomial layer under the PLONK prover, zkp_kzg_open and Nova's openings (csrc/plonk.hpp: the three-launch
+ * scan, fr_scale_pow_kernel, the division by (X - z), fr_poly_eval_kernel, fr_lincomb_kernel, fr_trim_len_kernel).  Host code only: each
+ * hook calls the host helper the prover calls (csrc/plonk_host.inc), which launches the kernels the prover launches, on the caller's
+ * buffers and stream; scratch comes from the slot's staging buffer.  Vectors are Fr in memory form (Montgomery, 4 x u64) in device memory,
+ * at most 2^22 elements each (ZKP_E_SIZE beyond); scalars (z, base, s) are host Fr in the same form.  The arrays d_in, d_out, n, ... are
+ * host arrays with one entry per job.  A null pointer that would be read or written, a count or a chunk out of range and an output that
+ * overlaps an input it may not overlap are refused with ZKP_E_ARG before anything is enqueued.  `chunk` = 0 takes the elements per thread
+ * the production rule picks for the longest vector of the call; any other value forces it (the prover never does).  Not part of the hot
+ * path (tests/test_gpu_poly_primitives.py).
+ *   zkp_selftest_poly_scan_dev        count = 1 or 2 jobs of one operator (op 0: +, 1: *): flags[j] bit 0 = from the top index down
+ *                                     (suffix scan), bit 1 = exclusive: d_out[j][i] = op of d_in[j][k] over k <= i (< i when exclusive; >= i,
+ *                                     > i for a suffix scan), the empty operation being 0 or 1.  chunk 1..16.  d_out[j] may be d_in[j];
+ *                                     no other overlap.  (run_scan_batch)
+ *   zkp_selftest_poly_scale_pow_dev   d_out[i] = d_in[i] * base^(i + e0).  chunk 1..8.  d_out may be d_in.  (scale_pow_params and the grid
+ *                                     of the division)
+ *   zkp_selftest_poly_div_linear_dev  count = 1 or 2 requests: d_out[j] receives the len[j] - 1 coefficients of (c_j(X) - c_j(z_j)) / (X - z_j),
+ *                                     q_k = sum_{i > k} c_i z^(i - k - 1); z = count x 4 words.  len <= 1 writes nothing.  chunk 1..8, for the
+ *                                     scaling and the scan alike.  A quotient may not overlap a dividend.  (div_linear_batch_dev)
+ *   zkp_selftest_poly_eval_dev        count <= 8 requests: out (host, count x 4 words) receives c_j(z_j); len 0 gives 0.  Returns after the
+ *                                     stream has finished this work.  (eval_many_dev)
+ *   zkp_selftest_poly_lincomb_dev     d_out[i] = sum_k s_k d_p[k][i] over the terms with i < len[k], i < n_out; terms <= 12, s = terms x 4
+ *                                     words.  d_out may be one of the d_p[k].  (lincomb_dev)
+ *   zkp_selftest_poly_trim_len_dev    *out_len = the highest index of a non-zero element of d_c[0..n) plus one, 0 if there is none.  Returns
+ *                                     after the stream has finished this work.  (the launch of trim_len_dev) */
+int zkp_selftest_poly_scan_dev(int op, size_t count, const void *const *d_in, void *const *d_out, const size_t *n, const unsigned *flags,
+                               unsigned chunk, void *stream);
+int zkp_selftest_poly_scale_pow_dev(const void *d_in, size_t n, const uint64_t base[4], uint64_t e0, unsigned chunk, void *d_out,
+                                    void *stream);
+int zkp_selftest_poly_div_linear_dev(size_t count, const void *const *d_c, const size_t *len, const uint64_t *z, void *const *d_out,
+                                     unsigned chunk, void *stream);
+int zkp_selftest_poly_eval_dev(size_t count, const void *const *d_c, const size_t *len, const uint64_t *z, uint64_t *out, void *stream);
+int zkp_selftest_poly_lincomb_dev(size_t terms, const void *const *d_p, const size_t *len, const uint64_t *s, size_t n_out, void *d_out,
+                                  void *stream);
+int zkp_selftest_poly_trim_len_dev(const void *d_c, size_t n, size_t *out_len, void *stream);
 /* [s^i]G for i < n into host memory (kzg/src/srs.rs:48-63: n = circuit_size + 3). */
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t *out_xy);
 

@@ -198,6 +198,12 @@ extern "C" {
     pub fn zkp_selftest_gl_dev(op: i32, d_in: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_g1_dev(op: i32, d_a: *const c_void, d_b: *const c_void, n: usize, stride: usize, d_out: *mut c_void, d_flag: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_glv_split_dev(d_scalars: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_poly_scan_dev(op: i32, count: usize, d_in: *const *const c_void, d_out: *const *mut c_void, n: *const usize, flags: *const u32, chunk: u32, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_poly_scale_pow_dev(d_in: *const c_void, n: usize, base: *const u64, e0: u64, chunk: u32, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_poly_div_linear_dev(count: usize, d_c: *const *const c_void, len: *const usize, z: *const u64, d_out: *const *mut c_void, chunk: u32, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_poly_eval_dev(count: usize, d_c: *const *const c_void, len: *const usize, z: *const u64, out: *mut u64, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_poly_lincomb_dev(terms: usize, d_p: *const *const c_void, len: *const usize, s: *const u64, n_out: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_poly_trim_len_dev(d_c: *const c_void, n: usize, out_len: *mut usize, stream: *mut c_void) -> i32;
     pub fn zkp_srs_g1(secret: *const u64, n: usize, out_xy: *mut u64) -> i32;
     pub fn zkp_ntt_fr(data: *mut u64, log_n: u32, inverse: i32, coset: *const u64) -> i32;
     pub fn zkp_ntt_fr_dev(d_data: *mut c_void, log_n: u32, batch: usize, inverse: i32, coset: *const u64, stream: *mut c_void) -> i32;

@@ -692,6 +692,31 @@ def test_kzg_open_long_polynomial_device_path(zkp, orc):
     assert np.array_equal(w0, exp0)
 
 
+@pytest.mark.parametrize("n", [4096, 4097, 65537, (1 << 17) + 1])
+def test_kzg_open_device_path_at_its_thresholds(zkp, orc, n):
+    """open() at the first length on the device path (4096) and the one after it, at 257 workgroups per scan (2^16 + 1: two totals per
+    thread in the scan's middle launch) and at the first length above 2^17, where the production rule gives a thread of the scan and of
+    the scaling two elements.  y exactly against Horner in Python integers; W against [(p(s) - y) / (s - z)]G from the SRS secret --
+    one scalar multiplication, since the quotient's commitment is q(s) G."""
+    s_int = 0x1234567 + n
+    srs = zkp.Srs.new_from_secret(orc.fr_from_ints([s_int])[0], n)  # n + 3 points
+    c = orc.rand_fr(0xAB00 + n, n)
+    c[n // 2] = 0
+    c[1] = orc.fr_from_ints([M.R - 1])[0]
+    z = orc.rand_fr(0xCD00 + n, 1)[0]
+    (w, winf), ev = zkp.KzgScheme(srs).open(c, z)
+    ci, z_int = orc.fr_to_ints(c), orc.fr_to_ints(z.reshape(1, 4))[0]
+    assert ci[-1] != 0 and z_int not in (0, s_int)
+    y = ps = 0
+    for x in reversed(ci):
+        y = (y * z_int + x) % M.R
+        ps = (ps * s_int + x) % M.R
+    assert orc.fr_to_ints(ev.reshape(1, 4))[0] == y
+    k = (ps - y) * pow(s_int - z_int, -1, M.R) % M.R
+    exp, einf = orc.g1_mul(orc.g1_generator(), 0, orc.fr_from_ints([k])[0])
+    assert winf == einf == 0 and np.array_equal(w, exp)
+
+
 @pytest.mark.parametrize("wb", [12, 16, 20, 22, 23, 24])
 def test_msm_shared_buckets_with_expanded_bases(zkp, orc, wb):
     """zkp_g1_bases_precompute: all windows of a scalar share one bucket set through pre-multiplied copies of the bases.

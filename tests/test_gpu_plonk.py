@@ -51,8 +51,27 @@ SMALL_CIRCUITS = {"ref": PM.reference_test_circuit,       # plonk/src/verifier.r
                   "pi": PM.public_input_circuit}          # non-zero pi on a mul, an add and a constant gate (gate.rs:38-111)
 
 
+def chain_circuit(m, last_output_off_by=0):
+    """m gates, mul / add alternating, the output of gate i wired to the left input of gate i + 1; last_output_off_by != 0 makes row
+    m - 1 the one row that violates its gate equation (its output is wired nowhere, so every copy constraint still holds)"""
+    c = PM.Circuit()
+    a = 3
+    for i in range(m):
+        b = 7 + 3 * i
+        out = a * b % R if i % 2 == 0 else (a + b) % R
+        if i == m - 1:
+            out = (out + last_output_off_by) % R
+        a_pos = (2, i - 1) if i else (0, 0)
+        c_pos = (0, i + 1) if i < m - 1 else (2, i)
+        (c.add_multiplication_gate if i % 2 == 0 else c.add_addition_gate)((a_pos[0], a_pos[1], a), (1, i, b), (c_pos[0], c_pos[1], out))
+        a = out
+    return c
+
+
+# chain300: n = 512 -- two workgroups in every scan, a quotient domain of 16 workgroups; the polynomials of a circuit larger than one
+# wave, coefficient by coefficient
 @pytest.mark.parametrize("case,seed", [("ref", 1), ("ref", 2), ("chain5", 3), ("chain37", 4), ("ref02", 5), ("ref03", 6), ("pi", 7),
-                                       ("pi", 8)])
+                                       ("pi", 8), ("chain300", 9)])
 def test_plonk_rounds_match_reference_model(zkp, orc, case, seed):
     if case in SMALL_CIRCUITS:
         cc = SMALL_CIRCUITS[case]().compile()
@@ -61,17 +80,8 @@ def test_plonk_rounds_match_reference_model(zkp, orc, case, seed):
         if case == "pi":
             assert any(cc["pi"])
     else:
-        m = int(case[5:])
-        c = PM.Circuit()
-        a = 3
-        for i in range(m):
-            b = 7 + 3 * i
-            out = a * b % R if i % 2 == 0 else (a + b) % R
-            a_pos = (2, i - 1) if i else (0, 0)
-            c_pos = (0, i + 1) if i < m - 1 else (2, i)
-            (c.add_multiplication_gate if i % 2 == 0 else c.add_addition_gate)((a_pos[0], a_pos[1], a), (1, i, b), (c_pos[0], c_pos[1], out))
-            a = out
-        cc = c.compile()
+        cc = chain_circuit(int(case[5:])).compile()
+        assert cc["n"] == 1 << (int(case[5:]) - 1).bit_length()
     blinders, ch = challenges(seed)
     secret = M.rand_fr_list(200 + seed, 1)[0]
     ref = PM.prove(cc, secret, blinders, ch)
@@ -90,9 +100,13 @@ def test_plonk_rounds_match_reference_model(zkp, orc, case, seed):
         check_commit(orc, g, d[k])
 
 
-@pytest.mark.parametrize("what", ["gate_row", "copy_constraint"])
+@pytest.mark.parametrize("what", ["gate_row", "copy_constraint", "gate_row_299"])
 def test_plonk_unsatisfied_circuit_is_rejected(zkp, orc, what):
-    if what == "gate_row":
+    if what == "gate_row_299":
+        # the only violated row lies in the second workgroup of the gate check, and its wave's ballot has a single bit set
+        c = chain_circuit(300, last_output_off_by=1)
+        msg = "expected: 1 gate row(s)"  # the same message as below, and the count it carries
+    elif what == "gate_row":
         c = PM.Circuit()
         c.add_multiplication_gate((1, 0, 3), (0, 0, 3), (0, 3, 9))
         c.add_multiplication_gate((1, 1, 4), (0, 1, 4), (1, 3, 16))

@@ -21,8 +21,10 @@ constexpr int PK_THREADS = 256;
 // workgroup are scanned in place (wave shuffles + four wave totals through LDS): every thread leaves its exclusive prefix inside the
 // workgroup, the workgroup its total; (2) one workgroup per job scans the workgroup totals; (3) apply.  At PLONK's 2^16 elements
 // these kernels are chains of dependent field products over a nearly empty machine, so the host picks the chunk that keeps about
-// 2^16 threads (4 elements per thread there: 5 + 8, ~8, 5 dependent products in the three launches; the first version -- 16 elements
-// per thread, one workgroup of 1024 threads over 4096 totals -- had 16, 18, 16 and took 103 us per scan against ~35 now).
+// 2^16 threads (scan_chunk_for: 1 element per thread up to 2^17 - 1 elements -- at 2^16 that is 256 workgroups and one total per
+// thread in the middle launch -- then n >> 16 elements per thread, at most 16; the first version -- 16 elements per thread, one
+// workgroup of 1024 threads over 4096 totals -- had chains of 16, 18, 16 dependent products in the three launches and took 103 us
+// per scan against ~35 now).
 // -------------------------------------------------------------------------------------------------------------
 struct OpMul {
     static ZKP_DEV Fr id() { return Fr::one(); }
@@ -51,10 +53,11 @@ ZKP_HD uint32_t scan_chunk_for(uint64_t n) {  // about 2^16 threads, 1..16 eleme
     uint64_t c = n >> 16;
     return (uint32_t)(c < 1 ? 1 : c > SCAN_MAX_CHUNK ? SCAN_MAX_CHUNK : c);
 }
-ZKP_HD uint64_t scan_blocks_for(uint64_t n) {
-    const uint64_t threads = (n + scan_chunk_for(n) - 1) / scan_chunk_for(n);
+ZKP_HD uint64_t scan_blocks_for(uint64_t n, uint32_t chunk) {
+    const uint64_t threads = (n + chunk - 1) / chunk;
     return (threads + 255) / 256;
 }
+ZKP_HD uint64_t scan_blocks_for(uint64_t n) { return scan_blocks_for(n, scan_chunk_for(n)); }
 // scratch (tpre + btot of a batch) that covers every scan of at most n elements: below 2^20 elements the chunk rule keeps the thread
 // count under 2^17 (512 workgroups), above it a thread takes 16 elements
 ZKP_HD uint64_t scan_scratch_elems(uint64_t n) {

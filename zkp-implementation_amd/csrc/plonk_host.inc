@@ -119,10 +119,12 @@ int commit_batch_dev(const zkp_plonk_prover* p, const Fr* const* coeffs, size_t 
     return ZKP_OK;
 }
 
-// up to SCAN_MAX_BATCH independent scans with one operator in one set of three launches
+// up to SCAN_MAX_BATCH independent scans with one operator in one set of three launches.  force_chunk: 0 = the elements per thread of
+// scan_chunk_for (every caller but the self-test hooks at the end of this file), else that many (1..SCAN_MAX_CHUNK)
 template <class Op>
-int run_scan_batch(const PlonkScratch& s, const ScanJob* jobs, int count, hipStream_t st) {
+int run_scan_batch(const PlonkScratch& s, const ScanJob* jobs, int count, hipStream_t st, uint32_t force_chunk = 0) {
     if (count < 1 || count > SCAN_MAX_BATCH) return fail(ZKP_E_ARG, "internal: scan batch");
+    if (force_chunk > (uint32_t)SCAN_MAX_CHUNK) return fail(ZKP_E_ARG, "internal: scan chunk");
     ScanParams sp;
     std::memset(&sp, 0, sizeof sp);
     uint64_t nmax = 0;
@@ -131,8 +133,8 @@ int run_scan_batch(const PlonkScratch& s, const ScanJob* jobs, int count, hipStr
         nmax = std::max<uint64_t>(nmax, jobs[j].n);
     }
     if (nmax == 0) return ZKP_OK;
-    sp.chunk = scan_chunk_for(nmax);
-    const uint64_t blocks = scan_blocks_for(nmax);
+    sp.chunk = force_chunk ? force_chunk : scan_chunk_for(nmax);
+    const uint64_t blocks = scan_blocks_for(nmax, sp.chunk);
     if (blocks > (1u << 20) || SCAN_MAX_BATCH * blocks * 257 > s.scan_cap) return fail(ZKP_E_ARG, "internal: scan scratch too small");
     sp.blocks = (uint32_t)blocks;
     sp.tpre = s.scan;
@@ -209,10 +211,15 @@ int eval_dev(const PlonkScratch& s, const Fr* c, uint64_t len, const HFr& z, hip
     return eval_many_dev(s, {EvalReq{c, len, z, out}}, st);
 }
 
+// *d_len = highest index of c[0..n) with a non-zero element, plus one (0: none); n >= 1.  Enqueued on `st`.
+int trim_len_enqueue(const Fr* c, uint64_t n, unsigned long long* d_len, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(d_len, 0, 8, st));
+    hipLaunchKernelGGL(fr_trim_len_kernel, dim3((unsigned)((n + PK_THREADS - 1) / PK_THREADS)), dim3(PK_THREADS), 0, st, c, n, d_len);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+}
 int trim_len_dev(zkp_plonk_prover* p, const Fr* c, uint64_t n, hipStream_t st, uint64_t* len) {
-    HIPCHK(hipMemsetAsync(p->d_len, 0, 8, st));
-    hipLaunchKernelGGL(fr_trim_len_kernel, dim3((unsigned)((n + PK_THREADS - 1) / PK_THREADS)), dim3(PK_THREADS), 0, st, c, n,
-                       p->d_len);
+    ZCHK(trim_len_enqueue(c, n, p->d_len, st));
     HIPCHK(hipMemcpyAsync(p->h_pin, p->d_len, 8, hipMemcpyDeviceToHost, st));
     ZCHK(wait_stream(p->scratch(), st));
     *len = p->h_pin[0];
@@ -230,11 +237,19 @@ ScalePowParams scale_pow_params(const HFr& base, uint64_t e0, uint32_t chunk) {
     }
     return sp;
 }
+// elements per thread of fr_scale_pow_kernel over at most n elements (about 2^16 threads) and the grid of `jobs` jobs
+constexpr uint32_t SCALE_MAX_CHUNK = 8;
+uint32_t scale_chunk_for(uint64_t n) { return (uint32_t)std::min<uint64_t>(SCALE_MAX_CHUNK, std::max<uint64_t>(1, n >> 16)); }
+dim3 scale_pow_grid(uint64_t nmax, uint32_t chunk, int jobs) {
+    return dim3((unsigned)(((nmax + chunk - 1) / chunk + PK_THREADS - 1) / PK_THREADS), (unsigned)jobs);
+}
 
 // q = (c(X) - c(z)) / (X - z): len - 1 coefficients into `out` (may not alias c), one or two divisions per set of launches (the two
-// opening quotients of round 5 are independent); uses ev[] as scratch (2 len elements per division)
+// opening quotients of round 5 are independent); uses ev[] as scratch (2 len elements per division).  force_chunk: 0 = the elements
+// per thread of scale_chunk_for and scan_chunk_for, else that many in both steps (1..SCALE_MAX_CHUNK; the self-test hooks only)
 struct DivReq { const Fr* c; uint64_t len; HFr z; Fr* out; };
-int div_linear_batch_dev(const PlonkScratch& s, const DivReq* reqs, int count, hipStream_t st) {
+int div_linear_batch_dev(const PlonkScratch& s, const DivReq* reqs, int count, hipStream_t st, uint32_t force_chunk = 0) {
+    if (force_chunk > SCALE_MAX_CHUNK) return fail(ZKP_E_ARG, "internal: scale chunk");
     DivReq rq[2];
     int m = 0;
     for (int i = 0; i < count; i++) {
@@ -249,7 +264,7 @@ int div_linear_batch_dev(const PlonkScratch& s, const DivReq* reqs, int count, h
     if (!m) return ZKP_OK;
     uint64_t nmax = 0;
     for (int i = 0; i < m; i++) nmax = std::max(nmax, rq[i].len);
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(1, nmax >> 16));  // about 2^16 threads
+    const uint32_t chunk = force_chunk ? force_chunk : scale_chunk_for(nmax);
     HFr zinv[2];
     if (m == 2) {  // both inverses from one inversion
         const HFr pi = (rq[0].z * rq[1].z).inverse();
@@ -274,9 +289,9 @@ int div_linear_batch_dev(const PlonkScratch& s, const DivReq* reqs, int count, h
         back.sp[i] = scale_pow_params(zinv[i], 1, chunk);
     }
     fwd.chunk = back.chunk = chunk;
-    const dim3 grid((unsigned)(((nmax + chunk - 1) / chunk + PK_THREADS - 1) / PK_THREADS), (unsigned)m);
+    const dim3 grid = scale_pow_grid(nmax, chunk, m);
     hipLaunchKernelGGL(fr_scale_pow_kernel, grid, dim3(PK_THREADS), 0, st, fwd);
-    ZCHK(run_scan_batch<OpAdd>(s, sj, m, st));
+    ZCHK(run_scan_batch<OpAdd>(s, sj, m, st, force_chunk));
     hipLaunchKernelGGL(fr_scale_pow_kernel, grid, dim3(PK_THREADS), 0, st, back);
     HIPCHK(hipGetLastError());
     return ZKP_OK;
@@ -904,3 +919,170 @@ extern "C" int zkp_plonk_prove(zkp_plonk_prover* p, const uint64_t* blinders /* 
     ch.generate(1, out->u);
     return ZKP_OK;
 } ZKP_CATCH_INT
+
+// ---- self-test hooks of the polynomial helpers above (include/zkp_hip.h: zkp_selftest_poly_*_dev) ---------------
+// Host code only: every hook checks its arguments, carves the helper's scratch from the slot's staging buffer (as kzg_open_device does)
+// and calls the helper the prover calls, which launches the kernels the prover launches.  tests/test_gpu_poly_primitives.py.
+namespace {
+
+constexpr uint64_t POLY_SELFTEST_MAX = 1ull << 22;  // elements per vector: the scratch of two scans at one element per thread stays near 0.5 GB
+
+// [a, a + na) and [b, b + nb) (32-byte elements) share a byte; the same start is accepted where `same_ok` (a kernel that reads
+// element i and writes element i in one thread works in place)
+bool fr_ranges_clash(const void* a, uint64_t na, const void* b, uint64_t nb, bool same_ok) {
+    if (!na || !nb || !a || !b) return false;
+    if (a == b) return !same_ok;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + 32 * nb && b0 < a0 + 32 * na;
+}
+int poly_selftest_scratch(uint64_t elems, Fr** out) {
+    ZCHK(ctx().tmp.ensure(32 * elems + 64));
+    *out = reinterpret_cast<Fr*>(ctx().tmp.p);
+    return ZKP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkp_selftest_poly_scan_dev(int op, size_t count, const void* const* d_in, void* const* d_out, const size_t* n, const unsigned* flags,
+                               unsigned chunk, void* stream) try {
+    if (!d_in || !d_out || !n || !flags) return fail(ZKP_E_ARG, "null argument");
+    if (op != 0 && op != 1) return fail(ZKP_E_ARG, "op must be 0 (add) or 1 (mul)");
+    if (count < 1 || count > (size_t)SCAN_MAX_BATCH) return fail(ZKP_E_ARG, "a scan launch takes one or two jobs");
+    if (chunk > (unsigned)SCAN_MAX_CHUNK) return fail(ZKP_E_ARG, "chunk must be 0 (the production rule) or 1..16 elements per thread");
+    ScanJob jobs[SCAN_MAX_BATCH];
+    uint64_t nmax = 0;
+    for (size_t j = 0; j < count; j++) {
+        if (n[j] && (!d_in[j] || !d_out[j])) return fail(ZKP_E_ARG, "null argument");
+        if (flags[j] > 3) return fail(ZKP_E_ARG, "flags: bit 0 = suffix scan, bit 1 = exclusive");
+        if (n[j] > POLY_SELFTEST_MAX) return fail(ZKP_E_SIZE, "a polynomial self-test takes at most 2^22 elements per vector");
+        jobs[j] = ScanJob{reinterpret_cast<const Fr*>(d_in[j]), reinterpret_cast<Fr*>(d_out[j]), n[j], flags[j] & 1u, (flags[j] >> 1) & 1u};
+        nmax = std::max<uint64_t>(nmax, n[j]);
+    }
+    for (size_t j = 0; j < count; j++)
+        for (size_t k = 0; k < count; k++)
+            if (fr_ranges_clash(d_out[j], n[j], d_in[k], n[k], j == k) || (k != j && fr_ranges_clash(d_out[j], n[j], d_out[k], n[k], false)))
+                return fail(ZKP_E_ARG, "a scan's output overlaps another vector of the launch (in place is d_out == d_in of the same job)");
+    CTX_ENTER(-1);
+    if (!nmax) return ZKP_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    // the rule's own bound where the rule picks the chunk, what the forced chunk needs otherwise
+    const uint64_t cap = chunk ? SCAN_MAX_BATCH * scan_blocks_for(nmax, chunk) * 257 : scan_scratch_elems(nmax);
+    Fr* scratch = nullptr;
+    ZCHK(poly_selftest_scratch(cap, &scratch));
+    const PlonkScratch w{nullptr, scratch, cap, nullptr, 0, nullptr, nullptr};
+    return op ? run_scan_batch<OpMul>(w, jobs, (int)count, st, chunk) : run_scan_batch<OpAdd>(w, jobs, (int)count, st, chunk);
+} ZKP_CATCH_INT
+
+int zkp_selftest_poly_scale_pow_dev(const void* d_in, size_t n, const uint64_t base[4], uint64_t e0, unsigned chunk, void* d_out,
+                                    void* stream) try {
+    if (!base || (n && (!d_in || !d_out))) return fail(ZKP_E_ARG, "null argument");
+    if (chunk > SCALE_MAX_CHUNK) return fail(ZKP_E_ARG, "chunk must be 0 (the production rule) or 1..8 elements per thread");
+    if (n > POLY_SELFTEST_MAX) return fail(ZKP_E_SIZE, "a polynomial self-test takes at most 2^22 elements per vector");
+    if (fr_ranges_clash(d_out, n, d_in, n, true)) return fail(ZKP_E_ARG, "d_out overlaps d_in (in place is d_out == d_in)");
+    CTX_ENTER(-1);
+    if (!n) return ZKP_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ScalePowBatch b;
+    std::memset(&b, 0, sizeof b);
+    b.chunk = chunk ? chunk : scale_chunk_for(n);
+    b.job[0] = ScalePowJob{reinterpret_cast<const Fr*>(d_in), reinterpret_cast<Fr*>(d_out), n};
+    b.sp[0] = scale_pow_params(HFr::load(base), e0, b.chunk);
+    hipLaunchKernelGGL(fr_scale_pow_kernel, scale_pow_grid(n, b.chunk, 1), dim3(PK_THREADS), 0, st, b);
+    HIPCHK(hipGetLastError());
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_selftest_poly_div_linear_dev(size_t count, const void* const* d_c, const size_t* len, const uint64_t* z, void* const* d_out,
+                                     unsigned chunk, void* stream) try {
+    if (!d_c || !len || !z || !d_out) return fail(ZKP_E_ARG, "null argument");
+    if (count < 1 || count > 2) return fail(ZKP_E_ARG, "a division launch takes one or two requests");
+    if (chunk > SCALE_MAX_CHUNK) return fail(ZKP_E_ARG, "chunk must be 0 (the production rule) or 1..8 elements per thread");
+    DivReq rq[2];
+    uint64_t ev_elems = 0, nmax = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (len[i] > 1 && (!d_c[i] || !d_out[i])) return fail(ZKP_E_ARG, "null argument");
+        if (len[i] > POLY_SELFTEST_MAX) return fail(ZKP_E_SIZE, "a polynomial self-test takes at most 2^22 elements per vector");
+        rq[i] = DivReq{reinterpret_cast<const Fr*>(d_c[i]), len[i], HFr::load(z + 4 * i), reinterpret_cast<Fr*>(d_out[i])};
+        ev_elems += 2 * (uint64_t)len[i];
+        nmax = std::max<uint64_t>(nmax, len[i]);
+    }
+    for (size_t i = 0; i < count; i++)
+        for (size_t k = 0; k < count; k++)
+            if (len[i] > 1 && (fr_ranges_clash(d_out[i], len[i] - 1, d_c[k], len[k], false) ||
+                               (k != i && len[k] > 1 && fr_ranges_clash(d_out[i], len[i] - 1, d_out[k], len[k] - 1, false))))
+                return fail(ZKP_E_ARG, "a quotient may not overlap a dividend or the other quotient");
+    CTX_ENTER(-1);
+    if (nmax <= 1) return ZKP_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    const uint64_t cap = chunk ? SCAN_MAX_BATCH * scan_blocks_for(nmax, chunk) * 257 : scan_scratch_elems(nmax);
+    Fr* scratch = nullptr;
+    ZCHK(poly_selftest_scratch(ev_elems + cap, &scratch));
+    const PlonkScratch w{scratch, scratch + ev_elems, cap, nullptr, 0, nullptr, nullptr};
+    return div_linear_batch_dev(w, rq, (int)count, st, chunk);
+} ZKP_CATCH_INT
+
+int zkp_selftest_poly_eval_dev(size_t count, const void* const* d_c, const size_t* len, const uint64_t* z, uint64_t* out, void* stream) try {
+    if (count && (!d_c || !len || !z || !out)) return fail(ZKP_E_ARG, "null argument");
+    if (count > (size_t)EVAL_MAX_REQ) return fail(ZKP_E_ARG, "an evaluation launch takes at most 8 requests");
+    std::vector<EvalReq> reqs(count);
+    std::vector<HFr> y(count);
+    uint64_t partials = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (len[i] && !d_c[i]) return fail(ZKP_E_ARG, "null argument");
+        if (len[i] > POLY_SELFTEST_MAX) return fail(ZKP_E_SIZE, "a polynomial self-test takes at most 2^22 elements per vector");
+        reqs[i] = EvalReq{reinterpret_cast<const Fr*>(d_c[i]), len[i], HFr::load(z + 4 * i), &y[i]};
+        partials += (len[i] + EVAL_CHUNK * PK_THREADS - 1) / (EVAL_CHUNK * PK_THREADS);
+    }
+    CTX_ENTER(-1);
+    if (!count) return ZKP_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    Fr* scratch = nullptr;
+    ZCHK(poly_selftest_scratch(partials + 1, &scratch));
+    const PlonkScratch w{nullptr, nullptr, 0, scratch, (unsigned)partials, nullptr, nullptr};
+    ZCHK(eval_many_dev(w, reqs, st));
+    for (size_t i = 0; i < count; i++) y[i].store(out + 4 * i);
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_selftest_poly_lincomb_dev(size_t terms, const void* const* d_p, const size_t* len, const uint64_t* s, size_t n_out, void* d_out,
+                                  void* stream) try {
+    if ((terms && (!d_p || !len || !s)) || (n_out && !d_out)) return fail(ZKP_E_ARG, "null argument");
+    if (terms > (size_t)LINCOMB_MAX) return fail(ZKP_E_ARG, "a linear combination takes at most 12 terms");
+    if (n_out > POLY_SELFTEST_MAX) return fail(ZKP_E_SIZE, "a polynomial self-test takes at most 2^22 elements per vector");
+    std::vector<LcTerm> t(terms);
+    for (size_t k = 0; k < terms; k++) {
+        if (len[k] && !d_p[k]) return fail(ZKP_E_ARG, "null argument");
+        if (len[k] > POLY_SELFTEST_MAX) return fail(ZKP_E_SIZE, "a polynomial self-test takes at most 2^22 elements per vector");
+        if (fr_ranges_clash(d_out, n_out, d_p[k], len[k], true)) return fail(ZKP_E_ARG, "d_out overlaps a term (in place is d_out == d_p[k])");
+        t[k] = LcTerm{reinterpret_cast<const Fr*>(d_p[k]), len[k], HFr::load(s + 4 * k)};
+    }
+    CTX_ENTER(-1);
+    if (!n_out) return ZKP_OK;
+    return lincomb_dev(t, reinterpret_cast<Fr*>(d_out), n_out, reinterpret_cast<hipStream_t>(stream));
+} ZKP_CATCH_INT
+
+int zkp_selftest_poly_trim_len_dev(const void* d_c, size_t n, size_t* out_len, void* stream) try {
+    if (!out_len || (n && !d_c)) return fail(ZKP_E_ARG, "null argument");
+    if (n > POLY_SELFTEST_MAX) return fail(ZKP_E_SIZE, "a polynomial self-test takes at most 2^22 elements per vector");
+    CTX_ENTER(-1);
+    *out_len = 0;
+    if (!n) return ZKP_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    Fr* scratch = nullptr;
+    ZCHK(poly_selftest_scratch(1, &scratch));
+    unsigned long long* d_len = reinterpret_cast<unsigned long long*>(scratch);
+    ZCHK(trim_len_enqueue(reinterpret_cast<const Fr*>(d_c), n, d_len, st));
+    unsigned long long h = 0;
+    HIPCHK(hipMemcpyAsync(&h, d_len, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *out_len = (size_t)h;
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+}  // extern "C"

@@ -102,6 +102,12 @@ _SIGS = {
     "zkp_selftest_gl_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_g1_dev": ([C.c_int, _VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_selftest_glv_split_dev": ([_VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_selftest_poly_scan_dev": ([C.c_int, _SZ, _VP, _VP, _VP, _VP, C.c_uint, _VP], C.c_int),
+    "zkp_selftest_poly_scale_pow_dev": ([_VP, _SZ, _VP, C.c_uint64, C.c_uint, _VP, _VP], C.c_int),
+    "zkp_selftest_poly_div_linear_dev": ([_SZ, _VP, _VP, _VP, _VP, C.c_uint, _VP], C.c_int),
+    "zkp_selftest_poly_eval_dev": ([_SZ, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_selftest_poly_lincomb_dev": ([_SZ, _VP, _VP, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_selftest_poly_trim_len_dev": ([_VP, _SZ, C.POINTER(_SZ), _VP], C.c_int),
     "zkp_srs_g1": ([_VP, _SZ, _VP], C.c_int),
     "zkp_ntt_fr": ([_VP, C.c_uint, C.c_int, _VP], C.c_int),
     "zkp_ntt_fr_dev": ([_VP, C.c_uint, _SZ, C.c_int, _VP, _VP], C.c_int),
@@ -513,6 +519,63 @@ def selftest_g1_dev(op, a_tensor, b_tensor, n, stride, out_tensor, flag_tensor, 
     pts = 256 * (stride if SELFTEST_OPS["g1"][op] >= 7 else n)
     _chk(lib().zkp_selftest_g1_dev(SELFTEST_OPS["g1"][op], _dev_ptr(a_tensor, pts) if a_tensor is not None else None, _dev_ptr(b_tensor, pts),
                                    n, stride, _dev_ptr(out_tensor, pts), _dev_ptr(flag_tensor, 4 * n), _stream_ptr(stream)))
+
+
+# ---- self-test hooks of the polynomial layer (zkp_selftest_poly_*_dev): tensors hold Fr in memory form, 32 B per element; a tensor given
+# as None is passed as a null pointer (the library refuses it)
+def _fr_ptrs(tensors, lens):
+    return (C.c_void_p * max(len(tensors), 1))(*[None if t is None else _dev_ptr(t, 32 * int(n)).value for t, n in zip(tensors, lens)])
+
+
+def _sizes(lens):
+    return (C.c_size_t * max(len(lens), 1))(*[int(n) for n in lens])
+
+
+def selftest_poly_scan_dev(op, jobs, chunk=0, stream=None):
+    """zkp_selftest_poly_scan_dev: op "add" or "mul"; jobs = one or two (in_tensor, out_tensor, n, rev, excl); chunk 0 = the production rule."""
+    lens = [j[2] for j in jobs]
+    flags = (C.c_uint * max(len(jobs), 1))(*[int(bool(j[3])) | int(bool(j[4])) << 1 for j in jobs])
+    _chk(lib().zkp_selftest_poly_scan_dev({"add": 0, "mul": 1}[op], len(jobs), _fr_ptrs([j[0] for j in jobs], lens),
+                                          _fr_ptrs([j[1] for j in jobs], lens), _sizes(lens), flags, chunk, _stream_ptr(stream)))
+
+
+def selftest_poly_scale_pow_dev(in_tensor, n, base, e0, out_tensor, chunk=0, stream=None):
+    """zkp_selftest_poly_scale_pow_dev: out[i] = in[i] * base^(i + e0); base = 4 Montgomery limbs."""
+    _chk(lib().zkp_selftest_poly_scale_pow_dev(_fr_ptrs([in_tensor], [n])[0], n, _ptr(_np(base, np.uint64, (4,))), e0, chunk,
+                                               _fr_ptrs([out_tensor], [n])[0], _stream_ptr(stream)))
+
+
+def selftest_poly_div_linear_dev(reqs, chunk=0, stream=None):
+    """zkp_selftest_poly_div_linear_dev: reqs = one or two (c_tensor, len, z, out_tensor); out receives the len - 1 coefficients of
+    (c(X) - c(z)) / (X - z)."""
+    lens = [r[1] for r in reqs]
+    z = _np([r[2] for r in reqs], np.uint64, (-1, 4)) if reqs else np.zeros((1, 4), dtype=np.uint64)
+    _chk(lib().zkp_selftest_poly_div_linear_dev(len(reqs), _fr_ptrs([r[0] for r in reqs], lens), _sizes(lens), _ptr(z),
+                                                _fr_ptrs([r[3] for r in reqs], [max(n, 1) - 1 for n in lens]), chunk, _stream_ptr(stream)))
+
+
+def selftest_poly_eval_dev(reqs, stream=None):
+    """zkp_selftest_poly_eval_dev: reqs = up to eight (c_tensor, len, z) -> (len(reqs), 4) array of c(z)."""
+    lens = [r[1] for r in reqs]
+    z = _np([r[2] for r in reqs], np.uint64, (-1, 4)) if reqs else np.zeros((1, 4), dtype=np.uint64)
+    out = np.zeros((max(len(reqs), 1), 4), dtype=np.uint64)
+    _chk(lib().zkp_selftest_poly_eval_dev(len(reqs), _fr_ptrs([r[0] for r in reqs], lens), _sizes(lens), _ptr(z), _ptr(out), _stream_ptr(stream)))
+    return out[:len(reqs)]
+
+
+def selftest_poly_lincomb_dev(terms, n_out, out_tensor, stream=None):
+    """zkp_selftest_poly_lincomb_dev: terms = up to twelve (p_tensor, len, s); out[i] = sum_k s_k p_k[i] over the terms with i < len_k."""
+    lens = [t[1] for t in terms]
+    s = _np([t[2] for t in terms], np.uint64, (-1, 4)) if terms else np.zeros((1, 4), dtype=np.uint64)
+    _chk(lib().zkp_selftest_poly_lincomb_dev(len(terms), _fr_ptrs([t[0] for t in terms], lens), _sizes(lens), _ptr(s), n_out,
+                                             _fr_ptrs([out_tensor], [n_out])[0], _stream_ptr(stream)))
+
+
+def selftest_poly_trim_len_dev(c_tensor, n, stream=None):
+    """zkp_selftest_poly_trim_len_dev: the highest index of a non-zero element of c[0..n), plus one; 0 for none."""
+    out = C.c_size_t(0)
+    _chk(lib().zkp_selftest_poly_trim_len_dev(_fr_ptrs([c_tensor], [n])[0], n, C.byref(out), _stream_ptr(stream)))
+    return int(out.value)
 
 
 def msm_g1_dev(bases, scalars_tensor, n, stream=None):
