@@ -206,6 +206,54 @@ int zkp_g1_bases_validate(const zkp_bases *b, uint8_t *status, zkp_g1_validation
  * n above the handle's length: ZKP_E_SIZE; n == 1 checks P_0 only. */
 int zkp_srs_check(const zkp_bases *srs, const uint64_t g2s_xy[24], size_t n, const uint64_t *r, int *accepted);
 
+/* ---- Compressed G1 points and scalars as bytes, decoded and encoded on the GPU (csrc/g1_codec.hpp).  A ceremony SRS, a commitment
+ *      and a cell proof travel as 48-byte points: bits 7, 6 and 5 of byte 0 are the flags c (compressed, must be 1), i (infinity) and
+ *      s (y is the larger of {y, p - y} as canonical integers: y > (p - 1) / 2), the remaining 381 bits are the canonical x, big-endian;
+ *      infinity is c0 followed by 47 zero bytes.  This is what ark-bls12-381 0.4 serialize_compressed writes.  Decoding costs one
+ *      square root per point, y = (x^3 + 4)^((p + 1) / 4), one lane per point.  It is strict; per point, in this order, the first
+ *      failure being the point's status:
+ *        4 malformed         c = 0, or i = 1 with s = 1 or any other bit set
+ *        1 non-canonical     x >= p
+ *        2 off the curve     x^3 + 4 is not a square
+ *        3 outside G1        only with ZKP_G1_DECODE_SUBGROUP in `flags` (the test of zkp_g1_validate, a second launch over the decoded points)
+ *      and 0 for a valid point, a well-formed infinity included.  A point with status != 0 is written as twelve zero limbs with
+ *      is_inf = 0 -- (0, 0) is off the curve, so whoever ignores the report cannot carry it further unnoticed.
+ *      A bad point is a finding, not an error: the decompress entries return ZKP_OK with the report filled.  ZKP_E_ARG is for a null
+ *      required argument, an unknown bit in `flags`, and a device pointer to bytes or limbs that is not 16-byte aligned.  n == 0 is
+ *      ZKP_OK with an all-zero report, before the device is touched.  Encoding does not validate: limbs that are no point give bytes
+ *      that are no encoding, never a fault. ---- */
+#define ZKP_G1_DECODE_SUBGROUP 1u
+typedef struct {
+    uint64_t checked, bad;                                          /* points looked at, points with status != 0 */
+    uint64_t malformed, non_canonical, off_curve, outside_subgroup; /* sums to bad */
+    uint64_t first_bad;                                             /* lowest bad index, or n when bad == 0 */
+    int first_status;                                               /* its status, or 0 */
+} zkp_g1_decoding;
+/* n x 48 bytes in device memory -> n x 12 limbs and n infinity bytes in device memory (the slot is chosen from d_bytes as in
+ * zkp_g1_validate_dev); d_status: n bytes of device memory, or NULL.  Synchronises `stream` before it returns. */
+int zkp_g1_decompress_dev(const void *d_bytes, size_t n, unsigned flags, void *d_out_xy, uint8_t *d_out_is_inf, uint8_t *d_status,
+                          void *stream, zkp_g1_decoding *out);
+/* The same from and to host memory, uploaded in pieces of 2^18 points; indices in the report are global.  `status` may be NULL.  Runs
+ * on the thread's zkp_set_device() slot, or slot 0. */
+int zkp_g1_decompress(const uint8_t *bytes, size_t n, unsigned flags, uint64_t *out_xy, uint8_t *out_is_inf, uint8_t *status,
+                      zkp_g1_decoding *out);
+/* n x 12 limbs (d_is_inf may be NULL: every point finite) -> n x 48 bytes, all in device memory.  Does not synchronise. */
+int zkp_g1_compress_dev(const void *d_xy, const uint8_t *d_is_inf, size_t n, void *d_out_bytes, void *stream);
+/* The same from and to host memory, on the thread's zkp_set_device() slot or slot 0. */
+int zkp_g1_compress(const uint64_t *xy, const uint8_t *is_inf, size_t n, uint8_t *out_bytes);
+/* zkp_g1_bases_create from n x 48 bytes of host memory: decoded on the calling thread's slot (zkp_set_device; slot 0 by default) into
+ * device memory that goes straight to the path of zkp_g1_bases_create_dev -- the 96-byte points never visit the host.  IT NEVER
+ * SHARDS: with several slots the handle lives on that one slot.  Any bad point is ZKP_E_ARG with no handle left, the report
+ * (nullable) filled, and zkp_last_error() naming the lowest bad index and one of the words "encoding", "canonical", "curve",
+ * "subgroup". */
+int zkp_g1_bases_create_compressed(const uint8_t *bytes, size_t n, unsigned flags, zkp_g1_decoding *report, zkp_bases **out);
+/* Scalars: n x 32 bytes holding canonical integers below r, big-endian (big_endian != 0: Ethereum's KZG convention) or little-endian
+ * (ark's serialize of Fr), <-> n x 4 limbs in the Fr memory form, all in device memory (16-byte aligned).  A value >= r is counted in
+ * *bad and its slot zeroed; *first_bad (nullable) = the lowest such index, or n.  zkp_fr_from_bytes_dev synchronises `stream`,
+ * zkp_fr_to_bytes_dev does not. */
+int zkp_fr_from_bytes_dev(const void *d_bytes, size_t n, int big_endian, void *d_out, void *stream, uint64_t *bad, uint64_t *first_bad);
+int zkp_fr_to_bytes_dev(const void *d_in, size_t n, int big_endian, void *d_out_bytes, void *stream);
+
 /* ---- MSM: replaces the body of KzgScheme::evaluate_in_s, kzg/src/scheme.rs:84-96 (reached from commit :49,
  *      commit_vector :63, open :108, open_vector :132 and the 9 commit sites of plonk/src/prover.rs:92,123,150,
  *      267-268).  out = sum_{i<n} scalars[i] * bases[i]; n == 0 gives the identity (scheme.rs:94).

@@ -48,6 +48,22 @@ pub struct zkp_g1_validation {
     pub first_status: i32, // its status, or 0
 }
 
+/// ZKP_G1_DECODE_SUBGROUP: run the subgroup test of zkp_g1_validate while decoding
+pub const ZKP_G1_DECODE_SUBGROUP: u32 = 1;
+
+/// report of zkp_g1_decompress* / zkp_g1_bases_create_compressed; status of a point: as zkp_g1_validation, and 4 malformed encoding
+#[repr(C)]
+pub struct zkp_g1_decoding {
+    pub checked: u64,
+    pub bad: u64,
+    pub malformed: u64,
+    pub non_canonical: u64,
+    pub off_curve: u64,
+    pub outside_subgroup: u64,
+    pub first_bad: u64,    // lowest bad index, or n when bad == 0
+    pub first_status: i32, // its status, or 0
+}
+
 /// struct Proof of plonk/src/prover.rs:23-41 in ABI form
 #[repr(C)]
 pub struct zkp_plonk_proof {
@@ -150,6 +166,13 @@ extern "C" {
     pub fn zkp_g1_validate(xy: *const u64, is_inf: *const u8, n: usize, status: *mut u8, out: *mut zkp_g1_validation) -> i32;
     pub fn zkp_g1_bases_validate(b: *const zkp_bases, status: *mut u8, out: *mut zkp_g1_validation) -> i32;
     pub fn zkp_srs_check(srs: *const zkp_bases, g2s_xy: *const u64, n: usize, r: *const u64, accepted: *mut i32) -> i32;
+    pub fn zkp_g1_decompress_dev(d_bytes: *const c_void, n: usize, flags: u32, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, d_status: *mut u8, stream: *mut c_void, out: *mut zkp_g1_decoding) -> i32;
+    pub fn zkp_g1_decompress(bytes: *const u8, n: usize, flags: u32, out_xy: *mut u64, out_is_inf: *mut u8, status: *mut u8, out: *mut zkp_g1_decoding) -> i32;
+    pub fn zkp_g1_compress_dev(d_xy: *const c_void, d_is_inf: *const u8, n: usize, d_out_bytes: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_g1_compress(xy: *const u64, is_inf: *const u8, n: usize, out_bytes: *mut u8) -> i32;
+    pub fn zkp_g1_bases_create_compressed(bytes: *const u8, n: usize, flags: u32, report: *mut zkp_g1_decoding, out: *mut *mut zkp_bases) -> i32;
+    pub fn zkp_fr_from_bytes_dev(d_bytes: *const c_void, n: usize, big_endian: i32, d_out: *mut c_void, stream: *mut c_void, bad: *mut u64, first_bad: *mut u64) -> i32;
+    pub fn zkp_fr_to_bytes_dev(d_in: *const c_void, n: usize, big_endian: i32, d_out_bytes: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_msm_g1(bases: *const zkp_bases, scalars: *const u64, n: usize, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_msm_g1_dev(bases: *const zkp_bases, d_scalars: *const c_void, n: usize, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_msm_g1_batch_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;

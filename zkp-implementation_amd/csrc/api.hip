@@ -29,6 +29,7 @@
 #include "g1_check.hpp"
 #include "ntt.hpp"
 #include "g1_ntt.hpp"
+#include "g1_codec.hpp"
 #include "kzg_recover.hpp"
 #include "kzg_cells.hpp"
 #include "plonk.hpp"
@@ -1411,6 +1412,7 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "fri_host.inc"
 #include "verify_host.inc"
 #include "g1_check_host.inc"
+#include "g1_codec_host.inc"
 #include "kzg_handle.inc"
 #include "g1_ntt_host.inc"
 #include "kzg_recover_host.inc"

@@ -43,9 +43,8 @@ ZKP_DEV S30 s30_canonical(const Fq28& a) {
     return g;
 }
 ZKP_DEV Fq28 fq28_canonical(const Fq28& a) { return fq28_from_s30(s30_canonical(a)); }
-// tight internal residue (radix 2^392) -> the ABI's saturated canonical residue (radix 2^384): x 2^392 * 2^384 / 2^392
-ZKP_DEV Fq fq28_to_abi(const Fq28& a) {
-    const S30 d = s30_canonical(a * fq28_from_sat(Fq::one()));
+// canonical integer, 13 x 30 bits -> 12 x 32 bits
+ZKP_DEV Fq s30_to_sat(const S30& d) {
     Fq y;
 #pragma unroll
     for (int w = 0; w < 12; w++) {
@@ -57,6 +56,8 @@ ZKP_DEV Fq fq28_to_abi(const Fq28& a) {
     }
     return y;
 }
+// tight internal residue (radix 2^392) -> the ABI's saturated canonical residue (radix 2^384): x 2^392 * 2^384 / 2^392
+ZKP_DEV Fq fq28_to_abi(const Fq28& a) { return s30_to_sat(s30_canonical(a * fq28_from_sat(Fq::one()))); }
 
 // [k]P: k canonical (8 words, below r), P finite at p[q * pst]; t[q * tst] is the lane's table entry.  See the head of this file.
 ZKP_DEV X28 g1_28_mul_glv(const uint32_t* k, const uint4* p, uint64_t pst, uint4* t, uint64_t tst) {

@@ -56,6 +56,13 @@ _SIGS = {
     "zkp_g1_validate": ([_VP, _U8P, _SZ, _U8P, _VP], C.c_int),
     "zkp_g1_bases_validate": ([_VP, _U8P, _VP], C.c_int),
     "zkp_srs_check": ([_VP, _VP, _SZ, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_g1_decompress_dev": ([_VP, _SZ, C.c_uint, _VP, _U8P, _U8P, _VP, _VP], C.c_int),
+    "zkp_g1_decompress": ([_VP, _SZ, C.c_uint, _VP, _U8P, _U8P, _VP], C.c_int),
+    "zkp_g1_compress_dev": ([_VP, _U8P, _SZ, _VP, _VP], C.c_int),
+    "zkp_g1_compress": ([_VP, _U8P, _SZ, _VP], C.c_int),
+    "zkp_g1_bases_create_compressed": ([_VP, _SZ, C.c_uint, _VP, C.POINTER(_VP)], C.c_int),
+    "zkp_fr_from_bytes_dev": ([_VP, _SZ, C.c_int, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
+    "zkp_fr_to_bytes_dev": ([_VP, _SZ, C.c_int, _VP, _VP], C.c_int),
     "zkp_g1_scale_dev": ([_VP, _U8P, _VP, _SZ, _VP], C.c_int),
     "zkp_g1_ntt_dev": ([_VP, _U8P, C.c_uint, C.c_int, _VP], C.c_int),
     "zkp_g1_ntt": ([_VP, _U8P, C.c_uint, C.c_int], C.c_int),
@@ -360,6 +367,76 @@ def g1_validate_dev(xy_tensor, n, is_inf_tensor=None, status_tensor=None, stream
     return _validation_dict(v)
 
 
+class _G1Decoding(C.Structure):  # zkp_g1_decoding in include/zkp_hip.h
+    _fields_ = [("checked", C.c_uint64), ("bad", C.c_uint64), ("malformed", C.c_uint64), ("non_canonical", C.c_uint64),
+                ("off_curve", C.c_uint64), ("outside_subgroup", C.c_uint64), ("first_bad", C.c_uint64), ("first_status", C.c_int)]
+
+
+G1_MALFORMED = 4                # status byte of a compressed point that is no encoding at all (the others as above)
+G1_DECODE_SUBGROUP = 1          # ZKP_G1_DECODE_SUBGROUP
+_G1_STATUS_WORD = {G1_NON_CANONICAL: "canonical", G1_OFF_CURVE: "curve", G1_OUTSIDE_SUBGROUP: "subgroup", G1_MALFORMED: "encoding"}
+
+
+def _decoding_dict(v):
+    return {name: int(getattr(v, name)) for name, _ in _G1Decoding._fields_}
+
+
+def _bytes48(data):
+    return _np(np.frombuffer(data, dtype=np.uint8).copy() if isinstance(data, (bytes, bytearray, memoryview)) else data, np.uint8, (-1, 48))
+
+
+def g1_decompress(data, check_subgroup=True, want_status=False):
+    """zkp_g1_decompress: n x 48 bytes of compressed points (bytes or a uint8 array) decoded on the GPU -> ((n, 12) limbs, (n,) infinity
+    flags, report dict of checked, bad, malformed, non_canonical, off_curve, outside_subgroup, first_bad, first_status), and the (n,) uint8
+    statuses with want_status.  A point that does not decode is zeros with flag 0 and a non-zero status; nothing is raised for it."""
+    b = _bytes48(data)
+    n = b.shape[0]
+    xy, inf = np.zeros((n, 12), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+    status = np.zeros(n, dtype=np.uint8) if want_status else None
+    v = _G1Decoding()
+    _chk(lib().zkp_g1_decompress(_ptr(b), n, G1_DECODE_SUBGROUP if check_subgroup else 0, _ptr(xy), _ptr(inf), _ptr(status), C.byref(v)))
+    return (xy, inf, _decoding_dict(v), status) if want_status else (xy, inf, _decoding_dict(v))
+
+
+def g1_decompress_dev(bytes_tensor, n, out_xy_tensor, out_inf_tensor, check_subgroup=True, status_tensor=None, stream=None):
+    """zkp_g1_decompress_dev: the same with the 48 n bytes, the 96 n bytes of limbs, the n flags and the n statuses (or None) resident on
+    the device -> the report dict.  Blocks until the report is there."""
+    st = _dev_ptr(status_tensor, n) if status_tensor is not None else None
+    v = _G1Decoding()
+    _chk(lib().zkp_g1_decompress_dev(_dev_ptr(bytes_tensor, 48 * n), n, G1_DECODE_SUBGROUP if check_subgroup else 0,
+                                     _dev_ptr(out_xy_tensor, 96 * n), _dev_ptr(out_inf_tensor, n), st, _stream_ptr(stream), C.byref(v)))
+    return _decoding_dict(v)
+
+
+def g1_compress(xy, is_inf=None):
+    """zkp_g1_compress: (n, 12) limbs and optional infinity flags -> (n, 48) uint8.  No validation."""
+    xy = _np(xy, np.uint64, (-1, 12))
+    inf = _np(is_inf, np.uint8, (xy.shape[0],)) if is_inf is not None else None
+    out = np.zeros((xy.shape[0], 48), dtype=np.uint8)
+    _chk(lib().zkp_g1_compress(_ptr(xy), _ptr(inf), xy.shape[0], _ptr(out)))
+    return out
+
+
+def g1_compress_dev(xy_tensor, n, out_bytes_tensor, is_inf_tensor=None, stream=None):
+    """zkp_g1_compress_dev: the same on the device; nothing is synchronised."""
+    inf = _dev_ptr(is_inf_tensor, n) if is_inf_tensor is not None else None
+    _chk(lib().zkp_g1_compress_dev(_dev_ptr(xy_tensor, 96 * n), inf, n, _dev_ptr(out_bytes_tensor, 48 * n), _stream_ptr(stream)))
+
+
+def fr_from_bytes_dev(bytes_tensor, n, out_tensor, big_endian=True, stream=None):
+    """zkp_fr_from_bytes_dev: n x 32 bytes of canonical scalars on the device -> n x 4 limbs of the Fr memory form on the device;
+    -> (number of values >= r, lowest such index or n).  Their slots are zeroed."""
+    bad, first = C.c_uint64(0), C.c_uint64(0)
+    _chk(lib().zkp_fr_from_bytes_dev(_dev_ptr(bytes_tensor, 32 * n), n, int(bool(big_endian)), _dev_ptr(out_tensor, 32 * n), _stream_ptr(stream),
+                                     C.byref(bad), C.byref(first)))
+    return int(bad.value), int(first.value)
+
+
+def fr_to_bytes_dev(in_tensor, n, out_bytes_tensor, big_endian=True, stream=None):
+    """zkp_fr_to_bytes_dev: the way back; nothing is synchronised."""
+    _chk(lib().zkp_fr_to_bytes_dev(_dev_ptr(in_tensor, 32 * n), n, int(bool(big_endian)), _dev_ptr(out_bytes_tensor, 32 * n), _stream_ptr(stream)))
+
+
 def srs_check(bases, g2s, n, r):
     """zkp_srs_check: are the first n points of the handle [s^i]G for the s behind g2s = [s]_2?  r: (n - 1, 4) random Fr limbs.
     -> 1 accepted, 0 rejected.  Assumes valid points: G1Bases.validate() first."""
@@ -392,6 +469,19 @@ class G1Bases(_Handle):
         h = C.c_void_p()
         inf = C.c_void_p(is_inf_tensor.data_ptr()) if is_inf_tensor is not None else None
         _chk(lib().zkp_g1_bases_create_dev(_dev_ptr(xy_tensor, 96 * n), inf, n, _stream_ptr(stream), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_compressed(cls, data, check_subgroup=True):
+        """zkp_g1_bases_create_compressed: n x 48 bytes of compressed points, decoded on the GPU straight into the handle (one slot, never
+        sharded).  A point that does not decode raises ZkpError(ZKP_E_ARG) naming its index; ``.report`` of the error is the report dict."""
+        b = _bytes48(data)
+        h, v = C.c_void_p(), _G1Decoding()
+        code = lib().zkp_g1_bases_create_compressed(_ptr(b), b.shape[0], G1_DECODE_SUBGROUP if check_subgroup else 0, C.byref(v), C.byref(h))
+        if code != ZKP_OK:
+            err = ZkpError(code, lib().zkp_last_error().decode())
+            err.report = _decoding_dict(v)
+            raise err
         return cls(h)
 
     def precompute(self, window_bits=20, glv=False):
@@ -1173,6 +1263,39 @@ class KzgCellVerifier(_Handle):
                                             _dev_ptr(evals_tensor, 32 * cells * self.l), _dev_ptr(proofs_tensor, 96 * cells), pinf,
                                             _dev_ptr(weights_tensor, 32 * cells), _stream_ptr(stream), C.byref(acc)))
         return bool(acc.value)
+
+    def verify_bytes(self, commitments48, commit_index, coset_index, cell_bytes, proofs48, weights, big_endian=True):
+        """The wire form: commitments48 (n_commits x 48) and proofs48 (n_cells x 48) compressed points, cell_bytes n_cells x l x 32 bytes
+        of canonical scalars (big-endian unless told otherwise), weights (n_cells, 4) limbs as in verify -> accepted.  Everything is
+        decoded on the device; the points without the subgroup test, which zkp_kzg_verify_cells_dev runs on every point anyway.  A point
+        or scalar that does not decode raises ZkpError(ZKP_E_ARG) naming the array, the index and the status word.  Cells in the library's
+        own order (EIP-7594's bit-reversed numbering is not built)."""
+        import torch
+        ci, ki = self._indices(commit_index, coset_index)
+        cells = ci.shape[0]
+        cb, pb = _bytes48(commitments48), _bytes48(proofs48)
+        sb = _np(np.frombuffer(cell_bytes, dtype=np.uint8).copy() if isinstance(cell_bytes, (bytes, bytearray, memoryview)) else cell_bytes, np.uint8,
+                 (cells * self.l, 32))
+        if pb.shape[0] != cells:
+            raise ZkpError(ZKP_E_ARG, "one proof per cell")
+        if cells == 0:
+            return True
+        pts = []
+        for name, b in (("commitments", cb), ("proofs", pb)):
+            n = b.shape[0]
+            xy = torch.empty(max(n, 1) * 12, dtype=torch.int64, device="cuda")
+            inf = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+            rep = g1_decompress_dev(torch.from_numpy(b).cuda(), n, xy, inf, check_subgroup=False) if n else {"bad": 0}
+            if rep["bad"]:
+                raise ZkpError(ZKP_E_ARG, f"{name}[{rep['first_bad']}] does not decode ({_G1_STATUS_WORD[rep['first_status']]})")
+            pts.append((xy, inf, n))
+        ev = torch.empty(cells * self.l * 4, dtype=torch.int64, device="cuda")
+        bad, first = fr_from_bytes_dev(torch.from_numpy(sb).cuda(), cells * self.l, ev, big_endian=big_endian)
+        if bad:
+            raise ZkpError(ZKP_E_ARG, f"cell_bytes[{first}] does not decode (canonical): cell {first // self.l}, value {first % self.l}")
+        wt = torch.from_numpy(_np(weights, np.uint64, (cells, 4)).view(np.int64)).cuda()
+        (cxy, cinf, n_commits), (pxy, pinf, _) = pts
+        return self.verify_dev(cxy, n_commits, ci, ki, ev, pxy, wt, commits_inf_tensor=cinf, proofs_inf_tensor=pinf)
 
     def aggregate_dev(self, n_commits, commit_index, coset_index, evals_tensor, weights_tensor, out_interp_tensor, out_commit_weights_tensor,
                       out_proof_scalars_tensor, stream=None):
