@@ -592,6 +592,45 @@ int zkp_selftest_poly_eval_dev(size_t count, const void *const *d_c, const size_
 int zkp_selftest_poly_lincomb_dev(size_t terms, const void *const *d_p, const size_t *len, const uint64_t *s, size_t n_out, void *d_out,
                                   void *stream);
 int zkp_selftest_poly_trim_len_dev(const void *d_c, size_t n, size_t *out_len, void *stream);
+/* Self-test hook for the MSM's digit recoding and counting sort (csrc/msm.hpp: msm_digits*, msm_parthist, msm_partprefix, msm_partstart,
+ * msm_partscatter<TILE>, msm_binsort, msm_rank, msm_order).  Plans the MSM of `count` resident scalar vectors of n scalars over `bases`
+ * exactly as zkp_msm_g1_batch_dev does, sizes the same workspaces, fills the sort outputs of scalar range `range_index` with 0xFF bytes,
+ * runs that range's digits + sort through the launch function the MSM itself uses, and stops: no accumulate, no reduction.  *geom receives
+ * the geometry the kernels were given and, in out_words, the 32-bit words of every output below.  out == NULL: only *geom is filled and
+ * nothing is launched (the caller sizes its buffers with it).  Otherwise every out->d_out[k] is a device buffer of out->words[k] >=
+ * geom->out_words[k] words that receives, with W = nwin and every array window-major (window w first):
+ *   ZKP_SORT_DIGITS    W x n         the digits, (|d| << 1) | (d < 0), 0 = skip; laid out [msm or scalar half][slice][scalar of the range]
+ *   ZKP_SORT_ENTRIES   W x n x 2     first pass: (index | sign << 31, (bucket - 1) & (2^lo_bits - 1)), partition hi = (bucket - 1) >> lo_bits
+ *                                    at [pstart[hi], pstart[hi + 1]); words past pstart[nhi] untouched (0xFF)
+ *   ZKP_SORT_PSTART    W x (nhi+1)   exclusive prefix of the partition sizes
+ *   ZKP_SORT_GHIST     W x 256       ghist[255 - min(size, 255)] = buckets of that size class
+ *   ZKP_SORT_START     W x (nb+2)    start[0] = 0, start[b] = first sorted position of bucket b = 1..nb, start[nb + 1] = non-zero digits
+ *   ZKP_SORT_SORTED    W x n         index | sign << 31 in bucket order; words past start[nb + 1] untouched
+ *   ZKP_SORT_PERM      W x nb        the buckets by non-increasing min(size, 255)
+ *   ZKP_SORT_OVER      W x 2         {candidates n_over = buckets with min(size, 255) > min(run_limit, 254), pieces}
+ *   ZKP_SORT_OVER_B    W x over_cap  over_b[r] = perm[r], r < n_over; the rest untouched
+ *   ZKP_SORT_OVER_OFF  W x (over_cap+1)  first piece of candidate r (a candidate of size <= run_limit has none), [n_over] = pieces
+ *   ZKP_SORT_DESC      W x desc_cap x 4  piece j = {bucket, piece index p, start[b] + p piece, min(that + piece, start[b + 1])}
+ * Refused: null bases / geom / scalar pointers (ZKP_E_ARG), more scalars than bases (ZKP_E_SIZE), a range index past the plan and an
+ * output that is null or too small (ZKP_E_ARG).  Returns without waiting for the stream.  Not part of the hot path
+ * (tests/test_gpu_msm_sort.py, tests/model/msm_sort_model.py). */
+enum { ZKP_SORT_DIGITS = 0, ZKP_SORT_ENTRIES, ZKP_SORT_PSTART, ZKP_SORT_GHIST, ZKP_SORT_START, ZKP_SORT_SORTED, ZKP_SORT_PERM,
+       ZKP_SORT_OVER, ZKP_SORT_OVER_B, ZKP_SORT_OVER_OFF, ZKP_SORT_DESC, ZKP_SORT_OUTPUTS };
+typedef struct {
+    uint32_t c, nwin, nb, nslice;        /* widest slice in bits, sort windows W, buckets per window 2^(c-1), slices per scalar */
+    uint32_t shared, glv, nchunk, lo_bits, nhi, run_limit, piece, over_cap, desc_cap, ps_tile;
+    uint32_t nranges, range_index;       /* scalar ranges of the plan, and the one that ran */
+    uint64_t n, ns, chunk;               /* entries per sort window, scalars of this range, entries per chunk of the first pass */
+    uint64_t range_off, range_len;       /* first scalar and scalars of this range */
+    uint64_t out_words[ZKP_SORT_OUTPUTS];
+    uint16_t off[36];                    /* bit offset of every slice, off[nslice] >= the bits covered */
+} zkp_msm_sort_geometry;
+typedef struct {
+    void *d_out[ZKP_SORT_OUTPUTS];
+    size_t words[ZKP_SORT_OUTPUTS];      /* capacity of each buffer in 32-bit words */
+} zkp_msm_sort_outputs;
+int zkp_selftest_msm_sort_dev(const zkp_bases *bases, const void *const *d_scalars, size_t count, size_t n, size_t range_index, void *stream,
+                              zkp_msm_sort_geometry *geom, const zkp_msm_sort_outputs *out);
 /* [s^i]G for i < n into host memory (kzg/src/srs.rs:48-63: n = circuit_size + 3). */
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t *out_xy);
 

@@ -48,6 +48,45 @@ pub struct zkp_g1_validation {
     pub first_status: i32, // its status, or 0
 }
 
+/// outputs of zkp_selftest_msm_sort_dev, in the order of the ZKP_SORT_* enum: digits, entries, pstart, ghist, start, sorted, perm, over,
+/// over_b, over_off, desc
+pub const ZKP_SORT_OUTPUTS: usize = 11;
+
+/// the geometry the MSM's sort kernels were given (zkp_selftest_msm_sort_dev); out_words: 32-bit words of every output
+#[repr(C)]
+pub struct zkp_msm_sort_geometry {
+    pub c: u32,
+    pub nwin: u32,
+    pub nb: u32,
+    pub nslice: u32,
+    pub shared: u32,
+    pub glv: u32,
+    pub nchunk: u32,
+    pub lo_bits: u32,
+    pub nhi: u32,
+    pub run_limit: u32,
+    pub piece: u32,
+    pub over_cap: u32,
+    pub desc_cap: u32,
+    pub ps_tile: u32,
+    pub nranges: u32,
+    pub range_index: u32,
+    pub n: u64,
+    pub ns: u64,
+    pub chunk: u64,
+    pub range_off: u64,
+    pub range_len: u64,
+    pub out_words: [u64; ZKP_SORT_OUTPUTS],
+    pub off: [u16; 36],
+}
+
+/// caller's device buffers for zkp_selftest_msm_sort_dev and their capacities in 32-bit words
+#[repr(C)]
+pub struct zkp_msm_sort_outputs {
+    pub d_out: [*mut c_void; ZKP_SORT_OUTPUTS],
+    pub words: [usize; ZKP_SORT_OUTPUTS],
+}
+
 /// ZKP_G1_DECODE_SUBGROUP: run the subgroup test of zkp_g1_validate while decoding
 pub const ZKP_G1_DECODE_SUBGROUP: u32 = 1;
 
@@ -227,6 +266,7 @@ extern "C" {
     pub fn zkp_selftest_poly_eval_dev(count: usize, d_c: *const *const c_void, len: *const usize, z: *const u64, out: *mut u64, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_poly_lincomb_dev(terms: usize, d_p: *const *const c_void, len: *const usize, s: *const u64, n_out: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_poly_trim_len_dev(d_c: *const c_void, n: usize, out_len: *mut usize, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_msm_sort_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, range_index: usize, stream: *mut c_void, geom: *mut zkp_msm_sort_geometry, out: *const zkp_msm_sort_outputs) -> i32;
     pub fn zkp_srs_g1(secret: *const u64, n: usize, out_xy: *mut u64) -> i32;
     pub fn zkp_ntt_fr(data: *mut u64, log_n: u32, inverse: i32, coset: *const u64) -> i32;
     pub fn zkp_ntt_fr_dev(d_data: *mut c_void, log_n: u32, batch: usize, inverse: i32, coset: *const u64, stream: *mut c_void) -> i32;

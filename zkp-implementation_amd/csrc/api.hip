@@ -1273,6 +1273,18 @@ int zkp_selftest_glv_split_dev(const void* d_scalars, size_t n, void* d_out, voi
     return ZKP_OK;
 } ZKP_CATCH_INT
 
+int zkp_selftest_msm_sort_dev(const zkp_bases* bases, const void* const* d_scalars, size_t count, size_t n, size_t range_index, void* stream,
+                              zkp_msm_sort_geometry* geom, const zkp_msm_sort_outputs* out) try {
+    if (!bases || !geom || (count && !d_scalars)) return fail(ZKP_E_ARG, "null argument");
+    if (!bases->shards.empty()) return fail(ZKP_E_ARG, kShardedDev);
+    for (size_t m = 0; n && m < count && m < (size_t)MSM_MAX_BATCH; m++)
+        if (!d_scalars[m]) return fail(ZKP_E_ARG, "null scalar pointer");
+    CTX_ENTER(bases->slot);
+    WsOrder ord(reinterpret_cast<hipStream_t>(stream));
+    return msm_sort_selftest(bases, reinterpret_cast<const Fr* const*>(d_scalars), count, n, range_index, reinterpret_cast<hipStream_t>(stream),
+                             geom, out);
+} ZKP_CATCH_INT
+
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t* out_xy) try {
     if (!secret || (n && !out_xy)) return fail(ZKP_E_ARG, "null argument");
     if (!n) return ZKP_OK;

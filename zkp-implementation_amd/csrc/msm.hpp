@@ -66,7 +66,8 @@ ZKP_DEV void msm_recode(const uint32_t (&k)[8], bool skip, const MsmGeom& g, uin
         uint32_t u = ((uint32_t)(v >> sh) & ((1u << width) - 1)) + carry;
         uint32_t enc;
         if (u > (1u << (width - 1))) {  // u in (2^(width-1), 2^width]: use u - 2^width < 0 and carry one into the next slice
-            enc = (((1u << width) - u) << 1) | 1u;
+            const uint32_t mag = (1u << width) - u;  // 0 when an all-ones slice takes a carry: the digit 0 is the skip word, without a sign
+            enc = (mag << 1) | (mag ? 1u : 0u);
             carry = 1;
         } else {
             enc = u << 1;

@@ -321,6 +321,52 @@ int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t
     return ZKP_OK;
 }
 
+// Self-test hook (zkp_selftest_msm_sort_dev): the plan, the pass and the workspaces of msm_partial_batch, then launch_sort of ONE
+// range and nothing else.  The range's sort outputs are filled with 0xFF first, so that a word no kernel owns is recognisable, and
+// copied to the caller's buffers behind the sort.  out == nullptr: the geometry only, nothing touches the device.
+int msm_sort_selftest(const zkp_bases* bases, const Fr* const* d_scalars, size_t count, size_t n, size_t range_index, hipStream_t st,
+                      zkp_msm_sort_geometry* geom, const zkp_msm_sort_outputs* out) {
+    MsmPlan p;
+    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, nullptr, ctx().tail_max_waves, &p))
+        return fail(rc, p.error);
+    if (range_index >= p.lens.size()) return fail(ZKP_E_ARG, "range index past the plan's scalar ranges");
+    const MsmRange r = range_geom(p, range_index);
+    const MsmGeom& g = r.g;
+    const size_t W = g.nwin, wn = W * g.n;
+    *geom = zkp_msm_sort_geometry{};
+    geom->c = g.c, geom->nwin = g.nwin, geom->nb = g.nb, geom->nslice = g.nslice, geom->shared = g.shared, geom->glv = g.glv;
+    geom->nchunk = g.nchunk, geom->lo_bits = p.sg.lo_bits, geom->nhi = p.sg.nhi, geom->run_limit = g.run_limit, geom->piece = g.piece;
+    geom->over_cap = p.over_cap, geom->desc_cap = p.desc_cap, geom->ps_tile = (uint32_t)p.ps_tile;
+    geom->nranges = (uint32_t)p.lens.size(), geom->range_index = (uint32_t)range_index;
+    geom->n = g.n, geom->ns = g.ns, geom->chunk = g.chunk, geom->range_off = r.off, geom->range_len = r.len;
+    std::memcpy(geom->off, g.off, sizeof(geom->off));
+    static_assert(sizeof(geom->off) == sizeof(g.off), "zkp_msm_sort_geometry::off");
+    const size_t words[ZKP_SORT_OUTPUTS] = {wn, 2 * wn, W * (p.sg.nhi + 1), W * 256, W * (g.nb + 2), wn, W * g.nb, 2 * W,
+                                            W * p.over_cap, W * ((size_t)p.over_cap + 1), 4 * W * p.desc_cap};
+    for (int k = 0; k < ZKP_SORT_OUTPUTS; k++) geom->out_words[k] = words[k];
+    if (!out) return ZKP_OK;
+    for (int k = 0; k < ZKP_SORT_OUTPUTS; k++) {
+        if (!out->d_out[k]) return fail(ZKP_E_ARG, "null output buffer");
+        if (out->words[k] < words[k]) return fail(ZKP_E_ARG, "output buffer too small (zkp_msm_sort_geometry::out_words)");
+    }
+    MsmPass pass{p, bases, d_scalars, count, nullptr, st, st};
+    ZCHK(pass.grow());
+    const RangeBuffers rb = pass.range_buffers(r.set);
+    Ctx& cx = ctx();
+    HIPCHK(hipMemsetAsync(rb.sorted, 0xFF, 4 * wn, st));
+    HIPCHK(hipMemsetAsync(rb.start, 0xFF, 4 * W * (g.nb + 2), st));
+    HIPCHK(hipMemsetAsync(rb.perm, 0xFF, 4 * W * g.nb, st));
+    HIPCHK(hipMemsetAsync(rb.desc, 0xFF, p.over_bytes, st));  // desc, over, over_b, over_off of this buffer set
+    HIPCHK(hipMemsetAsync(cx.entries.get(), 0xFF, 8 * wn, st));
+    pass.launch_sort(rb, r);
+    HIPCHK(hipGetLastError());
+    const void* const src[ZKP_SORT_OUTPUTS] = {cx.digits.get(), cx.entries.get(), pass.pstart, pass.ghist, rb.start, rb.sorted, rb.perm,
+                                               rb.over,         rb.over_b,        rb.over_off, rb.desc};
+    for (int k = 0; k < ZKP_SORT_OUTPUTS; k++)
+        if (words[k]) HIPCHK(hipMemcpyAsync(out->d_out[k], src[k], 4 * words[k], hipMemcpyDeviceToDevice, st));
+    return ZKP_OK;
+}
+
 int msm_partial(const zkp_bases* bases, const Fr* d_scalars, size_t n, hipStream_t st, HXyzz* out) {
     return msm_partial_batch(bases, &d_scalars, 1, n, st, out);
 }

@@ -115,6 +115,7 @@ _SIGS = {
     "zkp_selftest_poly_eval_dev": ([_SZ, _VP, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_selftest_poly_lincomb_dev": ([_SZ, _VP, _VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_poly_trim_len_dev": ([_VP, _SZ, C.POINTER(_SZ), _VP], C.c_int),
+    "zkp_selftest_msm_sort_dev": ([_VP, _VP, _SZ, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_srs_g1": ([_VP, _SZ, _VP], C.c_int),
     "zkp_ntt_fr": ([_VP, C.c_uint, C.c_int, _VP], C.c_int),
     "zkp_ntt_fr_dev": ([_VP, C.c_uint, _SZ, C.c_int, _VP, _VP], C.c_int),
@@ -666,6 +667,42 @@ def selftest_poly_trim_len_dev(c_tensor, n, stream=None):
     out = C.c_size_t(0)
     _chk(lib().zkp_selftest_poly_trim_len_dev(_fr_ptrs([c_tensor], [n])[0], n, C.byref(out), _stream_ptr(stream)))
     return int(out.value)
+
+
+# outputs of zkp_selftest_msm_sort_dev in the order of the ZKP_SORT_* enum of include/zkp_hip.h
+MSM_SORT_OUTPUTS = ("digits", "entries", "pstart", "ghist", "start", "sorted", "perm", "over", "over_b", "over_off", "desc")
+
+
+class _MsmSortGeometry(C.Structure):  # zkp_msm_sort_geometry in include/zkp_hip.h
+    _fields_ = [(k, C.c_uint32) for k in ("c", "nwin", "nb", "nslice", "shared", "glv", "nchunk", "lo_bits", "nhi", "run_limit", "piece",
+                                          "over_cap", "desc_cap", "ps_tile", "nranges", "range_index")] + \
+               [(k, C.c_uint64) for k in ("n", "ns", "chunk", "range_off", "range_len")] + \
+               [("out_words", C.c_uint64 * len(MSM_SORT_OUTPUTS)), ("off", C.c_uint16 * 36)]
+
+
+class _MsmSortOutputs(C.Structure):  # zkp_msm_sort_outputs in include/zkp_hip.h
+    _fields_ = [("d_out", C.c_void_p * len(MSM_SORT_OUTPUTS)), ("words", C.c_size_t * len(MSM_SORT_OUTPUTS))]
+
+
+def selftest_msm_sort_dev(bases, scalar_tensors, n, range_index=0, out_tensors=None, stream=None):
+    """zkp_selftest_msm_sort_dev: plan the MSM of the scalar vectors (each n x 32 B, resident) over ``bases`` and run the digits + sort
+    of one scalar range.  out_tensors None: -> the geometry dict only (its "out_words" names the int32 words of every output);
+    otherwise a dict of int32 CUDA tensors keyed by MSM_SORT_OUTPUTS, which receive the outputs -> the geometry dict."""
+    k = len(scalar_tensors)
+    ptrs = (C.c_void_p * max(k, 1))(*[_dev_ptr(t, 32 * n).value for t in scalar_tensors])
+    g, o = _MsmSortGeometry(), None
+    if out_tensors is not None:
+        o = _MsmSortOutputs()
+        for i, name in enumerate(MSM_SORT_OUTPUTS):
+            t = out_tensors[name]
+            o.d_out[i] = _dev_ptr(t, 0).value if t is not None and t.numel() else None
+            o.words[i] = t.numel() * t.element_size() // 4 if t is not None else 0
+    _chk(lib().zkp_selftest_msm_sort_dev(bases._h if bases is not None else None, ptrs, k, n, range_index, _stream_ptr(stream), C.byref(g),
+                                         C.byref(o) if o is not None else None))
+    d = {name: int(getattr(g, name)) for name, _ in _MsmSortGeometry._fields_[:21]}
+    d["out_words"] = {name: int(g.out_words[i]) for i, name in enumerate(MSM_SORT_OUTPUTS)}
+    d["off"] = [int(x) for x in g.off[:d["nslice"] + 1]]
+    return d
 
 
 def msm_g1_dev(bases, scalars_tensor, n, stream=None):
