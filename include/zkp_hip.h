@@ -44,7 +44,10 @@
  * a leaf workgroup of a recoverer multiplies, read by zkp_kzg_recoverer_create; tuning aid), ZKP_KZG_RECOVER_MAX_BYTES
  * (zkp_kzg_recoverer_create refuses, with ZKP_E_NOMEM and the sizes in zkp_last_error(), a recoverer whose device workspace is larger
  * than this many bytes; default: no limit), ZKP_KZG_CELLS_CHUNK_LOG (0..16: log2 of the cells of a coset, or weights of a commitment,
- * one lane of a cell verifier sums before the chunk sums are combined, read by zkp_kzg_cell_verifier_create, default 4; tuning aid).
+ * one lane of a cell verifier sums before the chunk sums are combined, read by zkp_kzg_cell_verifier_create, default 4; tuning aid),
+ * ZKP_KZG_EVALS_INVERSE (the one inversion per workgroup of zkp_kzg_open_evals_*: 0 = division steps, 1 = the Fermat power; read by
+ * every call; tuning aid), ZKP_KZG_EVALS_MAX_BYTES (zkp_kzg_eval_opener_create refuses, with ZKP_E_NOMEM and the sizes in
+ * zkp_last_error(), an opener whose device workspace is larger than this many bytes; default: no limit).
  */
 #ifndef ZKP_HIP_H
 #define ZKP_HIP_H
@@ -512,6 +515,47 @@ int zkp_kzg_verify_cells_dev(const zkp_kzg_cell_verifier *v, const void *d_commi
 int zkp_kzg_cells_aggregate_dev(const zkp_kzg_cell_verifier *v, size_t n_commits, size_t n_cells, const uint32_t *commit_index,
                                 const uint32_t *coset_index, const void *d_evals, const void *d_weights, void *d_out_interp,
                                 void *d_out_commit_weights, void *d_out_proof_scalars, void *stream);
+
+/* ---- Evaluation-form KZG: commitments and openings of a batch of polynomials given by their VALUES on the domain, no transform ----
+ * A row holds the n = 2^log_n values of a polynomial of degree < n on the roots of unity: position i holds the value at w^i
+ * (ZKP_KZG_ORDER_NATURAL) or at w^bitrev(i) (ZKP_KZG_ORDER_BITREV, the order blobs are stored in), as n x 4 limbs in the Fr memory
+ * form, used as given (values that are not canonical are reduced by the arithmetic).  With d_i = w^e(i) - z:
+ *   f(z) = (1 - z^n) / n * sum_i f_i w^e(i) / d_i,    q_e(i) = (f_i - f(z)) / d_i,    proof = the MSM of q over the Lagrange-basis SRS;
+ * for z = w^m in the domain f(z) = f at w^m and q_m = -w^(-m) sum_{j != m} q_j w^j.  The commitment is the MSM of the row itself.
+ * Row p of every output is byte for byte what zkp_kzg_open(monomial_srs, coeffs_p, n, z_p) and zkp_kzg_commit(monomial_srs,
+ * coeffs_p, n) return for the interpolant of row p.
+ *
+ * zkp_kzg_eval_opener_create: `lagrange` is BORROWED and must outlive the opener.  It is any single-device handle of at least n
+ * points (plain, expanded or endomorphism-split) made by zkp_g1_bases_lagrange for the same log_n; that it really is that basis is
+ * the caller's responsibility (nothing here can tell).  The opener lives on the bases' slot and owns a device workspace of about
+ * 32 n (1 + 2 max_polys) bytes, refused with ZKP_E_NOMEM -- sizes in zkp_last_error(), nothing left allocated -- beyond the free
+ * memory or ZKP_KZG_EVALS_MAX_BYTES.  ZKP_E_ARG: a null argument, log_n outside 1..24, an unknown order, max_polys outside 1..4096,
+ * sharded bases; ZKP_E_SIZE: bases of fewer than n points.
+ *
+ * The calls take n_polys <= max_polys rows (more: ZKP_E_SIZE; none: ZKP_OK, the device is not touched), rows contiguous, and one
+ * point per row (n_polys x 4 limbs).  Points (n_polys x 12 limbs, n_polys flag bytes; the identity has zero limbs and flag 1) and
+ * values y_p = f_p(z_p) (n_polys x 4) come back to HOST memory, so the four commit / open entries BLOCK; the *_dev forms differ only
+ * in where the rows and the points z live.  zkp_kzg_open_evals_field_dev is the field half alone: d_out_y (n_polys x 4) and
+ * d_out_quotient (n_polys x n x 4, in NATURAL order whatever the opener's order) in device memory; it allocates nothing and does not
+ * wait for the device.  There is no host path: without a device every entry is ZKP_E_DEVICE. */
+#define ZKP_KZG_ORDER_NATURAL 0
+#define ZKP_KZG_ORDER_BITREV  1   /* position i of a row holds the value at w^bitrev(i): the order blobs are stored in */
+typedef struct zkp_kzg_eval_opener zkp_kzg_eval_opener;
+int zkp_kzg_eval_opener_create(const zkp_bases *lagrange, unsigned log_n, int order, size_t max_polys, zkp_kzg_eval_opener **out);
+void zkp_kzg_eval_opener_destroy(zkp_kzg_eval_opener *o);
+int zkp_kzg_commit_evals_batch(const zkp_kzg_eval_opener *o, const uint64_t *evals, size_t n_polys, uint64_t *out_xy, uint8_t *out_is_inf);
+int zkp_kzg_commit_evals_batch_dev(const zkp_kzg_eval_opener *o, const void *d_evals, size_t n_polys, void *stream, uint64_t *out_xy,
+                                   uint8_t *out_is_inf);
+int zkp_kzg_open_evals_batch(const zkp_kzg_eval_opener *o, const uint64_t *evals, size_t n_polys, const uint64_t *z, uint64_t *out_xy,
+                             uint8_t *out_is_inf, uint64_t *out_y);
+int zkp_kzg_open_evals_batch_dev(const zkp_kzg_eval_opener *o, const void *d_evals, size_t n_polys, const void *d_z, void *stream,
+                                 uint64_t *out_xy, uint8_t *out_is_inf, uint64_t *out_y);
+int zkp_kzg_open_evals_field_dev(const zkp_kzg_eval_opener *o, const void *d_evals, size_t n_polys, const void *d_z, void *d_out_y,
+                                 void *d_out_quotient, void *stream);
+/* Self-test hook for the two device inversions of Fr (csrc/fr_inv.hpp, csrc/plonk.hpp): inverts n elements in device memory, one lane
+ * each, 8 x u32 words in and out (the memory form, Montgomery radix 2^256).  method 0: Bernstein-Yang division steps, any value
+ * below 2r in; method 1: the Fermat power.  Canonical a^-1 R out; 0 (and r, method 0) map to 0.  At most 2^24 elements. */
+int zkp_selftest_fr_inverse_dev(const void *d_in, size_t n, int method, void *d_out, void *stream);
 
 /* ---- single scalar multiplication: KzgScheme::commit_para, kzg/src/scheme.rs:78-82 (`g1_0.mul(para)`),
  *      6x per proof at plonk/src/prover.rs:183-188.  Serial by nature: computed on the host. ---- */

@@ -32,6 +32,7 @@
 #include "g1_codec.hpp"
 #include "kzg_recover.hpp"
 #include "kzg_cells.hpp"
+#include "kzg_evals.hpp"
 #include "plonk.hpp"
 #include "nova.hpp"
 #include "fri.hpp"
@@ -1429,4 +1430,5 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "g1_ntt_host.inc"
 #include "kzg_recover_host.inc"
 #include "kzg_cells_host.inc"
+#include "kzg_evals_host.inc"
 #include "nova_host.inc"

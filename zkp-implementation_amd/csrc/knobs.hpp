@@ -18,6 +18,7 @@ enum Knob {
     KNOB_NTT_NO_WIDE_PASS, KNOB_NTT_SHARD_MIN_LOG, KNOB_PLONK_NO_POLL, KNOB_FRI_ZERO_AS_0, KNOB_FRI_FR_TAIL_LOG,
     KNOB_KZG_COSET_GROUP_LOG, KNOB_KZG_OPENER_MAX_BYTES, KNOB_KZG_RECOVER_LEAF_LOG, KNOB_KZG_RECOVER_MAX_BYTES,
     KNOB_KZG_CELLS_CHUNK_LOG,
+    KNOB_KZG_EVALS_INVERSE, KNOB_KZG_EVALS_MAX_BYTES,
     KNOB_COUNT
 };
 
@@ -106,6 +107,12 @@ constexpr KnobRow kKnobs[KNOB_COUNT] = {
     {KNOB_KZG_CELLS_CHUNK_LOG, "ZKP_KZG_CELLS_CHUNK_LOG", KNOB_TUNING, KNOB_INT, 0, 16, KNOB_COMPUTED,
      "cell verifiers created from now on sum at most 2^v cells of a coset (weights of a commitment) per lane before the sums of the "
      "chunks are combined (default: KZG_CELLS_CHUNK_LOG): profiles/kzg_verify_cells.md"},
+    {KNOB_KZG_EVALS_INVERSE, "ZKP_KZG_EVALS_INVERSE", KNOB_TUNING, KNOB_INT, 0, 1, KNOB_COMPUTED,
+     "the one inversion per workgroup of zkp_kzg_open_evals_*: 0 division steps (fr_inv.hpp), 1 the Fermat power (default: "
+     "KZG_EVALS_INVERSE): profiles/kzg_open_evals.md"},
+    {KNOB_KZG_EVALS_MAX_BYTES, "ZKP_KZG_EVALS_MAX_BYTES", KNOB_POLICY, KNOB_INT, 0, LLONG_MAX, LLONG_MAX,
+     "an evaluation-form opener (zkp_kzg_eval_opener_create) whose device workspace is larger than this is refused with ZKP_E_NOMEM "
+     "before anything is allocated"},
 };
 
 constexpr bool knob_rows_in_enum_order() {

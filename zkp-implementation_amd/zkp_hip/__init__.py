@@ -103,6 +103,14 @@ _SIGS = {
     "zkp_g1_mul": ([_VP, C.c_uint8, _VP, _VP, _VP], C.c_int),
     "zkp_g1_fixed_base_mul_dev": ([_VP, _SZ, _VP, _U8P, _VP], C.c_int),
     "zkp_selftest_fq_inverse_dev": ([_VP, _SZ, C.c_int, _VP, _VP], C.c_int),
+    "zkp_selftest_fr_inverse_dev": ([_VP, _SZ, C.c_int, _VP, _VP], C.c_int),
+    "zkp_kzg_eval_opener_create": ([_VP, C.c_uint, C.c_int, _SZ, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_eval_opener_destroy": ([_VP], None),
+    "zkp_kzg_commit_evals_batch": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_kzg_commit_evals_batch_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_open_evals_batch": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_open_evals_batch_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_open_evals_field_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_selftest_fq28_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_fr29_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_fp_dev": ([C.c_int, C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
@@ -574,6 +582,12 @@ def selftest_fq_inverse_dev(in_tensor, n, form, out_tensor, stream=None):
     words = 12 if form == 0 else 16
     _chk(lib().zkp_selftest_fq_inverse_dev(_dev_ptr(in_tensor, 4 * words * n), n, form, _dev_ptr(out_tensor, 4 * words * n),
                                            _stream_ptr(stream)))
+
+
+def selftest_fr_inverse_dev(in_tensor, n, method, out_tensor, stream=None):
+    """zkp_selftest_fr_inverse_dev: n scalar-field elements (8 x u32 each, the memory form) inverted on the device, one lane each.
+    method 0: division steps (csrc/fr_inv.hpp), 1: the Fermat power."""
+    _chk(lib().zkp_selftest_fr_inverse_dev(_dev_ptr(in_tensor, 32 * n), n, method, _dev_ptr(out_tensor, 32 * n), _stream_ptr(stream)))
 
 
 # operation numbers of the lane-level self-tests (the enums of csrc/selftest.hpp; tests/test_limb_model_cpu.py compares the two)
@@ -1248,6 +1262,9 @@ class KzgRecoverer(_Handle):
                                                     _dev_ptr(inconsistent_tensor, 4 * n_polys), _stream_ptr(stream)))
 
 
+ZKP_KZG_ORDER_NATURAL, ZKP_KZG_ORDER_BITREV = 0, 1  # the orders of a row of evaluations (zkp_hip.kzg_evals.KzgEvalOpener)
+
+
 def _points(p):
     """(xy, is_inf) or xy alone -> ((count, 12) limbs, (count,) flags or None)"""
     xy, inf = p if isinstance(p, tuple) else (p, None)
@@ -1370,6 +1387,8 @@ class KzgScheme:
         self._coset_openers = {}  # (log_n, log_l) -> KzgOpener (open_cosets), released by close()
         self._recoverers = {}  # (log_n, log_l) -> KzgRecoverer (recover_cosets), released by close()
         self._cell_verifiers = {}  # (log_n, log_l) -> (g2_sl bytes, KzgCellVerifier) (verify_cells), released by close()
+        self._lagrange = {}  # log_n -> G1Bases (the Lagrange basis of the first 2^log_n points), released by close()
+        self._eval_openers = {}  # (log_n, bitrev) -> KzgEvalOpener (commit_evals_batch, open_evals_batch), released by close()
         if expand_bases:  # the SRS is fixed for the life of the scheme: pay the one-off expansion here
             srs.bases.precompute(0)
 
@@ -1455,12 +1474,40 @@ class KzgScheme:
             weights = _fr_mont_rows([secrets.randbits(128) for _ in range(cells)])
         return kept[1].verify(commitments, ci, coset_index, evals, proofs, weights)
 
+    def _eval_opener(self, log_n, bitrev, polys):
+        """The opener kept per (log_n, bitrev), replaced by a larger one when a batch outgrows it; the Lagrange basis is kept per log_n"""
+        from .kzg_evals import KzgEvalOpener  # (that module imports this one)
+        if log_n not in self._lagrange:
+            self._lagrange[log_n] = self.srs.bases.lagrange(log_n)
+        kept = self._eval_openers.get((log_n, bool(bitrev)))
+        if kept is None or kept.max_polys < polys:
+            if kept is not None:
+                kept.close()
+            self._eval_openers[log_n, bool(bitrev)] = KzgEvalOpener(self._lagrange[log_n], log_n, max(polys, 1), bitrev=bitrev)
+        return self._eval_openers[log_n, bool(bitrev)]
+
+    def commit_evals_batch(self, evals, log_n, bitrev=False):
+        """The commitments of the polynomials whose values on the domain of 2^log_n roots of unity are the rows of `evals`
+        ((P, n, 4); bitrev: position i holds the value at w^bitrev(i)): KzgEvalOpener.commit_batch -> ((P, 12), (P,) flags)"""
+        evals = _np(evals, np.uint64)
+        return self._eval_opener(log_n, bitrev, evals.shape[0]).commit_batch(evals)
+
+    def open_evals_batch(self, evals, zs, log_n, bitrev=False):
+        """The openings of those polynomials, row p at zs[p] ((P, 4)), with no transform: KzgEvalOpener.open_batch ->
+        (((P, 12) proofs, (P,) flags), (P, 4) values); row p is what open returns for the coefficients of row p's interpolant."""
+        evals = _np(evals, np.uint64)
+        return self._eval_opener(log_n, bitrev, evals.shape[0]).open_batch(evals, zs)
+
     def close(self):
         """Release the device memory of the openers open_all and open_cosets made (about 1.4 KB per point of a domain for open_all, about
         1.1 KB for open_cosets: 512 B of kept slices, 512 B of partial sums and 64 B of scalars, plus up to 64 MiB); the SRS stays."""
         for op in (list(self._openers.values()) + list(self._coset_openers.values()) + list(self._recoverers.values()) +
                    [ver for _, ver in self._cell_verifiers.values()]):
             op.close()
+        for op in list(self._eval_openers.values()) + list(self._lagrange.values()):  # (the openers borrow the bases: they go first)
+            op.close()
+        self._eval_openers = {}
+        self._lagrange = {}
         self._cell_verifiers = {}
         self._openers = {}
         self._coset_openers = {}
