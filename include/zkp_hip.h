@@ -273,6 +273,29 @@ int zkp_msm_g1_dev(const zkp_bases *bases, const void *d_scalars, size_t n, void
  * 267-268.  out_xy: count x 12 limbs; out_is_inf: count bytes. */
 int zkp_msm_g1_batch_dev(const zkp_bases *bases, const void *const *d_scalars, size_t count, size_t n, void *stream,
                          uint64_t *out_xy, uint8_t *out_is_inf);
+/* The three entries above for SHORT scalars: the caller states that every canonical scalar is below 2^bits (128-bit random weights of a
+ * batched check, witness columns of bits, bytes or words), and the MSM runs only the slices such scalars fill: the first t slices of
+ * the handle's offset table, t the smallest index with off[t] >= bits + 1 -- per-window mode: t of the 256 / c windows; an expansion:
+ * its first t planes; split planes (zkp_g1_bases_precompute_glv) up to 127 bits: ONE bucket set over the first t planes with no
+ * scalar split (a scalar below 2^127 < lambda is its own low half), so a batch may again hold 64 vectors; from 128 bits on a split
+ * handle runs both bucket sets over all its slices.  The result is the point the unbounded entry gives, bit for bit.
+ *   bits        1..256, else ZKP_E_ARG before anything is launched.  bits >= 255 IS the unbounded entry (r < 2^255).  One bound holds
+ *               for every vector of a batch.
+ *   violation   a scalar that is not below 2^bits: ZKP_E_ARG, zkp_last_error() names one offending vector and its index in that
+ *               vector, and the bound; the outputs are not written.  The kernels check this themselves and the pass runs to its end,
+ *               so the handle and the slot's workspaces serve the next call; an accepted call pays no launch and no wait for the check.
+ *   refusals    a sharded handle is ZKP_E_ARG (also for zkp_msm_g1_bits: bounded MSMs take single-device bases); everything else as
+ *               the unbounded entry: n > len(bases) ZKP_E_SIZE, the batch limits, null arguments.
+ * zkp_msm_g1_bits feeds host scalars exactly as zkp_msm_g1 does, ranges from 2^19 terms over expanded bases included. */
+int zkp_msm_g1_bits(const zkp_bases *bases, const uint64_t *scalars, size_t n, unsigned bits, uint64_t out_xy[12], uint8_t *out_is_inf);
+int zkp_msm_g1_bits_dev(const zkp_bases *bases, const void *d_scalars, size_t n, unsigned bits, void *stream, uint64_t out_xy[12],
+                        uint8_t *out_is_inf);
+int zkp_msm_g1_batch_bits_dev(const zkp_bases *bases, const void *const *d_scalars, size_t count, size_t n, unsigned bits, void *stream,
+                              uint64_t *out_xy, uint8_t *out_is_inf);
+/* *out_bits = the largest bit length among n scalars in device memory (n x 4 limbs, the Fr memory form, 16-byte aligned): the smallest
+ * `bits` the entries above accept for this vector; 0 for n == 0 or all zeros.  One memory-bound pass (32 bytes per scalar) on the
+ * slot chosen from d_scalars as in zkp_g1_validate_dev.  BLOCKS: synchronises `stream` before it returns. */
+int zkp_fr_bit_length_dev(const void *d_scalars, size_t n, void *stream, unsigned *out_bits);
 /* Multi-GPU building block: the same sum left UNNORMALISED as an extended-Jacobian point
  * (X, Y, ZZ, ZZZ = 24 limbs, ZZ == 0 for the identity) so that per-GPU partial sums can be exchanged
  * (RCCL all-gather of 192 bytes per rank) and combined with zkp_g1_xyzz_sum. */
@@ -675,6 +698,12 @@ typedef struct {
 } zkp_msm_sort_outputs;
 int zkp_selftest_msm_sort_dev(const zkp_bases *bases, const void *const *d_scalars, size_t count, size_t n, size_t range_index, void *stream,
                               zkp_msm_sort_geometry *geom, const zkp_msm_sort_outputs *out);
+/* The same hook over the plan and the digits kernel of the bounded entries (zkp_msm_g1_batch_bits_dev with this `bits`): *geom shows the
+ * slices the bound leaves (nslice, n, nwin, glv), the digits are those of the truncated offset table.  bits outside 1..256 is ZKP_E_ARG,
+ * bits >= 255 is the hook above.  With out != NULL and bits < 255 it synchronises `stream` before it returns; a scalar past the bound
+ * is not reported here. */
+int zkp_selftest_msm_sort_bits_dev(const zkp_bases *bases, const void *const *d_scalars, size_t count, size_t n, size_t range_index,
+                                   unsigned bits, void *stream, zkp_msm_sort_geometry *geom, const zkp_msm_sort_outputs *out);
 /* [s^i]G for i < n into host memory (kzg/src/srs.rs:48-63: n = circuit_size + 3). */
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t *out_xy);
 

@@ -218,6 +218,10 @@ extern "C" {
     pub fn zkp_msm_g1(bases: *const zkp_bases, scalars: *const u64, n: usize, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_msm_g1_dev(bases: *const zkp_bases, d_scalars: *const c_void, n: usize, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_msm_g1_batch_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
+    pub fn zkp_msm_g1_bits(bases: *const zkp_bases, scalars: *const u64, n: usize, bits: u32, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
+    pub fn zkp_msm_g1_bits_dev(bases: *const zkp_bases, d_scalars: *const c_void, n: usize, bits: u32, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
+    pub fn zkp_msm_g1_batch_bits_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, bits: u32, stream: *mut c_void, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
+    pub fn zkp_fr_bit_length_dev(d_scalars: *const c_void, n: usize, stream: *mut c_void, out_bits: *mut u32) -> i32;
     pub fn zkp_msm_g1_partial_dev(bases: *const zkp_bases, d_scalars: *const c_void, n: usize, stream: *mut c_void, out_xyzz: *mut u64) -> i32;
     pub fn zkp_msm_g1_partial(bases: *const zkp_bases, scalars: *const u64, n: usize, out_xyzz: *mut u64) -> i32;
     pub fn zkp_g1_bases_shard_count(b: *const zkp_bases) -> i32;
@@ -278,6 +282,7 @@ extern "C" {
     pub fn zkp_selftest_poly_lincomb_dev(terms: usize, d_p: *const *const c_void, len: *const usize, s: *const u64, n_out: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_poly_trim_len_dev(d_c: *const c_void, n: usize, out_len: *mut usize, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_msm_sort_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, range_index: usize, stream: *mut c_void, geom: *mut zkp_msm_sort_geometry, out: *const zkp_msm_sort_outputs) -> i32;
+    pub fn zkp_selftest_msm_sort_bits_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, range_index: usize, bits: u32, stream: *mut c_void, geom: *mut zkp_msm_sort_geometry, out: *const zkp_msm_sort_outputs) -> i32;
     pub fn zkp_srs_g1(secret: *const u64, n: usize, out_xy: *mut u64) -> i32;
     pub fn zkp_ntt_fr(data: *mut u64, log_n: u32, inverse: i32, coset: *const u64) -> i32;
     pub fn zkp_ntt_fr_dev(d_data: *mut c_void, log_n: u32, batch: usize, inverse: i32, coset: *const u64, stream: *mut c_void) -> i32;

@@ -956,7 +956,7 @@ const char* const kShardedDev = "bases are sharded over several devices: device-
                                 "(zkp_set_device + zkp_g1_bases_create*); use zkp_msm_g1 with host scalars";
 
 // sum_{i<n} scalars[i] * bases[i] for host scalars over ONE slot's bases, unnormalised
-int msm_host_scalars(const zkp_bases* bases, const uint64_t* scalars, size_t n, HXyzz* r) {
+int msm_host_scalars(const zkp_bases* bases, const uint64_t* scalars, size_t n, HXyzz* r, unsigned bits = MSM_BITS_MAX) {
     CTX_ENTER(bases->slot);
     hipStream_t st = host_stream();
     WsOrder ord(st);
@@ -970,10 +970,10 @@ int msm_host_scalars(const zkp_bases* bases, const uint64_t* scalars, size_t n, 
         ZCHK(ctx().copy_stream.ensure(hipStreamNonBlocking));
         ZCHK(ctx().copy_event.ensure(hipEventDisableTiming));
         const MsmFeed feed{scalars, ctx().copy_stream, ctx().copy_event, msm_feed_ranges(n)};  // (the range policy: msm_plan.hpp)
-        return msm_partial_batch(bases, &d_sc, 1, n, st, r, &feed);
+        return msm_partial_batch(bases, &d_sc, 1, n, st, r, &feed, bits);
     }
     HIPCHK(hipMemcpyAsync(ctx().scalars.p, scalars, 32 * n, hipMemcpyHostToDevice, st));
-    return msm_partial(bases, d_sc, n, st, r);
+    return msm_partial(bases, d_sc, n, st, r, bits);
 }
 
 // One MSM over the chunks of a sharded handle: body(i, lo, len, &part) runs chunk i's share [lo, lo + len) of the n terms on that
@@ -1033,6 +1033,75 @@ int zkp_msm_g1(const zkp_bases* bases, const uint64_t* scalars, size_t n, uint64
     HXyzz r;
     ZCHK(msm_host_scalars_any(bases, scalars, n, &r));
     r.to_affine(out_xy, out_is_inf);
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+// ---- bounded scalars: every canonical scalar below 2^bits (include/zkp_hip.h).  From 255 bits on these ARE the entries above.
+static int check_scalar_bits(const zkp_bases* bases, unsigned bits) {
+    if (bits < 1 || bits > MSM_BITS_MAX) return fail(ZKP_E_ARG, "bits must be 1..256");
+    if (bases && !bases->shards.empty()) return fail(ZKP_E_ARG, "bases are sharded over several devices: the bounded MSM entries take single-device bases");
+    return ZKP_OK;
+}
+
+int zkp_msm_g1_bits(const zkp_bases* bases, const uint64_t* scalars, size_t n, unsigned bits, uint64_t out_xy[12], uint8_t* out_is_inf) try {
+    ZCHK(check_scalar_bits(bases, bits));
+    if (bits >= MSM_BITS_WHOLE) return zkp_msm_g1(bases, scalars, n, out_xy, out_is_inf);
+    if (!bases || !out_xy || !out_is_inf || (n && !scalars)) return fail(ZKP_E_ARG, "null argument");
+    HXyzz r;
+    ZCHK(msm_host_scalars(bases, scalars, n, &r, bits));
+    r.to_affine(out_xy, out_is_inf);
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_msm_g1_bits_dev(const zkp_bases* bases, const void* d_scalars, size_t n, unsigned bits, void* stream, uint64_t out_xy[12],
+                        uint8_t* out_is_inf) try {
+    ZCHK(check_scalar_bits(bases, bits));
+    if (bits >= MSM_BITS_WHOLE) return zkp_msm_g1_dev(bases, d_scalars, n, stream, out_xy, out_is_inf);
+    if (!bases || !out_xy || !out_is_inf || (n && !d_scalars)) return fail(ZKP_E_ARG, "null argument");
+    CTX_ENTER(bases->slot);
+    WsOrder ord(reinterpret_cast<hipStream_t>(stream));
+    HXyzz r;
+    ZCHK(msm_partial(bases, reinterpret_cast<const Fr*>(d_scalars), n, reinterpret_cast<hipStream_t>(stream), &r, bits));
+    r.to_affine(out_xy, out_is_inf);
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+int zkp_msm_g1_batch_bits_dev(const zkp_bases* bases, const void* const* d_scalars, size_t count, size_t n, unsigned bits, void* stream,
+                              uint64_t* out_xy, uint8_t* out_is_inf) try {
+    ZCHK(check_scalar_bits(bases, bits));
+    if (bits >= MSM_BITS_WHOLE) return zkp_msm_g1_batch_dev(bases, d_scalars, count, n, stream, out_xy, out_is_inf);
+    if (!bases || (count && (!d_scalars || !out_xy || !out_is_inf))) return fail(ZKP_E_ARG, "null argument");
+    CTX_ENTER(bases->slot);
+    WsOrder ord(reinterpret_cast<hipStream_t>(stream));
+    std::vector<HXyzz> r(count);
+    ZCHK(msm_partial_batch(bases, reinterpret_cast<const Fr* const*>(d_scalars), count, n, reinterpret_cast<hipStream_t>(stream), r.data(),
+                           nullptr, bits));
+    batch_to_affine(r.data(), count, out_xy, out_is_inf);
+    return ZKP_OK;
+} ZKP_CATCH_INT
+
+// The largest bit length among n resident scalars: the OR of their canonical words (fr_or_words_kernel), read back and measured here
+int zkp_fr_bit_length_dev(const void* d_scalars, size_t n, void* stream, unsigned* out_bits) try {
+    if (!out_bits || (n && !d_scalars)) return fail(ZKP_E_ARG, "null argument");
+    *out_bits = 0;
+    if (!n) return ZKP_OK;
+    if (reinterpret_cast<uintptr_t>(d_scalars) & 15) return fail(ZKP_E_ARG, "device pointers must be 16-byte aligned");
+    int slot = -1;
+    ZCHK(slot_of_device_pointer(d_scalars, &slot));
+    CTX_ENTER(slot);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    WsOrder ord(st);
+    ZCHK(ctx().tmp.ensure(256));
+    uint32_t* d_or = reinterpret_cast<uint32_t*>(ctx().tmp.p);
+    uint32_t words[8];
+    HIPCHK(hipMemsetAsync(d_or, 0, sizeof words, st));
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + MSM_THREADS - 1) / MSM_THREADS, FR_OR_MAX_BLOCKS);
+    hipLaunchKernelGGL(fr_or_words_kernel, dim3(blocks), dim3(MSM_THREADS), 0, st, reinterpret_cast<const uint4*>(d_scalars), (uint64_t)n, d_or);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(words, d_or, sizeof words, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int q = 7; q >= 0 && !*out_bits; q--)
+        if (words[q]) *out_bits = 32u * (unsigned)q + 32u - (unsigned)__builtin_clz(words[q]);
     return ZKP_OK;
 } ZKP_CATCH_INT
 
@@ -1284,6 +1353,19 @@ int zkp_selftest_msm_sort_dev(const zkp_bases* bases, const void* const* d_scala
     WsOrder ord(reinterpret_cast<hipStream_t>(stream));
     return msm_sort_selftest(bases, reinterpret_cast<const Fr* const*>(d_scalars), count, n, range_index, reinterpret_cast<hipStream_t>(stream),
                              geom, out);
+} ZKP_CATCH_INT
+
+int zkp_selftest_msm_sort_bits_dev(const zkp_bases* bases, const void* const* d_scalars, size_t count, size_t n, size_t range_index, unsigned bits,
+                                   void* stream, zkp_msm_sort_geometry* geom, const zkp_msm_sort_outputs* out) try {
+    ZCHK(check_scalar_bits(bases, bits));
+    if (bits >= MSM_BITS_WHOLE) return zkp_selftest_msm_sort_dev(bases, d_scalars, count, n, range_index, stream, geom, out);
+    if (!bases || !geom || (count && !d_scalars)) return fail(ZKP_E_ARG, "null argument");
+    for (size_t m = 0; n && m < count && m < (size_t)MSM_MAX_BATCH; m++)
+        if (!d_scalars[m]) return fail(ZKP_E_ARG, "null scalar pointer");
+    CTX_ENTER(bases->slot);
+    WsOrder ord(reinterpret_cast<hipStream_t>(stream));
+    return msm_sort_selftest(bases, reinterpret_cast<const Fr* const*>(d_scalars), count, n, range_index, reinterpret_cast<hipStream_t>(stream),
+                             geom, out, bits);
 } ZKP_CATCH_INT
 
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t* out_xy) try {

@@ -98,6 +98,77 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_digits_glv_kernel(DigitSource
     msm_recode(k2, skip, g, nwin1, 2 * blockIdx.y + 1, i, digits);
 }
 
+// Bounded scalars (zkp_msm_g1_bits*; the plan: msm_plan.hpp, msm_bound_slices).  true: a bit at position `bits` or above is set
+ZKP_DEV bool fr_exceeds_bits(const uint32_t (&k)[8], uint32_t bits) {
+    uint32_t hi = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) {  // `bits` is uniform: scalar branches, static indexing
+        if (bits <= 32 * q) hi |= k[q];
+        else if (bits < 32 * q + 32) hi |= k[q] >> (bits - 32 * q);
+    }
+    return hi != 0;
+}
+constexpr unsigned long long MSM_NO_VIOLATION = ~0ull;
+// The digits kernels of the bounded path: as msm_digits_kernel / msm_digits_glv_kernel (GLV: a split handle above
+// MSM_BITS_GLV_ONE_SET bits), over the nwin1 slices the plan kept, and every canonical value is tested against 2^bits first.  A
+// violation goes to *violation -- pinned host memory next to the result flags of the pass, which the host reads with them -- as
+// (vector << 32) | index from the start of the vector: one 8-byte vector store by the lowest offending lane of a wave, so a pass with
+// several offenders names one of them.  The digits of an offender are those of its low bits: every bucket id stays in range, the pass
+// runs to its end and the host discards the sum.
+template <bool GLV>
+__global__ __launch_bounds__(MSM_THREADS) void msm_digits_bits_kernel(DigitSources src, const uint8_t* __restrict__ base_inf, MsmGeom g,
+                                                                     uint32_t nwin1, uint32_t bits, uint64_t range_off,
+                                                                     unsigned long long* __restrict__ violation,
+                                                                     uint32_t* __restrict__ digits) {
+    const uint64_t i = (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= g.ns) return;
+    const Fr k = from_mont(src.scalars[blockIdx.y][i]);
+    const bool skip = base_inf != nullptr && base_inf[i] != 0;  // (an infinity base does not excuse its scalar from the bound)
+    const unsigned long long bad = __ballot(fr_exceeds_bits(k.l, bits));
+    if (bad && (int)(threadIdx.x & 63u) == __ffsll((long long)bad) - 1)
+        __hip_atomic_store(violation, (unsigned long long)blockIdx.y << 32 | (range_off + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if constexpr (GLV) {
+        const GlvHalves h = glv_split(k.l);
+        const uint32_t k1[8] = {h.k1[0], h.k1[1], h.k1[2], h.k1[3], 0, 0, 0, 0}, k2[8] = {h.k2[0], h.k2[1], h.k2[2], h.k2[3], 0, 0, 0, 0};
+        msm_recode(k1, skip, g, nwin1, 2 * blockIdx.y, i, digits);
+        msm_recode(k2, skip, g, nwin1, 2 * blockIdx.y + 1, i, digits);
+    } else {
+        msm_recode(k.l, skip, g, nwin1, blockIdx.y, i, digits);
+    }
+}
+
+// The OR of the canonical words of n Montgomery scalars into out[0..8) (zeroed by the caller): its bit length is the largest bit length
+// in the vector (zkp_fr_bit_length_dev).  Memory-bound, 32 bytes read per element: a grid-stride loop, the wave's OR by shuffles, one
+// LDS step per workgroup, then at most eight atomics.
+constexpr uint32_t FR_OR_MAX_BLOCKS = 2048;  // eight workgroups of four waves per CU on 256 CUs: every SIMD full
+__global__ __launch_bounds__(MSM_THREADS) void fr_or_words_kernel(const uint4* __restrict__ scalars, uint64_t n, uint32_t* __restrict__ out) {
+    uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint64_t i = (uint64_t)blockIdx.x * MSM_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * MSM_THREADS) {
+        const Fr k = from_mont(Fr::load(scalars + i * 2));
+#pragma unroll
+        for (int q = 0; q < 8; q++) acc[q] |= k.l[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[q] |= __shfl_xor(acc[q], off);
+    __shared__ uint32_t part[MSM_THREADS / 64][8];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    if (lane < 8) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) v = lane == (uint32_t)q ? acc[q] : v;
+        part[wave][lane] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int w = 0; w < MSM_THREADS / 64; w++) v |= part[w][threadIdx.x];
+        if (v) atomicOr(out + threadIdx.x, v);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Counting sort of the point indices by bucket, two levels so that every scattered store lands in a region that
 // stays resident in L2 until its cache lines are complete (a single-level scatter over 2^15 buckets writes 4 bytes

@@ -32,11 +32,13 @@ struct MsmPass {
     size_t count;
     const MsmFeed* feed;
     hipStream_t st, sst;  // accumulate + reduction; digits + sort (a second stream when ranges overlap)
+    unsigned bits = 0;    // != 0: the bounded path (zkp_msm_g1_bits*): the digits kernels test every scalar against 2^bits
     Ctx& cx = ctx();
     const size_t W = p.g.nwin, nhi = p.sg.nhi;
     uint32_t *ptot, *pstart, *ghist, *gcur;  // counts = W x nchunk x nhi, then W x nhi, W x (nhi + 1), W x 256 size histogram, W x 256
     uint4* result_out;                       // pinned: W x c result points, then
-    uint32_t* result_flags;                  // W flag words
+    uint32_t* result_flags;                  // W flag words, then (bounded path)
+    unsigned long long* violation;           // the scalar that broke the bound (msm_digits_bits_kernel), MSM_NO_VIOLATION: none
     RangeUpload up;                          // host feed: the uploader's job for the later ranges, joined when the pass ends
 
     std::array<std::tuple<const char*, DevBuf*, size_t>, 14> buffers() {
@@ -50,13 +52,16 @@ struct MsmPass {
     // blit launch per MSM); the device `result` buffer holds the barrier counters of the last launch.
     int grow() {
         for (const auto& [name, buf, bytes] : buffers()) ZCHK(buf->ensure(bytes));
-        ZCHK(cx.host_result.ensure(p.bytes.host_result, hipHostMallocPortable | hipHostMallocMapped));  // written by this slot's device
+        ZCHK(cx.host_result.ensure(p.bytes.host_result + (bits ? 16 : 0), hipHostMallocPortable | hipHostMallocMapped));  // written by this slot's device
         ptot = cx.counts.get() + W * p.g.nchunk * nhi;
         pstart = ptot + W * nhi;
         ghist = pstart + W * (nhi + 1);
         gcur = ghist + W * 256;
         result_out = static_cast<uint4*>(cx.host_result.p);
         result_flags = reinterpret_cast<uint32_t*>(result_out + 16 * W * p.g.c);
+        violation = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(result_flags + W) + 7) & ~(uintptr_t)7);
+        // (the previous pass of this slot was read before its entry returned: nothing on the device still writes here)
+        if (bits) __atomic_store_n(violation, MSM_NO_VIOLATION, __ATOMIC_RELEASE);
         return ZKP_OK;
     }
     RangeBuffers range_buffers(size_t par) const {
@@ -153,8 +158,13 @@ struct MsmPass {
             ProfScope ps("msm_digits", sst);
             DigitSources ds;  // digits laid out [msm][slice][scalar]: a shared-mode sort window is one msm (split planes: one half of one)
             for (size_t m = 0; m < count; m++) ds.scalars[m] = scalars[m] + r.off;
-            hipLaunchKernelGGL(g.glv ? msm_digits_glv_kernel : msm_digits_kernel, dim3(sl.digits_x, (unsigned)count), dim3(MSM_THREADS), 0,
-                               sst, ds, bases->d_inf.p ? bases->d_inf.get() + r.off : nullptr, g, p.nwin1, cx.digits.get());
+            const uint8_t* inf = bases->d_inf.p ? bases->d_inf.get() + r.off : nullptr;
+            if (bits)  // indices in a violation count from the start of the vector: r.off
+                hipLaunchKernelGGL(g.glv ? msm_digits_bits_kernel<true> : msm_digits_bits_kernel<false>, dim3(sl.digits_x, (unsigned)count),
+                                   dim3(MSM_THREADS), 0, sst, ds, inf, g, p.nwin1, (uint32_t)bits, (uint64_t)r.off, violation, cx.digits.get());
+            else
+                hipLaunchKernelGGL(g.glv ? msm_digits_glv_kernel : msm_digits_kernel, dim3(sl.digits_x, (unsigned)count), dim3(MSM_THREADS), 0,
+                                   sst, ds, inf, g, p.nwin1, cx.digits.get());
             MSM_TRACE(sst, r.ridx, "digits");
         }
         ProfScope ps("msm_sort", sst, true);
@@ -281,16 +291,21 @@ void msm_host_tail(const uint32_t* host_res, size_t count, uint32_t wins_per_msm
 // 3 + 1 + 3 + 2 commitments of a PLONK proof) fills the GPU and pays the latency-bound bucket reduction once.  With expanded bases
 // (zkp_g1_bases_precompute) all windows of a scalar share one bucket set; with endomorphism-split planes
 // (zkp_g1_bases_precompute_glv) every scalar vector is a batch of two over the same planes and out[m] = V_1 + phi(V_2).
+// bits < MSM_BITS_WHOLE: the caller's bound on every canonical scalar.  The plan keeps the slices such scalars fill (plan_msm), the
+// digits kernels check the bound, and a scalar that breaks it is ZKP_E_ARG with nothing written to `out`: the pass has run to its end by
+// then (the violation arrives with the result flags, no launch and no wait of its own), so the workspaces serve the next call.
 int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t count, size_t n, hipStream_t st, HXyzz* out,
-                      const MsmFeed* feed = nullptr) {
+                      const MsmFeed* feed = nullptr, unsigned bits = MSM_BITS_MAX) {
     MsmPlan p;
-    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, feed ? &feed->ranges : nullptr, ctx().tail_max_waves, &p))
+    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, feed ? &feed->ranges : nullptr,
+                                ctx().tail_max_waves, &p, bits))
         return fail(rc, p.error);
+    const unsigned bound = bits < MSM_BITS_WHOLE ? bits : 0;
     if (p.lens.empty()) {
         for (size_t m = 0; m < count; m++) out[m] = HXyzz::infinity();
         return ZKP_OK;
     }
-    MsmPass pass{p, bases, d_scalars, count, feed, st, st};
+    MsmPass pass{p, bases, d_scalars, count, feed, st, st, bound};
     ZCHK(pass.grow());
 #ifdef ZKP_MSM_CHECK
     pass.dump(n);
@@ -317,6 +332,12 @@ int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t
 #endif
     if (count > 1 && !knob_flag(KNOB_POOL_NO_WARM)) host_pool().warm(std::chrono::microseconds(3000));  // the tails below run on the pool: wake it now
     ZCHK(wait_msm_result(p.poll_result, p.g.nwin, pass.result_flags, st));
+    if (bound) {
+        const unsigned long long v = __atomic_load_n(pass.violation, __ATOMIC_ACQUIRE);
+        if (v != MSM_NO_VIOLATION)
+            return fail(ZKP_E_ARG, "scalar " + std::to_string(v & 0xffffffffull) + " of vector " + std::to_string(v >> 32) + " is not below 2^" +
+                                       std::to_string(bound) + " (the bound of the call)");
+    }
     msm_host_tail(reinterpret_cast<const uint32_t*>(pass.result_out), count, p.g.shared ? 1u : p.nwin1, p.g.c, p.g.glv != 0, out);  // (the pool's threads are in no context)
     return ZKP_OK;
 }
@@ -325,9 +346,9 @@ int msm_partial_batch(const zkp_bases* bases, const Fr* const* d_scalars, size_t
 // range and nothing else.  The range's sort outputs are filled with 0xFF first, so that a word no kernel owns is recognisable, and
 // copied to the caller's buffers behind the sort.  out == nullptr: the geometry only, nothing touches the device.
 int msm_sort_selftest(const zkp_bases* bases, const Fr* const* d_scalars, size_t count, size_t n, size_t range_index, hipStream_t st,
-                      zkp_msm_sort_geometry* geom, const zkp_msm_sort_outputs* out) {
+                      zkp_msm_sort_geometry* geom, const zkp_msm_sort_outputs* out, unsigned bits = MSM_BITS_MAX) {
     MsmPlan p;
-    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, nullptr, ctx().tail_max_waves, &p))
+    if (const int rc = plan_msm({bases->n, bases->pre_c, bases->pre_planes, bases->pre_off, bases->pre_glv}, count, n, nullptr, ctx().tail_max_waves, &p, bits))
         return fail(rc, p.error);
     if (range_index >= p.lens.size()) return fail(ZKP_E_ARG, "range index past the plan's scalar ranges");
     const MsmRange r = range_geom(p, range_index);
@@ -349,7 +370,7 @@ int msm_sort_selftest(const zkp_bases* bases, const Fr* const* d_scalars, size_t
         if (!out->d_out[k]) return fail(ZKP_E_ARG, "null output buffer");
         if (out->words[k] < words[k]) return fail(ZKP_E_ARG, "output buffer too small (zkp_msm_sort_geometry::out_words)");
     }
-    MsmPass pass{p, bases, d_scalars, count, nullptr, st, st};
+    MsmPass pass{p, bases, d_scalars, count, nullptr, st, st, bits < MSM_BITS_WHOLE ? bits : 0u};  // (a scalar past the bound is not reported here)
     ZCHK(pass.grow());
     const RangeBuffers rb = pass.range_buffers(r.set);
     Ctx& cx = ctx();
@@ -364,9 +385,11 @@ int msm_sort_selftest(const zkp_bases* bases, const Fr* const* d_scalars, size_t
                                                rb.over,         rb.over_b,        rb.over_off, rb.desc};
     for (int k = 0; k < ZKP_SORT_OUTPUTS; k++)
         if (words[k]) HIPCHK(hipMemcpyAsync(out->d_out[k], src[k], 4 * words[k], hipMemcpyDeviceToDevice, st));
+    // the bounded digits kernel writes its violation word in the slot's pinned memory: be done with it before the next entry resets it
+    if (pass.bits) HIPCHK(hipStreamSynchronize(st));
     return ZKP_OK;
 }
 
-int msm_partial(const zkp_bases* bases, const Fr* d_scalars, size_t n, hipStream_t st, HXyzz* out) {
-    return msm_partial_batch(bases, &d_scalars, 1, n, st, out);
+int msm_partial(const zkp_bases* bases, const Fr* d_scalars, size_t n, hipStream_t st, HXyzz* out, unsigned bits = MSM_BITS_MAX) {
+    return msm_partial_batch(bases, &d_scalars, 1, n, st, out, nullptr, bits);
 }

@@ -170,6 +170,21 @@ inline MsmSlices msm_slice_offsets(uint32_t cover, uint32_t window_bits, uint32_
     return s;
 }
 
+// A bound on the scalars (zkp_msm_g1_bits*): canonical values below 2^bits need only the first t slices of an offset table off[0..nslice],
+// t the smallest index with off[t] >= bits + 1, at most nslice.  Slice s takes the bits [off[s], off[s + 1]) plus the carry of the slice
+// below and hands a carry up when that exceeds half its range (msm_recode).  The bit at position `bits` is zero, so the slice that holds it
+// stays below half its range whatever arrives from below, and nothing leaves slice t - 1: the t digits say the scalar exactly.  With
+// t - 1 slices off[t - 1] <= bits, every bit of 2^bits - 1 below off[t - 1] is set, and the top slice kept carries out: t is minimal.
+// From 255 bits on the bound says nothing (r < 2^255): MSM_BITS_WHOLE and above plan the whole scalar.
+// tests/host/msm_bits_plan.cpp checks the rule against brute force for every table the library makes.
+constexpr unsigned MSM_BITS_WHOLE = 255, MSM_BITS_MAX = 256;
+constexpr unsigned MSM_BITS_GLV_ONE_SET = 127;  // lambda = z^2 - 1 > 2^127: a scalar below 2^127 is its own low half, the high half is 0
+inline uint32_t msm_bound_slices(const uint16_t* off, uint32_t nslice, unsigned bits) {
+    uint32_t t = 1;
+    while (t < nslice && off[t] < bits + 1) t++;
+    return t;
+}
+
 // Host-fed scalars (zkp_msm_g1, shared-bucket mode): ranges of at most 2^range_log scalars; first_len != 0: a short first range (its
 // upload is the exposed one), second_len != 0: then a second short one, then the rest
 struct MsmFeedRanges { uint64_t range_log = 0, first_len = 0, second_len = 0; };
@@ -311,9 +326,21 @@ inline AccLaunch acc_launch(const MsmPlan& p, const MsmGeom& g) {
 
 // Everything msm_partial_batch decides before it touches the device, for a device that keeps tail_max_waves waves of the
 // reduction's last-levels launch resident (plan_reduce).  Reads the knobs of knobs.hpp before KNOB_MSM_PLAN_END.
-inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeedRanges* feed, uint32_t tail_max_waves, MsmPlan* p) {
+// scalar_bits: every canonical scalar is below 2^scalar_bits (the caller's promise; the digits kernel of the bounded path checks it).
+// From MSM_BITS_WHOLE on that is the plan of whole scalars.  Below it the plan is the one of bases that hold only the first
+// t = msm_bound_slices planes -- per-window mode: of scalars with t windows -- and split planes run as plain ones up to
+// MSM_BITS_GLV_ONE_SET bits (the high half is zero); with a wider bound they keep both bucket sets and every slice of a half.
+inline int plan_msm(const MsmBases& bases_in, size_t count, size_t n, const MsmFeedRanges* feed, uint32_t tail_max_waves, MsmPlan* p,
+                    unsigned scalar_bits = MSM_BITS_MAX) {
     auto refuse = [p](int code, const char* msg) { p->error = msg; return code; };
     p->lens.clear();
+    if (scalar_bits < 1 || scalar_bits > MSM_BITS_MAX) return refuse(ZKP_E_ARG, "scalar bound outside 1..256 bits");
+    MsmBases bases = bases_in;
+    const bool bounded = scalar_bits < MSM_BITS_WHOLE;
+    if (bounded && bases.pre_c && !(bases.glv && scalar_bits > MSM_BITS_GLV_ONE_SET)) {
+        bases.pre_planes = msm_bound_slices(bases.pre_off, bases.pre_planes, scalar_bits);
+        bases.glv = 0;
+    }
     if (n > bases.n) return refuse(ZKP_E_SIZE, "more scalars than bases (kzg/src/scheme.rs:86)");
     if (count == 0 || n == 0) return ZKP_OK;
     if (n >= (1ull << 31)) return refuse(ZKP_E_ARG, "n >= 2^31");
@@ -327,10 +354,15 @@ inline int plan_msm(const MsmBases& bases, size_t count, size_t n, const MsmFeed
         return refuse(ZKP_E_ARG, "batch of more than 32 MSMs over endomorphism-split bases (two bucket sets per MSM, 64 per pass)");
     MsmGeom& g = p->g = MsmGeom{};
     g.c = shared ? bases.pre_c : pick_window_bits(n);
-    const uint32_t nwin1 = shared ? bases.pre_planes : 256 / g.c + (256 % g.c ? 1 : 0);
-    p->nwin1 = g.nslice = nwin1;
+    uint32_t nwin1 = shared ? bases.pre_planes : 256 / g.c + (256 % g.c ? 1 : 0);
     static_assert(sizeof(MsmGeom::off) / sizeof(uint16_t) == 36, "MsmGeom::off");
     if (nwin1 + 1 > 36) return refuse(ZKP_E_ARG, "more than 35 windows per scalar");
+    if (bounded && !shared) {  // the windows a bounded scalar fills (off[s] = s c, as below)
+        uint16_t off[36];
+        for (uint32_t s = 0; s <= nwin1; s++) off[s] = (uint16_t)(s * g.c);
+        nwin1 = msm_bound_slices(off, nwin1, scalar_bits);
+    }
+    p->nwin1 = g.nslice = nwin1;
     for (uint32_t s = 0; s <= nwin1; s++) g.off[s] = shared ? bases.pre_off[s] : (uint16_t)(s * g.c);
     g.shared = shared ? 1u : 0u;
     g.glv = glv ? 1u : 0u;

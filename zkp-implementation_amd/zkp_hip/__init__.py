@@ -93,6 +93,10 @@ _SIGS = {
     "zkp_msm_g1": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_msm_g1_batch_dev": ([_VP, _VP, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
+    "zkp_msm_g1_bits": ([_VP, _VP, _SZ, C.c_uint, _VP, _VP], C.c_int),
+    "zkp_msm_g1_bits_dev": ([_VP, _VP, _SZ, C.c_uint, _VP, _VP, _VP], C.c_int),
+    "zkp_msm_g1_batch_bits_dev": ([_VP, _VP, _SZ, _SZ, C.c_uint, _VP, _VP, _VP], C.c_int),
+    "zkp_fr_bit_length_dev": ([_VP, _SZ, _VP, C.POINTER(C.c_uint)], C.c_int),
     "zkp_msm_g1_partial_dev": ([_VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_msm_g1_partial": ([_VP, _VP, _SZ, _VP], C.c_int),
     "zkp_g1_bases_shard_count": ([_VP], C.c_int),
@@ -124,6 +128,7 @@ _SIGS = {
     "zkp_selftest_poly_lincomb_dev": ([_SZ, _VP, _VP, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_poly_trim_len_dev": ([_VP, _SZ, C.POINTER(_SZ), _VP], C.c_int),
     "zkp_selftest_msm_sort_dev": ([_VP, _VP, _SZ, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
+    "zkp_selftest_msm_sort_bits_dev": ([_VP, _VP, _SZ, _SZ, _SZ, C.c_uint, _VP, _VP, _VP], C.c_int),
     "zkp_srs_g1": ([_VP, _SZ, _VP], C.c_int),
     "zkp_ntt_fr": ([_VP, C.c_uint, C.c_int, _VP], C.c_int),
     "zkp_ntt_fr_dev": ([_VP, C.c_uint, _SZ, C.c_int, _VP, _VP], C.c_int),
@@ -539,12 +544,17 @@ class G1Bases(_Handle):
         return int(lib().zkp_g1_bases_len(self._h))
 
 
-def msm_g1(bases, scalars):
-    """sum_i scalars[i] * bases[i]  ->  ((12,) uint64 affine Montgomery coords, is_infinity).  Host scalars."""
+def msm_g1(bases, scalars, bits=None):
+    """sum_i scalars[i] * bases[i]  ->  ((12,) uint64 affine Montgomery coords, is_infinity).  Host scalars.
+    bits: every canonical scalar is below 2**bits (zkp_msm_g1_bits: only the slices such scalars fill are run; a scalar past the
+    bound is ZKP_E_ARG).  None: whole scalars."""
     scalars = _np(scalars, np.uint64, (-1, 4))
     out = np.zeros(12, dtype=np.uint64)
     inf = C.c_uint8(0)
-    _chk(lib().zkp_msm_g1(bases._h, _ptr(scalars), scalars.shape[0], _ptr(out), C.byref(inf)))
+    if bits is None:
+        _chk(lib().zkp_msm_g1(bases._h, _ptr(scalars), scalars.shape[0], _ptr(out), C.byref(inf)))
+    else:
+        _chk(lib().zkp_msm_g1_bits(bases._h, _ptr(scalars), scalars.shape[0], bits, _ptr(out), C.byref(inf)))
     return out, int(inf.value)
 
 
@@ -698,10 +708,11 @@ class _MsmSortOutputs(C.Structure):  # zkp_msm_sort_outputs in include/zkp_hip.h
     _fields_ = [("d_out", C.c_void_p * len(MSM_SORT_OUTPUTS)), ("words", C.c_size_t * len(MSM_SORT_OUTPUTS))]
 
 
-def selftest_msm_sort_dev(bases, scalar_tensors, n, range_index=0, out_tensors=None, stream=None):
+def selftest_msm_sort_dev(bases, scalar_tensors, n, range_index=0, out_tensors=None, stream=None, bits=None):
     """zkp_selftest_msm_sort_dev: plan the MSM of the scalar vectors (each n x 32 B, resident) over ``bases`` and run the digits + sort
     of one scalar range.  out_tensors None: -> the geometry dict only (its "out_words" names the int32 words of every output);
-    otherwise a dict of int32 CUDA tensors keyed by MSM_SORT_OUTPUTS, which receive the outputs -> the geometry dict."""
+    otherwise a dict of int32 CUDA tensors keyed by MSM_SORT_OUTPUTS, which receive the outputs -> the geometry dict.
+    bits: the plan and the digits kernel of the bounded entries (zkp_selftest_msm_sort_bits_dev)."""
     k = len(scalar_tensors)
     ptrs = (C.c_void_p * max(k, 1))(*[_dev_ptr(t, 32 * n).value for t in scalar_tensors])
     g, o = _MsmSortGeometry(), None
@@ -711,29 +722,48 @@ def selftest_msm_sort_dev(bases, scalar_tensors, n, range_index=0, out_tensors=N
             t = out_tensors[name]
             o.d_out[i] = _dev_ptr(t, 0).value if t is not None and t.numel() else None
             o.words[i] = t.numel() * t.element_size() // 4 if t is not None else 0
-    _chk(lib().zkp_selftest_msm_sort_dev(bases._h if bases is not None else None, ptrs, k, n, range_index, _stream_ptr(stream), C.byref(g),
-                                         C.byref(o) if o is not None else None))
+    h, po = bases._h if bases is not None else None, C.byref(o) if o is not None else None
+    if bits is None:
+        _chk(lib().zkp_selftest_msm_sort_dev(h, ptrs, k, n, range_index, _stream_ptr(stream), C.byref(g), po))
+    else:
+        _chk(lib().zkp_selftest_msm_sort_bits_dev(h, ptrs, k, n, range_index, bits, _stream_ptr(stream), C.byref(g), po))
     d = {name: int(getattr(g, name)) for name, _ in _MsmSortGeometry._fields_[:21]}
     d["out_words"] = {name: int(g.out_words[i]) for i, name in enumerate(MSM_SORT_OUTPUTS)}
     d["off"] = [int(x) for x in g.off[:d["nslice"] + 1]]
     return d
 
 
-def msm_g1_dev(bases, scalars_tensor, n, stream=None):
+def msm_g1_dev(bases, scalars_tensor, n, stream=None, bits=None):
+    """Resident scalars.  bits: as msm_g1 (zkp_msm_g1_bits_dev); fr_bit_length_dev finds the smallest bound a vector allows."""
     out = np.zeros(12, dtype=np.uint64)
     inf = C.c_uint8(0)
-    _chk(lib().zkp_msm_g1_dev(bases._h, _dev_ptr(scalars_tensor, 32 * n), n, _stream_ptr(stream), _ptr(out),
-                              C.byref(inf)))
+    if bits is None:
+        _chk(lib().zkp_msm_g1_dev(bases._h, _dev_ptr(scalars_tensor, 32 * n), n, _stream_ptr(stream), _ptr(out),
+                                  C.byref(inf)))
+    else:
+        _chk(lib().zkp_msm_g1_bits_dev(bases._h, _dev_ptr(scalars_tensor, 32 * n), n, bits, _stream_ptr(stream), _ptr(out),
+                                       C.byref(inf)))
     return out, int(inf.value)
 
 
-def msm_g1_batch_dev(bases, scalar_tensors, n, stream=None):
-    """Several MSMs over the same bases in one pass (equal length n): list of (affine (12,), is_inf)."""
+def msm_g1_batch_dev(bases, scalar_tensors, n, stream=None, bits=None):
+    """Several MSMs over the same bases in one pass (equal length n): list of (affine (12,), is_inf).
+    bits: one bound for every vector (zkp_msm_g1_batch_bits_dev)."""
     k = len(scalar_tensors)
     ptrs = (C.c_void_p * k)(*[_dev_ptr(t, 32 * n).value for t in scalar_tensors])
     xy, inf = np.zeros((k, 12), dtype=np.uint64), np.zeros(k, dtype=np.uint8)
-    _chk(lib().zkp_msm_g1_batch_dev(bases._h, ptrs, k, n, _stream_ptr(stream), _ptr(xy), _ptr(inf)))
+    if bits is None:
+        _chk(lib().zkp_msm_g1_batch_dev(bases._h, ptrs, k, n, _stream_ptr(stream), _ptr(xy), _ptr(inf)))
+    else:
+        _chk(lib().zkp_msm_g1_batch_bits_dev(bases._h, ptrs, k, n, bits, _stream_ptr(stream), _ptr(xy), _ptr(inf)))
     return [(xy[i].copy(), int(inf[i])) for i in range(k)]
+
+
+def fr_bit_length_dev(tensor, n, stream=None):
+    """zkp_fr_bit_length_dev: the largest bit length among the n resident scalars of ``tensor`` (0 for none or all zeros).  Blocks."""
+    bits = C.c_uint(0)
+    _chk(lib().zkp_fr_bit_length_dev(_dev_ptr(tensor, 32 * n) if n else None, n, _stream_ptr(stream), C.byref(bits)))
+    return int(bits.value)
 
 
 def msm_g1_partial_dev(bases, scalars_tensor, n, stream=None):
