@@ -575,6 +575,75 @@ int zkp_kzg_open_evals_batch_dev(const zkp_kzg_eval_opener *o, const void *d_eva
                                  uint64_t *out_xy, uint8_t *out_is_inf, uint64_t *out_y);
 int zkp_kzg_open_evals_field_dev(const zkp_kzg_eval_opener *o, const void *d_evals, size_t n_polys, const void *d_z, void *d_out_y,
                                  void *d_out_quotient, void *stream);
+/* ---- batched verification of point openings: any number of openings of any number of commitments, one pairing check ----
+ * The device counterpart of zkp_kzg_batch_verify for what zkp_kzg_open, zkp_kzg_open_all and zkp_kzg_open_evals_batch hand out.
+ * Opening i < n_openings claims f_m(z_i) = y_i for the commitment C_m, m = commit_index[i] < n_commits, with the proof W_i =
+ * proofs_xy[i], the point z[i], the value y[i] and the weight r_i = weights[i] (each n_openings x 4 limbs, Fr memory form, used as
+ * given: limbs that are not canonical are reduced by the arithmetic).  commit_index may be NULL: opening i then belongs to
+ * commitment i and n_commits must equal n_openings (else ZKP_E_ARG); that is the shape of zkp_kzg_batch_verify.  The batch is
+ * accepted iff
+ *   e( sum_m (sum_{i: m_i = m} r_i) C_m + sum_i (r_i z_i) W_i - (sum_i r_i y_i) G , G_2 ) == e( sum_i r_i W_i , [s]_2 ),
+ * the equation of zkp_kzg_verify summed with the weights: two Miller loops and one final exponentiation whatever n_openings.
+ * Measured (profiles/kzg_verify_points.md): 34 ms for 1 .. 64 openings and 35 ms for 4096, 31 ms of it the host's pairing, against
+ * 33 ms (N = 1), 35 ms (N = 4), 73 ms (N = 64) and 2.5 s (N = 4096) of zkp_kzg_batch_verify: slower by 1 ms at N = 1, level at 4.
+ * THE WEIGHTS ARE THE CALLER'S RANDOMNESS (as r_primes of zkp_kzg_batch_verify and the weights of zkp_kzg_verify_cells): independent,
+ * unpredictable to whoever made the openings, 128 bits are enough.  A weight of 0 drops its opening from the check; equal (or
+ * otherwise related) weights let the errors of different openings cancel, so a batch with a wrong opening can be accepted.  An
+ * opening may appear more than once; one proof shared by several openings is not supported (give it once per opening).
+ * Everything before the pairings runs on the device: one lane per opening forms r_i z_i and r_i and adds r_i y_i up a tree, the
+ * weights of a commitment are summed in chunks of 2^ZKP_KZG_CELLS_CHUNK_LOG openings (work per lane is bounded however the openings
+ * are spread over the commitments), and both G1 sums are one batch of two MSMs over the n_commits + n_openings + 1 points
+ * [C .., W .., G]: the generator term rides in that pass as one more point.  ALL commitments and proofs are validated on the
+ * device first (canonical, on the curve, in G1; the kernels of zkp_g1_validate): the batched equation is unsound on points outside
+ * G1, so this is not optional.  A bad point is ZKP_E_ARG and zkp_last_error() names the array ("commits" or "proofs"), the lowest
+ * bad index and the status word "canonical", "curve" or "subgroup".  is_inf arrays may be NULL (no identity among them).
+ * zkp_kzg_point_verifier_create: g2s_xy = [s]_2 is validated (ZKP_E_ARG); max_openings and max_commits in 1 .. 2^30, else
+ * ZKP_E_ARG.  The verifier needs no SRS; it lives on the slot current at creation (zkp_set_device) and owns a workspace of about
+ * 100 bytes per opening and 64 per commitment.  A workspace that does not fit is ZKP_E_NOMEM with the sizes in zkp_last_error() and
+ * nothing left allocated.  No device: ZKP_E_DEVICE; there is no host path.
+ * zkp_kzg_verify_points / _dev: a null argument is ZKP_E_ARG, n_openings > max_openings or n_commits > max_commits ZKP_E_SIZE, a
+ * commitment index >= n_commits ZKP_E_ARG naming the opening -- all before anything is launched; n_openings == 0 accepts without
+ * touching the device.  Both end in host pairings, so both BLOCK; the _dev form differs only in where its inputs live:
+ * d_commits_xy, d_commits_is_inf, d_z, d_y, d_proofs_xy, d_proofs_is_inf and d_weights are memory of the verifier's device, the
+ * index array stays HOST memory (the grouping is planned on the host).  Either form may allocate: the transient point handle of
+ * the call, and the slot's MSM workspaces when they have to grow.  While profiling is on a call records the phases
+ * "kzg_points_field", "kzg_points_points" (validation and the MSMs) and "kzg_points_pairing" (host), the last once per pairing check.
+ * zkp_kzg_verify_points_find_bad / _dev: the same, and *first_bad = SIZE_MAX when the batch is accepted, else the lowest index
+ * whose opening fails: the openings are bisected, always testing the lower half of the failing slice with the same weights and all
+ * the commitments (one no opening of the slice names gets weight 0), in at most ceil(log2 n_openings) further pairing checks.  The
+ * points are validated once for the whole batch.  (The index is exact for weights under which no failing slice cancels, the
+ * condition the verdict itself rests on.)
+ * zkp_kzg_points_aggregate_dev: the field half alone, exact to the bit, every word canonical: d_out_commit_weights (n_commits x 4
+ * limbs) the sums of the weights per commitment, d_out_rz and d_out_r (n_openings x 4 each) r_i z_i and r_i, d_out_neg_sum (4) the
+ * value -sum r_i y_i.  Same refusals.  It neither allocates nor waits for the device, except for the previous call's copy of the
+ * index table out of the handle's staging buffer; calls on one handle are serialised with its slot.
+ * zkp_kzg_verify_evals_batch_dev: the blob form.  Row p of d_evals (the rows zkp_kzg_open_evals_batch_dev takes, in the opener's
+ * order) is opened at d_z[p]; no value is supplied: y_p = f_p(z_p) is formed by the opener's field half (z_p in the domain
+ * included) and checked against commitment p and proof p with weight p.  The opener and the verifier must live on the same slot
+ * (ZKP_E_ARG); n_polys beyond the opener's max_polys or the verifier's capacities is ZKP_E_SIZE.  Blocks. */
+typedef struct zkp_kzg_point_verifier zkp_kzg_point_verifier;
+int zkp_kzg_point_verifier_create(const uint64_t g2s_xy[24], size_t max_openings, size_t max_commits, zkp_kzg_point_verifier **out);
+void zkp_kzg_point_verifier_destroy(zkp_kzg_point_verifier *v);
+int zkp_kzg_verify_points(const zkp_kzg_point_verifier *v, const uint64_t *commits_xy, const uint8_t *commits_is_inf, size_t n_commits,
+                          size_t n_openings, const uint32_t *commit_index, const uint64_t *z, const uint64_t *y, const uint64_t *proofs_xy,
+                          const uint8_t *proofs_is_inf, const uint64_t *weights, int *accepted);
+int zkp_kzg_verify_points_dev(const zkp_kzg_point_verifier *v, const void *d_commits_xy, const uint8_t *d_commits_is_inf, size_t n_commits,
+                              size_t n_openings, const uint32_t *commit_index, const void *d_z, const void *d_y, const void *d_proofs_xy,
+                              const uint8_t *d_proofs_is_inf, const void *d_weights, void *stream, int *accepted);
+int zkp_kzg_verify_points_find_bad(const zkp_kzg_point_verifier *v, const uint64_t *commits_xy, const uint8_t *commits_is_inf,
+                                   size_t n_commits, size_t n_openings, const uint32_t *commit_index, const uint64_t *z, const uint64_t *y,
+                                   const uint64_t *proofs_xy, const uint8_t *proofs_is_inf, const uint64_t *weights, int *accepted,
+                                   size_t *first_bad);
+int zkp_kzg_verify_points_find_bad_dev(const zkp_kzg_point_verifier *v, const void *d_commits_xy, const uint8_t *d_commits_is_inf,
+                                       size_t n_commits, size_t n_openings, const uint32_t *commit_index, const void *d_z, const void *d_y,
+                                       const void *d_proofs_xy, const uint8_t *d_proofs_is_inf, const void *d_weights, void *stream,
+                                       int *accepted, size_t *first_bad);
+int zkp_kzg_points_aggregate_dev(const zkp_kzg_point_verifier *v, size_t n_commits, size_t n_openings, const uint32_t *commit_index,
+                                 const void *d_z, const void *d_y, const void *d_weights, void *d_out_commit_weights, void *d_out_rz,
+                                 void *d_out_r, void *d_out_neg_sum, void *stream);
+int zkp_kzg_verify_evals_batch_dev(const zkp_kzg_point_verifier *v, const zkp_kzg_eval_opener *o, const void *d_evals, size_t n_polys,
+                                   const void *d_z, const void *d_commits_xy, const uint8_t *d_commits_is_inf, const void *d_proofs_xy,
+                                   const uint8_t *d_proofs_is_inf, const void *d_weights, void *stream, int *accepted);
 /* Self-test hook for the two device inversions of Fr (csrc/fr_inv.hpp, csrc/plonk.hpp): inverts n elements in device memory, one lane
  * each, 8 x u32 words in and out (the memory form, Montgomery radix 2^256).  method 0: Bernstein-Yang division steps, any value
  * below 2r in; method 1: the Fermat power.  Canonical a^-1 R out; 0 (and r, method 0) map to 0.  At most 2^24 elements. */

@@ -32,6 +32,7 @@
 #include "g1_codec.hpp"
 #include "kzg_recover.hpp"
 #include "kzg_cells.hpp"
+#include "kzg_points.hpp"
 #include "kzg_evals.hpp"
 #include "plonk.hpp"
 #include "nova.hpp"
@@ -1513,4 +1514,5 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "kzg_recover_host.inc"
 #include "kzg_cells_host.inc"
 #include "kzg_evals_host.inc"
+#include "kzg_points_host.inc"
 #include "nova_host.inc"

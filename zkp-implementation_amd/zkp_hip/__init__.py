@@ -115,6 +115,15 @@ _SIGS = {
     "zkp_kzg_open_evals_batch": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_kzg_open_evals_batch_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_kzg_open_evals_field_dev": ([_VP, _VP, _SZ, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_point_verifier_create": ([_VP, _SZ, _SZ, C.POINTER(_VP)], C.c_int),
+    "zkp_kzg_point_verifier_destroy": ([_VP], None),
+    "zkp_kzg_verify_points": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_kzg_verify_points_dev": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _VP, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_kzg_verify_points_find_bad": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _VP, C.POINTER(C.c_int), C.POINTER(_SZ)], C.c_int),
+    "zkp_kzg_verify_points_find_bad_dev": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _VP, _VP, C.POINTER(C.c_int), C.POINTER(_SZ)],
+                                           C.c_int),
+    "zkp_kzg_points_aggregate_dev": ([_VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "zkp_kzg_verify_evals_batch_dev": ([_VP, _VP, _VP, _SZ, _VP, _VP, _U8P, _VP, _U8P, _VP, _VP, C.POINTER(C.c_int)], C.c_int),
     "zkp_selftest_fq28_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_fr29_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_fp_dev": ([C.c_int, C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
@@ -1504,6 +1513,26 @@ class KzgScheme:
             weights = _fr_mont_rows([secrets.randbits(128) for _ in range(cells)])
         return kept[1].verify(commitments, ci, coset_index, evals, proofs, weights)
 
+    def verify_points(self, g2s_xy, commitments, zs, ys, proofs, commit_index=None, weights=None):
+        """Point openings (open, open_all, open_evals_batch) of any of `commitments` in one pairing check: KzgPointVerifier.verify
+        (one verifier is kept and grows with the batch).  commit_index None: opening i belongs to commitment i, the shape of
+        kzg_batch_verify.  weights=None draws a 128-bit weight per opening from `secrets`, the counterpart of
+        Fr::from(rng.gen::<u128>()) in kzg/src/scheme.rs:215-245; pass weights only to reproduce a run."""
+        count, commits = _points(proofs)[0].shape[0], _points(commitments)[0].shape[0]
+        g2 = _np(g2s_xy, np.uint64).reshape(24)
+        kept = getattr(self, "_point_verifier", None)
+        if kept is None or kept[0] != g2.tobytes() or kept[1].max_openings < count or kept[1].max_commits < commits:
+            room = (max(count, 1), max(commits, 1))
+            if kept is not None:  # (grows in either capacity, shrinks in neither)
+                room = (max(room[0], kept[1].max_openings), max(room[1], kept[1].max_commits))
+                kept[1].close()
+            from .kzg_points import KzgPointVerifier  # (that module imports this one)
+            kept = self._point_verifier = (g2.tobytes(), KzgPointVerifier(g2, *room))
+        if weights is None:
+            import secrets
+            weights = _fr_mont_rows([secrets.randbits(128) for _ in range(count)])
+        return kept[1].verify(commitments, zs, ys, proofs, weights, commit_index=commit_index)
+
     def _eval_opener(self, log_n, bitrev, polys):
         """The opener kept per (log_n, bitrev), replaced by a larger one when a batch outgrows it; the Lagrange basis is kept per log_n"""
         from .kzg_evals import KzgEvalOpener  # (that module imports this one)
@@ -1536,6 +1565,9 @@ class KzgScheme:
             op.close()
         for op in list(self._eval_openers.values()) + list(self._lagrange.values()):  # (the openers borrow the bases: they go first)
             op.close()
+        kept, self._point_verifier = getattr(self, "_point_verifier", None), None  # (verify_points)
+        if kept is not None:
+            kept[1].close()
         self._eval_openers = {}
         self._lagrange = {}
         self._cell_verifiers = {}
