@@ -644,6 +644,67 @@ int zkp_kzg_points_aggregate_dev(const zkp_kzg_point_verifier *v, size_t n_commi
 int zkp_kzg_verify_evals_batch_dev(const zkp_kzg_point_verifier *v, const zkp_kzg_eval_opener *o, const void *d_evals, size_t n_polys,
                                    const void *d_z, const void *d_commits_xy, const uint8_t *d_commits_is_inf, const void *d_proofs_xy,
                                    const uint8_t *d_proofs_is_inf, const void *d_weights, void *stream, int *accepted);
+
+/* ---- Pairing-product checks on the GPU: many independent checks per launch, a verdict byte per check (csrc/pairing.hpp).
+ * Every verifier above ends in ONE pairing check on the host; a verdict per item -- which openings of a rejected batch are bad,
+ * which of many independent proofs fail -- is thousands of independent checks, one lane each here.  Check c is accepted iff
+ * prod_j e(P[c][j], Q_j) == 1 over k FIXED G2 points Q_j (G_2, [s]_2, ...): their Miller walks are done once, on the host, at
+ * creation (68 line steps per point, 13056 bytes), so the device does no G2 arithmetic.  Two kernels: the Miller product of a
+ * check (its k Miller functions share their squarings), then the final exponentiation E(f) = f^(3 (p^12 - 1) / r) by the x-chain.
+ * THE VALUE IS THE CUBE OF zkp_pairing's (gcd(3, r) = 1: E == 1 iff the canonical pairing product is 1, so every verdict is the
+ * canonical one; zkp_pairing keeps the plain exponent and its pinned value).  One lane per check: a single device check is slower
+ * than the host's (profiles/pairing_dev.md) and the verifiers above keep their host check -- this is for many checks at once.
+ * zkp_pairing_checker_create: k in 1 .. 8 (else ZKP_E_ARG), each point validated as [s]_2 is everywhere (canonical, on the twist,
+ * in G2: ZKP_E_ARG naming the slot) unless g2_is_inf (nullable, k flags) marks it as the identity; max_checks in 1 .. 2^24.  The
+ * checker lives on the slot current at creation and owns the prepared lines and 576 bytes per check; a workspace that does not
+ * fit is ZKP_E_NOMEM with the sizes in zkp_last_error() and nothing left allocated.
+ * zkp_pairing_check_batch_dev: d_p_xy holds n_checks x k x 12 limbs (check-major), d_p_is_inf (nullable) n_checks x k flags.  A
+ * pair whose P is the identity, or whose Q was created as the identity, contributes nothing (a check with no live pair is
+ * accepted).  validate != 0 runs the kernels of zkp_g1_validate over all n_checks x k points first and synchronises: a bad point
+ * is ZKP_E_ARG and zkp_last_error() names the lowest flat index, its check and pair, and the status word "canonical", "curve" or
+ * "subgroup".  validate == 0: garbage in, garbage verdict, never a fault (no index and no trip count depends on the data).
+ * d_ok (n_checks bytes, 1 / 0) and d_out_fq12 (n_checks x 72 limbs: E in zkp_pairing's memory order, canonical residues) are
+ * each nullable, not both.  Does not synchronise unless validate != 0; allocates nothing.  n_checks == 0 does nothing;
+ * n_checks > max_checks is ZKP_E_SIZE.  While profiling is on a call records "pairing_miller" and "pairing_final_exp".
+ * zkp_pairing_check_batch: the same from host arrays through the slot's staging buffer; blocks. */
+typedef struct zkp_pairing_checker zkp_pairing_checker;
+int zkp_pairing_checker_create(const uint64_t *g2_xy /* k x 24 */, const uint8_t *g2_is_inf, size_t k, size_t max_checks,
+                               zkp_pairing_checker **out);
+void zkp_pairing_checker_destroy(zkp_pairing_checker *c);
+int zkp_pairing_check_batch_dev(const zkp_pairing_checker *c, const void *d_p_xy, const uint8_t *d_p_is_inf, size_t n_checks,
+                                int validate, uint8_t *d_ok, void *d_out_fq12, void *stream);
+int zkp_pairing_check_batch(const zkp_pairing_checker *c, const uint64_t *p_xy, const uint8_t *p_is_inf, size_t n_checks, int validate,
+                            uint8_t *ok, uint64_t *out_fq12);
+/* A verdict PER OPENING on the point verifier: the arguments of zkp_kzg_verify_points without weights.  ok[i] = 1 iff opening i alone
+ * verifies,  e(C_m(i) + [z_i]W_i - [y_i]G, G_2) * e(-W_i, [s]_2) == 1;  *n_bad (nullable) receives the number of zeros.  One lane per
+ * opening forms the left point (two variable-base multiplications by the lane routine of zkp_g1_scale_dev, complete additions, one
+ * inversion per lane) and the verifier's own pairing checker over (G_2, [s]_2) judges every pair; that checker and a workspace of
+ * about 1 KiB per opening are made on the FIRST call, so creating a verifier costs what it did, and the workspace grows with the
+ * largest call (ZKP_E_NOMEM with the sizes when it does not fit).  No value visits the host before the verdict bytes.  The points
+ * are validated as zkp_kzg_verify_points validates them (a bad point: ZKP_E_ARG naming the array, the lowest index and the status
+ * word) and the refusals are the same; more than 2^24 openings in one call is ZKP_E_SIZE.  n_openings == 0 touches nothing
+ * (*n_bad = 0).  Both forms BLOCK (the count comes back); in the _dev form everything but commit_index (host) is memory of the
+ * verifier's device and d_ok receives n_openings bytes.  While profiling is on a call records "kzg_each_points", "pairing_miller"
+ * and "pairing_final_exp". */
+int zkp_kzg_verify_points_each(const zkp_kzg_point_verifier *v, const uint64_t *commits_xy, const uint8_t *commits_is_inf,
+                               size_t n_commits, size_t n_openings, const uint32_t *commit_index, const uint64_t *z, const uint64_t *y,
+                               const uint64_t *proofs_xy, const uint8_t *proofs_is_inf, uint8_t *ok, size_t *n_bad);
+int zkp_kzg_verify_points_each_dev(const zkp_kzg_point_verifier *v, const void *d_commits_xy, const uint8_t *d_commits_is_inf,
+                                   size_t n_commits, size_t n_openings, const uint32_t *commit_index, const void *d_z, const void *d_y,
+                                   const void *d_proofs_xy, const uint8_t *d_proofs_is_inf, uint8_t *d_ok, size_t *n_bad, void *stream);
+/* How many host pairing checks have ended in the x-chain final exponentiation (out[0]) and in the plain power (out[1]) since the
+ * library was loaded: what ZKP_PAIRING_FINAL_EXP chose, for the test suite. */
+int zkp_selftest_final_exp_counts(uint64_t out[2]);
+/* Self-test hooks for the device tower under the checks (csrc/pairing_tower.hpp over the saturated Fq), one lane per case, raw ABI
+ * limbs in and out: d_a, d_b and d_out hold n x 72 limbs (an Fq12 in zkp_pairing's memory order, canonical residues); d_out must not
+ * be an operand.  op: 0 a * b, 1 a^2, 2 the sparse product a * line with the line read from b as (A, B, C) = (b.c0.c0, b.c0.c1,
+ * b.c1.c1.c0), 3 1 / a (0 -> 0), 4 / 5 / 6 the Frobenius maps a^p, a^(p^2), a^(p^3), 7 Granger-Scott cyclotomic squaring (the square
+ * only inside the cyclotomic subgroup), 8 E(a).  d_b is read by 0 and 2 only.  At most 2^24 cases.
+ * zkp_selftest_miller_dev: the value of the Miller kernel BEFORE the final exponentiation, n_checks x 72 limbs: bit for bit the
+ * product over j of the model's miller_loop(P[c][j], Q_j).  Arguments as zkp_pairing_check_batch_dev. */
+int zkp_selftest_fq12_dev(int op, const void *d_a, const void *d_b, size_t n, void *d_out, void *stream);
+int zkp_selftest_miller_dev(const zkp_pairing_checker *c, const void *d_p_xy, const uint8_t *d_p_is_inf, size_t n_checks,
+                            void *d_out_fq12, void *stream);
 /* Self-test hook for the two device inversions of Fr (csrc/fr_inv.hpp, csrc/plonk.hpp): inverts n elements in device memory, one lane
  * each, 8 x u32 words in and out (the memory form, Montgomery radix 2^256).  method 0: Bernstein-Yang division steps, any value
  * below 2r in; method 1: the Fermat power.  Canonical a^-1 R out; 0 (and r, method 0) map to 0.  At most 2^24 elements. */

@@ -28,6 +28,7 @@ pub const ZKP_KZG_ORDER_BITREV: i32 = 1;
 #[repr(C)] pub struct zkp_kzg_cell_verifier { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_kzg_eval_opener { _private: [u8; 0] }
 #[repr(C)] pub struct zkp_kzg_point_verifier { _private: [u8; 0] }
+#[repr(C)] pub struct zkp_pairing_checker { _private: [u8; 0] }
 
 /// how a bases handle is expanded (zkp_g1_bases_expansion); all zero when it is not
 #[repr(C)]
@@ -274,6 +275,15 @@ extern "C" {
     pub fn zkp_kzg_verify_points_find_bad_dev(v: *const zkp_kzg_point_verifier, d_commits_xy: *const c_void, d_commits_is_inf: *const u8, n_commits: usize, n_openings: usize, commit_index: *const u32, d_z: *const c_void, d_y: *const c_void, d_proofs_xy: *const c_void, d_proofs_is_inf: *const u8, d_weights: *const c_void, stream: *mut c_void, accepted: *mut i32, first_bad: *mut usize) -> i32;
     pub fn zkp_kzg_points_aggregate_dev(v: *const zkp_kzg_point_verifier, n_commits: usize, n_openings: usize, commit_index: *const u32, d_z: *const c_void, d_y: *const c_void, d_weights: *const c_void, d_out_commit_weights: *mut c_void, d_out_rz: *mut c_void, d_out_r: *mut c_void, d_out_neg_sum: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_kzg_verify_evals_batch_dev(v: *const zkp_kzg_point_verifier, o: *const zkp_kzg_eval_opener, d_evals: *const c_void, n_polys: usize, d_z: *const c_void, d_commits_xy: *const c_void, d_commits_is_inf: *const u8, d_proofs_xy: *const c_void, d_proofs_is_inf: *const u8, d_weights: *const c_void, stream: *mut c_void, accepted: *mut i32) -> i32;
+    pub fn zkp_pairing_checker_create(g2_xy: *const u64, g2_is_inf: *const u8, k: usize, max_checks: usize, out: *mut *mut zkp_pairing_checker) -> i32;
+    pub fn zkp_pairing_checker_destroy(c: *mut zkp_pairing_checker);
+    pub fn zkp_pairing_check_batch_dev(c: *const zkp_pairing_checker, d_p_xy: *const c_void, d_p_is_inf: *const u8, n_checks: usize, validate: i32, d_ok: *mut u8, d_out_fq12: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_pairing_check_batch(c: *const zkp_pairing_checker, p_xy: *const u64, p_is_inf: *const u8, n_checks: usize, validate: i32, ok: *mut u8, out_fq12: *mut u64) -> i32;
+    pub fn zkp_kzg_verify_points_each(v: *const zkp_kzg_point_verifier, commits_xy: *const u64, commits_is_inf: *const u8, n_commits: usize, n_openings: usize, commit_index: *const u32, z: *const u64, y: *const u64, proofs_xy: *const u64, proofs_is_inf: *const u8, ok: *mut u8, n_bad: *mut usize) -> i32;
+    pub fn zkp_kzg_verify_points_each_dev(v: *const zkp_kzg_point_verifier, d_commits_xy: *const c_void, d_commits_is_inf: *const u8, n_commits: usize, n_openings: usize, commit_index: *const u32, d_z: *const c_void, d_y: *const c_void, d_proofs_xy: *const c_void, d_proofs_is_inf: *const u8, d_ok: *mut u8, n_bad: *mut usize, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_final_exp_counts(out: *mut u64) -> i32;
+    pub fn zkp_selftest_fq12_dev(op: i32, d_a: *const c_void, d_b: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn zkp_selftest_miller_dev(c: *const zkp_pairing_checker, d_p_xy: *const c_void, d_p_is_inf: *const u8, n_checks: usize, d_out_fq12: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_fr_inverse_dev(d_in: *const c_void, n: usize, method: i32, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_g1_mul(base_xy: *const u64, base_is_inf: u8, scalar: *const u64, out_xy: *mut u64, out_is_inf: *mut u8) -> i32;
     pub fn zkp_g1_fixed_base_mul_dev(d_scalars: *const c_void, n: usize, d_out_xy: *mut c_void, d_out_is_inf: *mut u8, stream: *mut c_void) -> i32;

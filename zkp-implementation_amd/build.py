@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libzkp_hip.so")
-SOURCES = ["api.hip", "selftest.hip"]
+SOURCES = ["api.hip", "selftest.hip", "pairing.hip"]
 # what the library is built from: every source file of csrc/ and the public header (paths relative to csrc/)
 DEPS = sorted(f for f in os.listdir(SRC) if f.endswith((".hip", ".hpp", ".inc"))) + [os.path.join("..", "..", "include", "zkp_hip.h")]
 

@@ -33,14 +33,18 @@
 #include "kzg_recover.hpp"
 #include "kzg_cells.hpp"
 #include "kzg_points.hpp"
+#include "kzg_points_each.hpp"
 #include "kzg_evals.hpp"
 #include "plonk.hpp"
 #include "nova.hpp"
 #include "fri.hpp"
 #include "fri_fr.hpp"
 #include "selftest.hpp"
+#include "pairing.hpp"
 #include "transcript_host.hpp"
 #include "pairing_host.hpp"
+#define ZKP_PAIRING_TOWER_HOST
+#include "pairing_tower.hpp"
 
 using namespace zkp;
 using namespace zkp::host;
@@ -1515,4 +1519,5 @@ int zkp_poly_mul_fr(const uint64_t* a, size_t la, const uint64_t* b, size_t lb, 
 #include "kzg_cells_host.inc"
 #include "kzg_evals_host.inc"
 #include "kzg_points_host.inc"
+#include "pairing_host.inc"
 #include "nova_host.inc"

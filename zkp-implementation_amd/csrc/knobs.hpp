@@ -19,6 +19,7 @@ enum Knob {
     KNOB_KZG_COSET_GROUP_LOG, KNOB_KZG_OPENER_MAX_BYTES, KNOB_KZG_RECOVER_LEAF_LOG, KNOB_KZG_RECOVER_MAX_BYTES,
     KNOB_KZG_CELLS_CHUNK_LOG,
     KNOB_KZG_EVALS_INVERSE, KNOB_KZG_EVALS_MAX_BYTES,
+    KNOB_PAIRING_FINAL_EXP,
     KNOB_COUNT
 };
 
@@ -28,7 +29,8 @@ enum KnobForm {
     KNOB_INT_CLAMP,   // the same; outside: the nearer bound
     KNOB_INT_REFUSE,  // the same; outside: the caller refuses the call with ZKP_E_ARG and its own message (the reader hands the value on)
     KNOB_SET,         // flag: on when the variable exists, whatever it holds
-    KNOB_ONE          // flag: on when the value begins with '1'
+    KNOB_ONE,         // flag: on when the value begins with '1'
+    KNOB_WORD         // a choice between words: knob_is(k, word) is true when the value is exactly that word; anything else is the default
 };
 constexpr long long KNOB_COMPUTED = LLONG_MIN;  // the default depends on the problem: the caller passes it to knob_int
 
@@ -113,6 +115,9 @@ constexpr KnobRow kKnobs[KNOB_COUNT] = {
     {KNOB_KZG_EVALS_MAX_BYTES, "ZKP_KZG_EVALS_MAX_BYTES", KNOB_POLICY, KNOB_INT, 0, LLONG_MAX, LLONG_MAX,
      "an evaluation-form opener (zkp_kzg_eval_opener_create) whose device workspace is larger than this is refused with ZKP_E_NOMEM "
      "before anything is allocated"},
+    {KNOB_PAIRING_FINAL_EXP, "ZKP_PAIRING_FINAL_EXP", KNOB_TUNING, KNOB_WORD, 0, 1, 0,
+     "the final exponentiation of the host pairing check every verifier ends in: chain (default) the x-chain of pairing_tower.hpp, "
+     "plain the one 4314-bit power; the verdicts are the same, zkp_pairing's value is always the plain one: profiles/pairing_dev.md"},
 };
 
 constexpr bool knob_rows_in_enum_order() {
@@ -132,6 +137,14 @@ inline long long knob_int(Knob k, long long dflt) {
     return r.form == KNOB_INT_CLAMP ? (v < r.lo ? r.lo : r.hi) : dflt;
 }
 inline long long knob_int(Knob k) { return knob_int(k, kKnobs[k].dflt); }
+
+// A KNOB_WORD knob: set to exactly `word`
+inline bool knob_is(Knob k, const char* word) {
+    const char* e = getenv(kKnobs[k].name);
+    if (!e) return false;
+    while (*e && *e == *word) e++, word++;
+    return *e == 0 && *word == 0;
+}
 
 inline bool knob_flag(Knob k) {
     const char* e = getenv(kKnobs[k].name);

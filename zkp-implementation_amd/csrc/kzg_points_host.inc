@@ -11,6 +11,11 @@ struct zkp_kzg_point_verifier : KzgHandle {  // work: kzg_points_sizes
     KzgPointsSizes sz;
     mutable HostStage stage;                // the table on its way to the device
     mutable std::vector<uint32_t> scratch;  // where the sort counts (host)
+    // zkp_kzg_verify_points_each* (pairing_host.inc): the pairing checker over (G_2, [s]_2) and the workspace of the left points, both
+    // made on first use, so that creating a verifier costs what it did
+    mutable zkp_pairing_checker* each = nullptr;
+    mutable DevBuf each_ws;
+    ~zkp_kzg_point_verifier() { zkp_pairing_checker_destroy(each); }
 };
 
 namespace {

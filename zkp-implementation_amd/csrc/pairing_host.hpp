@@ -178,6 +178,30 @@ inline Fq12 miller_loop(const HFq& px, const HFq& py, bool p_inf, const G2Aff& q
     return f.conj();
 }
 
+// The G2 half of miller_loop done once for a fixed Q (the prepared form of pairing.hpp): the same walk, and per line step -- 63
+// doublings and 5 additions, in the loop's order -- the pair (lambda, lambda x_T - y_T) as 4 Fq = 24 words.  The line at P is then
+// ((a, -x_P lambda, 0), (0, y_P, 0)): no G2 arithmetic and no inversion is left for whoever evaluates it.  q finite.
+constexpr int PREPARED_G2_STEPS = 68, PREPARED_G2_WORDS = 68 * 24;
+inline void prepare_g2_lines(const G2Aff& q, uint64_t out[PREPARED_G2_WORDS]) {
+    const uint64_t X_ABS = 0xd201000000010000ull;
+    const HFq two = HFq::from_u64(2), three = HFq::from_u64(3);
+    G2Aff t = q;
+    uint64_t* o = out;
+    auto emit = [&](const Fq2& lam) {
+        lam.store(o);
+        (lam * t.x - t.y).store(o + 12);
+        o += 24;
+    };
+    for (int b = 62; b >= 0; b--) {
+        emit((t.x * t.x).scale(three) * t.y.scale(two).inverse());
+        t = t.dbl();
+        if ((X_ABS >> b) & 1) {
+            emit((q.y - t.y) * (q.x - t.x).inverse());
+            t = t.add(q);
+        }
+    }
+}
+
 inline Fq12 pairing(const uint64_t p_xy[12], bool p_inf, const G2Aff& q) {
     const HFq px = p_inf ? HFq::zero() : HFq::load(p_xy), py = p_inf ? HFq::zero() : HFq::load(p_xy + 6);
     return final_exponentiation(miller_loop(px, py, p_inf, q));

@@ -46,8 +46,20 @@ int g2_validate(const uint64_t xy[24], const char* what, G2Aff* out) {
     return ZKP_OK;
 }
 
-// e(p1, q1) == e(p2, q2)  <=>  FE(ml(p1, q1) * ml(-p2, q2)) == 1: two Miller loops share ONE final exponentiation (the plain
-// (p^12 - 1) / r power, ~19 ms on the host, dominates a pairing)
+// FE(f) == 1, the question every check ends in.  By default through the tower the device kernels use (pairing_tower.hpp over HFq):
+// E(f) = f^(3 (p^12 - 1) / r) by the x-chain, and E(f) == 1 iff FE(f) == 1 because gcd(3, r) = 1.  ZKP_PAIRING_FINAL_EXP=plain keeps
+// the one (p^12 - 1) / r power (~19 ms on the host, what used to dominate a check); zkp_pairing always uses that one, its VALUE is pinned.
+std::atomic<uint64_t> g_final_exp_runs[2];  // [0] the x-chain, [1] the plain power: what zkp_selftest_final_exp_counts reports
+bool final_exp_is_one(const Fq12& f) {
+    const bool plain = knob_is(KNOB_PAIRING_FINAL_EXP, "plain");
+    g_final_exp_runs[plain ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+    if (plain) return final_exponentiation(f) == Fq12::one();
+    uint64_t w[72];
+    f.store(w);
+    return tower::f12_is_one(tower::final_exp(tower::f12_load(w)));
+}
+
+// e(p1, q1) == e(p2, q2)  <=>  FE(ml(p1, q1) * ml(-p2, q2)) == 1: two Miller loops share ONE final exponentiation
 bool pairings_equal(const HXyzz& p1, const G2Aff& q1, const HXyzz& p2, const G2Aff& q2) {
     uint64_t a[12], b[12];
     uint8_t ai = 0, bi = 0;
@@ -55,12 +67,18 @@ bool pairings_equal(const HXyzz& p1, const G2Aff& q1, const HXyzz& p2, const G2A
     p2.negate().to_affine(b, &bi);
     const Fq12 f = miller_loop(ai ? HFq::zero() : HFq::load(a), ai ? HFq::zero() : HFq::load(a + 6), ai != 0, q1) *
                    miller_loop(bi ? HFq::zero() : HFq::load(b), bi ? HFq::zero() : HFq::load(b + 6), bi != 0, q2);
-    return final_exponentiation(f) == Fq12::one();
+    return final_exp_is_one(f);
 }
 
 }  // namespace
 
 extern "C" {
+
+int zkp_selftest_final_exp_counts(uint64_t out[2]) try {
+    if (!out) return fail(ZKP_E_ARG, "null argument");
+    for (int i = 0; i < 2; i++) out[i] = g_final_exp_runs[i].load(std::memory_order_relaxed);
+    return ZKP_OK;
+} ZKP_CATCH_INT
 
 int zkp_g2_generator(uint64_t out_xy[24]) try {
     if (!out_xy) return fail(ZKP_E_ARG, "null argument");

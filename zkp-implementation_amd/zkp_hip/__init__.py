@@ -124,6 +124,15 @@ _SIGS = {
                                            C.c_int),
     "zkp_kzg_points_aggregate_dev": ([_VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
     "zkp_kzg_verify_evals_batch_dev": ([_VP, _VP, _VP, _SZ, _VP, _VP, _U8P, _VP, _U8P, _VP, _VP, C.POINTER(C.c_int)], C.c_int),
+    "zkp_pairing_checker_create": ([_VP, _U8P, _SZ, _SZ, C.POINTER(_VP)], C.c_int),
+    "zkp_pairing_checker_destroy": ([_VP], None),
+    "zkp_pairing_check_batch_dev": ([_VP, _VP, _U8P, _SZ, C.c_int, _U8P, _VP, _VP], C.c_int),
+    "zkp_pairing_check_batch": ([_VP, _VP, _U8P, _SZ, C.c_int, _U8P, _VP], C.c_int),
+    "zkp_kzg_verify_points_each": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _U8P, C.POINTER(_SZ)], C.c_int),
+    "zkp_kzg_verify_points_each_dev": ([_VP, _VP, _U8P, _SZ, _SZ, _VP, _VP, _VP, _VP, _U8P, _U8P, C.POINTER(_SZ), _VP], C.c_int),
+    "zkp_selftest_final_exp_counts": ([_VP], C.c_int),
+    "zkp_selftest_fq12_dev": ([C.c_int, _VP, _VP, _SZ, _VP, _VP], C.c_int),
+    "zkp_selftest_miller_dev": ([_VP, _VP, _U8P, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_fq28_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_fr29_dev": ([C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
     "zkp_selftest_fp_dev": ([C.c_int, C.c_int, _VP, _SZ, _VP, _VP], C.c_int),
@@ -1532,6 +1541,21 @@ class KzgScheme:
             import secrets
             weights = _fr_mont_rows([secrets.randbits(128) for _ in range(count)])
         return kept[1].verify(commitments, zs, ys, proofs, weights, commit_index=commit_index)
+
+    def verify_points_each(self, g2s_xy, commitments, zs, ys, proofs, commit_index=None):
+        """A verdict per opening (KzgPointVerifier.verify_each over the verifier verify_points keeps): -> (ok (n_openings,) uint8,
+        n_bad).  ok[i] = 1 iff opening i alone verifies; no weights, every opening gets its own pairing check on the device."""
+        count, commits = _points(proofs)[0].shape[0], _points(commitments)[0].shape[0]
+        g2 = _np(g2s_xy, np.uint64).reshape(24)
+        kept = getattr(self, "_point_verifier", None)
+        if kept is None or kept[0] != g2.tobytes() or kept[1].max_openings < count or kept[1].max_commits < commits:
+            room = (max(count, 1), max(commits, 1))
+            if kept is not None:
+                room = (max(room[0], kept[1].max_openings), max(room[1], kept[1].max_commits))
+                kept[1].close()
+            from .kzg_points import KzgPointVerifier
+            kept = self._point_verifier = (g2.tobytes(), KzgPointVerifier(g2, *room))
+        return kept[1].verify_each(commitments, zs, ys, proofs, commit_index=commit_index)
 
     def _eval_opener(self, log_n, bitrev, polys):
         """The opener kept per (log_n, bitrev), replaced by a larger one when a batch outgrows it; the Lagrange basis is kept per log_n"""

@@ -87,6 +87,36 @@ class KzgPointVerifier(_Handle):
         _chk(lib().zkp_kzg_verify_points_find_bad_dev(*args, C.byref(acc), C.byref(bad)))
         return None if acc.value else int(bad.value)
 
+    def verify_each(self, commitments, zs, ys, proofs, commit_index=None):
+        """zkp_kzg_verify_points_each: a verdict per opening, no weights -> (ok (n_openings,) uint8, n_bad).  ok[i] = 1 iff opening i
+        alone verifies.  Blocks."""
+        ci = self._index(commit_index)
+        (cxy, cinf), (pxy, pinf) = _points(commitments), _points(proofs)
+        count = pxy.shape[0]
+        if ci is not None and ci.shape[0] != count:
+            raise ZkpError(ZKP_E_ARG, "one proof per opening")
+        z, y = _np(zs, np.uint64, (count, 4)), _np(ys, np.uint64, (count, 4))
+        ok, bad = np.zeros(count, dtype=np.uint8), C.c_size_t(0)
+        _chk(lib().zkp_kzg_verify_points_each(self._h, _ptr(cxy), _ptr(cinf), cxy.shape[0], count, _ptr(ci), _ptr(z), _ptr(y), _ptr(pxy), _ptr(pinf),
+                                              _ptr(ok), C.byref(bad)))
+        return ok, int(bad.value)
+
+    def verify_each_dev(self, commits_tensor, n_commits, n_openings, z_tensor, y_tensor, proofs_tensor, ok_tensor, commit_index=None,
+                        commits_inf_tensor=None, proofs_inf_tensor=None, stream=None):
+        """The same with everything but the index vector (host) resident on the verifier's device: ok_tensor receives n_openings
+        bytes -> n_bad.  Blocks."""
+        ci = self._index(commit_index)
+        if ci is not None and ci.shape[0] != n_openings:
+            raise ZkpError(ZKP_E_ARG, "one index per opening")
+        cinf = _dev_ptr(commits_inf_tensor, n_commits) if commits_inf_tensor is not None else None
+        pinf = _dev_ptr(proofs_inf_tensor, n_openings) if proofs_inf_tensor is not None else None
+        bad = C.c_size_t(0)
+        _chk(lib().zkp_kzg_verify_points_each_dev(self._h, _dev_ptr(commits_tensor, 96 * n_commits), cinf, n_commits, n_openings, _ptr(ci),
+                                                  _dev_ptr(z_tensor, 32 * n_openings), _dev_ptr(y_tensor, 32 * n_openings),
+                                                  _dev_ptr(proofs_tensor, 96 * n_openings), pinf, _dev_ptr(ok_tensor, n_openings), C.byref(bad),
+                                                  _stream_ptr(stream)))
+        return int(bad.value)
+
     def verify_bytes(self, commitments48, zs32, ys32, proofs48, weights, commit_index=None, big_endian=True):
         """The wire form: commitments48 (n_commits x 48) and proofs48 (n_openings x 48) compressed points, zs32 and ys32 n_openings x 32
         bytes of canonical scalars (big-endian unless told otherwise), weights (n_openings, 4) limbs as in verify -> accepted.
