@@ -834,6 +834,56 @@ int zkp_selftest_msm_sort_dev(const zkp_bases *bases, const void *const *d_scala
  * is not reported here. */
 int zkp_selftest_msm_sort_bits_dev(const zkp_bases *bases, const void *const *d_scalars, size_t count, size_t n, size_t range_index,
                                    unsigned bits, void *stream, zkp_msm_sort_geometry *geom, const zkp_msm_sort_outputs *out);
+/* Self-test hook for the MSM's bucket reduction (csrc/msm.hpp: msm_combine, msm_fold_parts, msm_fold_parts_lane, msm_pyramid,
+ * msm_pyramid_quad, msm_pyramid_tail, msm_collect).  No bases, no scalars, no sort: the caller names the window width c (2..24), the
+ * bucket sets nwin and split_log (0..2) and supplies the bucket contents; the hook runs, on the workspaces of device slot `slot` (< 0: the
+ * thread's), what an MSM runs behind its accumulate, through the launch functions and plans the MSM itself uses (plan_fold, plan_reduce, the
+ * combine grid of acc_launch): the combine if in->d_over is given, the fold steps, the reduction.  It zeroes the barrier counters of the
+ * last-levels launch, which the sort does in an MSM.  Before the caller's data goes in, the second pyramid buffer, both odd buffers, the pinned
+ * result and whatever the bucket workspace holds past nwin sets are filled with 0xFF bytes, so that a result that read an entry no launch wrote
+ * is no stored point.  Layouts, with nb = 2^(c-1), cap = nwin x nb, a point = 64 words (X, Y, ZZ, ZZZ of 16 words each, csrc/g1_28.hpp):
+ *   plane-major  16 planes of cap uint4; bucket b = 1..nb of set w is entry w nb + pyr_pos(b - 1, nb), pyr_pos(i, n) = (i >> 1) + (i & 1)(n >> 1)
+ *   entry-major  64 consecutive words per point
+ *   d_buckets    plane-major, cap entries                       d_parts    2^split_log - 1 such arrays back to back (NULL for split_log 0)
+ *   d_over       nwin x 2: {candidates, pieces} per set         d_over_b   nwin x over_cap: the bucket id of candidate r
+ *   d_over_off   nwin x (over_cap + 1): first piece of candidate r, [candidates] = pieces; a candidate with no piece is left alone
+ *   d_pieces     entry-major, nwin x desc_cap                   d_carry    entry-major, cap entries at the buckets' positions (resume only)
+ * resume != 0: the combine adds the carry entry to a combined bucket.  more != 0: it writes the combined buckets to the hand-over array (entry-
+ * major, cap entries) instead of the buckets; the hook then stops, copies that array to d_out_carry and leaves out_results / out_flags alone.
+ * d_out_buckets (nullable): the bucket array behind combine and fold, before the first pyramid launch.  out_results (host): nwin x c points
+ * entry-major, [w][0] = the sum of the set's buckets, [w][1 + j] = U_j = the sum of the buckets whose 0-based index has bit j set;
+ * out_flags (host): nwin words, a set's barrier counter as the last-levels launch left it -- tail_blocks arrivals for each of its c - 1 - nlevel
+ * levels, bit 31 set when a workgroup gave up waiting -- and 0 from msm_collect.  *geom receives the shape of every launch and the words of every
+ * buffer.  out_results == NULL: only *geom is filled and nothing is launched.  Returns after the results have arrived (more: after the stream
+ * has finished); ZKP_E_DEVICE when the last-levels launch timed out, as the MSM reports it.  With a combine block the hook first waits for
+ * `stream` and reads d_over and d_over_b back: more candidates than over_cap or a bucket id outside 1..nb is refused, not launched.
+ * Refused (ZKP_E_ARG): null in / geom, c outside 2..24, nwin outside 1..65535 or cap >= 2^31, split_log > 2, a null or too-small buffer, d_over
+ * with over_cap 0 or desc_cap 0 or nwin times either >= 2^24, resume / more without d_over, a ZKP_PYR_TAIL_* knob out of range (before
+ * anything is enqueued).  Not part of the hot path
+ * (tests/test_gpu_msm_reduce.py, tests/model/msm_reduce_model.py). */
+typedef struct { uint32_t level, half, quad, grid_x; } zkp_msm_reduce_level;  /* grid (grid_x, level + 1, nwin); quad: four lanes per add */
+typedef struct { uint32_t pairs, lane, grid_x; } zkp_msm_fold_step;           /* grid (grid_x, pairs); lane: one lane per add, else four */
+typedef struct {
+    uint32_t c, nwin, nb, split_log;
+    uint32_t tail_max_waves;             /* waves of the last-levels launch this device keeps resident */
+    uint32_t nlevel, tail_blocks, tail_threads;  /* levels 0..nlevel-1 as own launches, then (tail_blocks, nwin) x tail_threads; 0: msm_collect */
+    uint32_t combine_x, over_cap, desc_cap, reserved;  /* combine grid (combine_x, nwin); 0 without a combine block */
+    uint64_t cap;
+    zkp_msm_reduce_level level[24];
+    zkp_msm_fold_step fold[2];
+    uint64_t bucket_words, parts_words, over_words, over_b_words, over_off_words, pieces_words, carry_words, result_words, flag_words;
+} zkp_msm_reduce_geometry;
+typedef struct {
+    uint32_t c, nwin, split_log;
+    uint32_t over_cap, desc_cap, resume, more, reserved;
+    const void *d_buckets, *d_parts, *d_over, *d_over_b, *d_over_off, *d_pieces, *d_carry;
+    size_t buckets_words, parts_words, over_words, over_b_words, over_off_words, pieces_words, carry_words;  /* 32-bit words of each */
+    void *d_out_buckets, *d_out_carry;
+    size_t out_buckets_words, out_carry_words;
+    uint32_t *out_results, *out_flags;
+    size_t out_results_words, out_flags_words;
+} zkp_msm_reduce_io;
+int zkp_selftest_msm_reduce_dev(int slot, const zkp_msm_reduce_io *in, void *stream, zkp_msm_reduce_geometry *geom);
 /* [s^i]G for i < n into host memory (kzg/src/srs.rs:48-63: n = circuit_size + 3). */
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t *out_xy);
 

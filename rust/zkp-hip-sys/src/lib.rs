@@ -92,6 +92,89 @@ pub struct zkp_msm_sort_outputs {
     pub words: [usize; ZKP_SORT_OUTPUTS],
 }
 
+/// one pyramid launch of the bucket reduction: grid (grid_x, level + 1, nwin); quad: four lanes per add
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct zkp_msm_reduce_level {
+    pub level: u32,
+    pub half: u32,
+    pub quad: u32,
+    pub grid_x: u32,
+}
+
+/// one fold step: grid (grid_x, pairs); lane: one lane per add, else four
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct zkp_msm_fold_step {
+    pub pairs: u32,
+    pub lane: u32,
+    pub grid_x: u32,
+}
+
+/// the launches and buffer sizes (32-bit words) of zkp_selftest_msm_reduce_dev
+#[repr(C)]
+pub struct zkp_msm_reduce_geometry {
+    pub c: u32,
+    pub nwin: u32,
+    pub nb: u32,
+    pub split_log: u32,
+    pub tail_max_waves: u32,
+    pub nlevel: u32,
+    pub tail_blocks: u32,
+    pub tail_threads: u32,
+    pub combine_x: u32,
+    pub over_cap: u32,
+    pub desc_cap: u32,
+    pub reserved: u32,
+    pub cap: u64,
+    pub level: [zkp_msm_reduce_level; 24],
+    pub fold: [zkp_msm_fold_step; 2],
+    pub bucket_words: u64,
+    pub parts_words: u64,
+    pub over_words: u64,
+    pub over_b_words: u64,
+    pub over_off_words: u64,
+    pub pieces_words: u64,
+    pub carry_words: u64,
+    pub result_words: u64,
+    pub flag_words: u64,
+}
+
+/// the caller's buffers for zkp_selftest_msm_reduce_dev and their capacities in 32-bit words
+#[repr(C)]
+pub struct zkp_msm_reduce_io {
+    pub c: u32,
+    pub nwin: u32,
+    pub split_log: u32,
+    pub over_cap: u32,
+    pub desc_cap: u32,
+    pub resume: u32,
+    pub more: u32,
+    pub reserved: u32,
+    pub d_buckets: *const c_void,
+    pub d_parts: *const c_void,
+    pub d_over: *const c_void,
+    pub d_over_b: *const c_void,
+    pub d_over_off: *const c_void,
+    pub d_pieces: *const c_void,
+    pub d_carry: *const c_void,
+    pub buckets_words: usize,
+    pub parts_words: usize,
+    pub over_words: usize,
+    pub over_b_words: usize,
+    pub over_off_words: usize,
+    pub pieces_words: usize,
+    pub carry_words: usize,
+    pub d_out_buckets: *mut c_void,
+    pub d_out_carry: *mut c_void,
+    pub out_buckets_words: usize,
+    pub out_carry_words: usize,
+    pub out_results: *mut u32,
+    pub out_flags: *mut u32,
+    pub out_results_words: usize,
+    pub out_flags_words: usize,
+}
+
 /// ZKP_G1_DECODE_SUBGROUP: run the subgroup test of zkp_g1_validate while decoding
 pub const ZKP_G1_DECODE_SUBGROUP: u32 = 1;
 
@@ -301,6 +384,7 @@ extern "C" {
     pub fn zkp_selftest_poly_lincomb_dev(terms: usize, d_p: *const *const c_void, len: *const usize, s: *const u64, n_out: usize, d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_poly_trim_len_dev(d_c: *const c_void, n: usize, out_len: *mut usize, stream: *mut c_void) -> i32;
     pub fn zkp_selftest_msm_sort_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, range_index: usize, stream: *mut c_void, geom: *mut zkp_msm_sort_geometry, out: *const zkp_msm_sort_outputs) -> i32;
+    pub fn zkp_selftest_msm_reduce_dev(slot: i32, r#in: *const zkp_msm_reduce_io, stream: *mut c_void, geom: *mut zkp_msm_reduce_geometry) -> i32;
     pub fn zkp_selftest_msm_sort_bits_dev(bases: *const zkp_bases, d_scalars: *const *const c_void, count: usize, n: usize, range_index: usize, bits: u32, stream: *mut c_void, geom: *mut zkp_msm_sort_geometry, out: *const zkp_msm_sort_outputs) -> i32;
     pub fn zkp_srs_g1(secret: *const u64, n: usize, out_xy: *mut u64) -> i32;
     pub fn zkp_ntt_fr(data: *mut u64, log_n: u32, inverse: i32, coset: *const u64) -> i32;

@@ -1373,6 +1373,13 @@ int zkp_selftest_msm_sort_bits_dev(const zkp_bases* bases, const void* const* d_
                              geom, out, bits);
 } ZKP_CATCH_INT
 
+int zkp_selftest_msm_reduce_dev(int slot, const zkp_msm_reduce_io* in, void* stream, zkp_msm_reduce_geometry* geom) try {
+    if (!in || !geom) return fail(ZKP_E_ARG, "null argument");
+    CTX_ENTER(slot);
+    WsOrder ord(reinterpret_cast<hipStream_t>(stream));
+    return msm_reduce_selftest(*in, reinterpret_cast<hipStream_t>(stream), geom);
+} ZKP_CATCH_INT
+
 int zkp_srs_g1(const uint64_t secret[4], size_t n, uint64_t* out_xy) try {
     if (!secret || (n && !out_xy)) return fail(ZKP_E_ARG, "null argument");
     if (!n) return ZKP_OK;

@@ -139,7 +139,14 @@ struct MsmPass {
                 HIPCHK(hipEventRecord(cx.ev_sort[par], sst));
                 HIPCHK(hipStreamWaitEvent(st, cx.ev_sort[par], 0));
             }
-            launch_accumulate(rb, r);
+            {
+                ProfScope ps("msm_accumulate", st, true);
+                const AccLaunch a = acc_launch(p, r.g);
+                launch_accumulate(rb, r, a);
+                launch_combine(rb, r.g, a);
+                MSM_TRACE(st, r.ridx, "combine");
+                launch_fold(r.g);
+            }
             if (p.overlap) HIPCHK(hipEventRecord(cx.ev_acc[par], st));
         }
         return ZKP_OK;
@@ -188,11 +195,11 @@ struct MsmPass {
         MSM_TRACE(sst, r.ridx, "order");
     }
 
-    // Accumulate the sorted range r into the buckets, combine the pieces of oversized buckets, fold split runs
-    void launch_accumulate(const RangeBuffers& rb, const MsmRange& r) {
-        ProfScope ps("msm_accumulate", st, true);
+    // Accumulate the sorted range r into the buckets (a = acc_launch(p, r.g)); then launch_combine adds up the pieces of oversized
+    // buckets and launch_fold the parts of split runs.  walk() calls the three in this order; the self-test hook of the reduction
+    // (msm_reduce_selftest) calls the last two on bucket contents of its caller's.
+    void launch_accumulate(const RangeBuffers& rb, const MsmRange& r, const AccLaunch& a) {
         const MsmGeom& g = r.g;
-        const AccLaunch a = acc_launch(p, g);
         const uint4* xy = static_cast<const uint4*>(bases->d_xy.p) + r.off * 8;
         uint4 *buckets = cx.buckets.get(), *pieces = cx.pieces.get(), *parts = cx.parts.get(), *carry = cx.pyr1.get();
         if (a.quad)
@@ -202,12 +209,17 @@ struct MsmPass {
             hipLaunchKernelGGL(msm_accumulate_kernel, dim3(a.grid), dim3(ACC_THREADS), 0, st, xy, rb.sorted, rb.start, rb.perm, rb.over, rb.desc,
                                p.desc_cap, a.bucket_blocks, a.extra_blocks, g, buckets, pieces, parts, carry, clk_record(CLK_MSM_ACCUMULATE));
         MSM_TRACE(st, r.ridx, "accumulate");
+    }
+    // One wave per oversized bucket adds its pieces up: into the bucket, or (g.more) into the hand-over array, which is pyr1
+    void launch_combine(const RangeBuffers& rb, const MsmGeom& g, const AccLaunch& a) {
         hipLaunchKernelGGL(msm_combine_kernel, dim3(a.combine_x, g.nwin), dim3(64), 0, st, rb.over, rb.over_b,
-                           rb.over_off, p.over_cap, p.desc_cap, g, pieces, buckets, carry);
-        MSM_TRACE(st, r.ridx, "combine");
-        for (uint32_t t = 0; t < g.split_log; t++)  // buckets += parts, pairwise (the steps: plan_msm)
+                           rb.over_off, p.over_cap, p.desc_cap, g, cx.pieces.get(), cx.buckets.get(), cx.pyr1.get());
+    }
+    // buckets += parts, pairwise (the steps: plan_fold)
+    void launch_fold(const MsmGeom& g) {
+        for (uint32_t t = 0; t < g.split_log; t++)
             hipLaunchKernelGGL(p.fold[t].lane ? msm_fold_parts_lane_kernel : msm_fold_parts_kernel, dim3(p.fold[t].grid_x, p.fold[t].pairs),
-                               dim3(MSM_THREADS), 0, st, buckets, parts, (uint64_t)g.nwin * g.nb, t);
+                               dim3(MSM_THREADS), 0, st, cx.buckets.get(), cx.parts.get(), (uint64_t)g.nwin * g.nb, t);
     }
 
     // The weighted bucket sums: pyramid levels as their own launches, then the last levels (or only the gathering) in one launch
@@ -387,6 +399,112 @@ int msm_sort_selftest(const zkp_bases* bases, const Fr* const* d_scalars, size_t
         if (words[k]) HIPCHK(hipMemcpyAsync(out->d_out[k], src[k], 4 * words[k], hipMemcpyDeviceToDevice, st));
     // the bounded digits kernel writes its violation word in the slot's pinned memory: be done with it before the next entry resets it
     if (pass.bits) HIPCHK(hipStreamSynchronize(st));
+    return ZKP_OK;
+}
+
+// Self-test hook (zkp_selftest_msm_reduce_dev): what msm_partial_batch runs behind the accumulate -- launch_combine, launch_fold,
+// reduce(), wait_msm_result -- on bucket contents of the caller's, in the slot's own workspaces.  The plan is put together from the
+// pieces plan_msm uses (plan_fold, plan_reduce, acc_launch's combine grid); there are no bases, no scalars and no sort, so the hook does
+// what the sort does for the reduction: it zeroes the barrier counters of the last-levels launch (msm_partstart_kernel in an MSM).
+// Everything the reduction may read without having written it is filled with 0xFF bytes first.
+int msm_reduce_selftest(const zkp_msm_reduce_io& in, hipStream_t st, zkp_msm_reduce_geometry* geom) {
+    if (in.c < 2 || in.c > MSM_MAX_WINDOW_BITS) return fail(ZKP_E_ARG, "window width outside 2..24 bits");
+    if (!in.nwin || in.nwin > 65535) return fail(ZKP_E_ARG, "bucket sets outside 1..65535");
+    if (in.split_log > MSM_MAX_SPLIT_LOG) return fail(ZKP_E_ARG, "split_log above 2");
+    const bool combine = in.d_over != nullptr;
+    if (combine && (!in.over_cap || !in.desc_cap)) return fail(ZKP_E_ARG, "a combine block with over_cap or desc_cap 0");
+    if (!combine && (in.resume || in.more)) return fail(ZKP_E_ARG, "resume / more without a combine block");
+    Ctx& cx = ctx();
+    MsmPlan p{};
+    MsmGeom& g = p.g;
+    g.c = in.c, g.nwin = in.nwin, g.nb = 1u << (in.c - 1), g.split_log = in.split_log;
+    g.resume = in.resume ? 1u : 0u, g.more = in.more ? 1u : 0u;
+    const size_t W = g.nwin, cap = W * g.nb, nparts = (1u << g.split_log) - 1;
+    if (cap >= (1ull << 31)) return fail(ZKP_E_ARG, "nwin x 2^(c-1) >= 2^31");
+    p.nwin1 = 1, p.nbuf = 1;
+    p.over_cap = combine ? in.over_cap : 0u, p.desc_cap = combine ? in.desc_cap : 0u;
+    if (combine && ((uint64_t)W * p.desc_cap >= (1ull << 24) || (uint64_t)W * p.over_cap >= (1ull << 24)))
+        return fail(ZKP_E_ARG, "nwin x over_cap or nwin x desc_cap >= 2^24");
+    p.over_bytes = ((4 * W * (2 + (size_t)p.over_cap + p.over_cap + 1) + 16 * W * (size_t)p.desc_cap) + 255) & ~(size_t)255;
+    plan_fold(g.nwin, g.nb, g.split_log, p.fold);
+    if (const int rc = plan_reduce(g.c, g.nwin, cx.tail_max_waves, &p.red, &p.error)) return fail(rc, p.error);
+    const AccLaunch a = acc_launch(p, g);
+    p.bytes = MsmSizes{};
+    if (combine) p.bytes.over = p.over_bytes, p.bytes.pieces = 256 * W * (size_t)p.desc_cap;
+    p.bytes.buckets = p.bytes.pyr1 = p.bytes.odd0 = p.bytes.odd1 = 256 * cap;
+    p.bytes.parts = 256 * cap * nparts;
+    p.bytes.result = 4 * PYR_BAR_STRIDE * W;
+    p.bytes.host_result = 256 * W * g.c + 4 * W;
+
+    *geom = zkp_msm_reduce_geometry{};
+    geom->c = g.c, geom->nwin = g.nwin, geom->nb = g.nb, geom->split_log = g.split_log, geom->tail_max_waves = cx.tail_max_waves;
+    geom->nlevel = p.red.nlevel, geom->tail_blocks = p.red.tail_blocks, geom->tail_threads = p.red.tail_threads;
+    geom->combine_x = combine ? a.combine_x : 0u, geom->over_cap = p.over_cap, geom->desc_cap = p.desc_cap, geom->cap = cap;
+    static_assert(sizeof(geom->level) / sizeof(geom->level[0]) == MSM_MAX_WINDOW_BITS, "zkp_msm_reduce_geometry::level");
+    static_assert(sizeof(geom->fold) / sizeof(geom->fold[0]) == MSM_MAX_SPLIT_LOG, "zkp_msm_reduce_geometry::fold");
+    for (uint32_t k = 0; k < p.red.nlevel; k++) geom->level[k] = {p.red.level[k].level, p.red.level[k].half, p.red.level[k].quad, p.red.level[k].grid_x};
+    for (uint32_t t = 0; t < g.split_log; t++) geom->fold[t] = {p.fold[t].pairs, p.fold[t].lane, p.fold[t].grid_x};
+    geom->bucket_words = geom->carry_words = 64 * cap, geom->parts_words = 64 * cap * nparts;
+    geom->over_words = combine ? 2 * W : 0, geom->over_b_words = W * p.over_cap, geom->over_off_words = combine ? W * ((size_t)p.over_cap + 1) : 0;
+    geom->pieces_words = 64 * W * (size_t)p.desc_cap, geom->result_words = 64 * W * g.c, geom->flag_words = W;
+    if (!in.out_results) return ZKP_OK;
+
+    auto short_of = [](const void* q, size_t have, size_t want) { return want && (!q || have < want); };
+    if (short_of(in.d_buckets, in.buckets_words, geom->bucket_words) || short_of(in.d_parts, in.parts_words, geom->parts_words) ||
+        short_of(in.out_results, in.out_results_words, geom->result_words) || short_of(in.out_flags, in.out_flags_words, geom->flag_words) ||
+        (in.d_out_buckets && in.out_buckets_words < geom->bucket_words))
+        return fail(ZKP_E_ARG, "null or too-small buffer (zkp_msm_reduce_geometry: the words of every buffer)");
+    if (combine && (short_of(in.d_over, in.over_words, geom->over_words) || short_of(in.d_over_b, in.over_b_words, geom->over_b_words) ||
+                    short_of(in.d_over_off, in.over_off_words, geom->over_off_words) || short_of(in.d_pieces, in.pieces_words, geom->pieces_words) ||
+                    (g.resume && short_of(in.d_carry, in.carry_words, geom->carry_words)) ||
+                    (g.more && short_of(in.d_out_carry, in.out_carry_words, geom->carry_words))))
+        return fail(ZKP_E_ARG, "null or too-small buffer of the combine block (zkp_msm_reduce_geometry: the words of every buffer)");
+    if (combine) {  // the kernel trusts the sort for these: candidates within over_cap, bucket ids 1..nb (its piece range it clamps itself)
+        std::vector<uint32_t> over(2 * W), over_b(W * p.over_cap);
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(over.data(), in.d_over, 4 * over.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(over_b.data(), in.d_over_b, 4 * over_b.size(), hipMemcpyDeviceToHost));
+        for (size_t w = 0; w < W; w++) {
+            if (over[2 * w] > p.over_cap) return fail(ZKP_E_ARG, "more oversized candidates than over_cap");
+            for (uint32_t r = 0; r < over[2 * w]; r++)
+                if (over_b[w * p.over_cap + r] < 1 || over_b[w * p.over_cap + r] > g.nb) return fail(ZKP_E_ARG, "bucket id of a candidate outside 1..2^(c-1)");
+        }
+    }
+
+    MsmPass pass{p, nullptr, nullptr, 0, nullptr, st, st, 0u};
+    ZCHK(pass.grow());
+    const RangeBuffers rb = pass.range_buffers(0);
+    for (DevBuf* b : {static_cast<DevBuf*>(&cx.buckets), static_cast<DevBuf*>(&cx.pyr1), static_cast<DevBuf*>(&cx.odd0), static_cast<DevBuf*>(&cx.odd1)})
+        HIPCHK(hipMemsetAsync(b->p, 0xFF, b->cap, st));  // (buckets: a workspace larger than nwin sets keeps no stored point behind them)
+    std::memset(cx.host_result.p, 0xFF, p.bytes.host_result);  // (nothing on the device writes here: the slot's previous entry has read its results)
+    HIPCHK(hipMemsetAsync(cx.result.get(), 0, p.bytes.result, st));  // the barrier counters, one line per bucket set
+    HIPCHK(hipMemcpyAsync(cx.buckets.get(), in.d_buckets, 256 * cap, hipMemcpyDeviceToDevice, st));
+    if (nparts) HIPCHK(hipMemcpyAsync(cx.parts.get(), in.d_parts, 256 * cap * nparts, hipMemcpyDeviceToDevice, st));
+    if (combine) {
+        HIPCHK(hipMemcpyAsync(rb.over, in.d_over, 4 * geom->over_words, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(rb.over_b, in.d_over_b, 4 * geom->over_b_words, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(rb.over_off, in.d_over_off, 4 * geom->over_off_words, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(cx.pieces.get(), in.d_pieces, 4 * geom->pieces_words, hipMemcpyDeviceToDevice, st));
+        if (g.resume) HIPCHK(hipMemcpyAsync(cx.pyr1.get(), in.d_carry, 256 * cap, hipMemcpyDeviceToDevice, st));
+        pass.launch_combine(rb, g, a);
+        HIPCHK(hipGetLastError());
+        if (g.more) {  // the sums went to the hand-over array: there is nothing to fold or to reduce
+            HIPCHK(hipMemcpyAsync(in.d_out_carry, cx.pyr1.get(), 256 * cap, hipMemcpyDeviceToDevice, st));
+            if (in.d_out_buckets) HIPCHK(hipMemcpyAsync(in.d_out_buckets, cx.buckets.get(), 256 * cap, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));
+            return ZKP_OK;
+        }
+        if (g.resume) HIPCHK(hipMemsetAsync(cx.pyr1.p, 0xFF, cx.pyr1.cap, st));  // the carry has been read: pyr1 is a pyramid buffer from here on
+    }
+    pass.launch_fold(g);
+    HIPCHK(hipGetLastError());
+    if (in.d_out_buckets) HIPCHK(hipMemcpyAsync(in.d_out_buckets, cx.buckets.get(), 256 * cap, hipMemcpyDeviceToDevice, st));
+    pass.reduce();
+    HIPCHK(hipGetLastError());
+    const int rc = wait_msm_result(true, W, pass.result_flags, st);
+    std::memcpy(in.out_flags, pass.result_flags, 4 * W);
+    ZCHK(rc);
+    std::memcpy(in.out_results, pass.result_out, 256 * W * g.c);
     return ZKP_OK;
 }
 

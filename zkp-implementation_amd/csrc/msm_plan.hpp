@@ -263,6 +263,17 @@ inline int plan_reduce(uint32_t c, uint32_t nwin, uint32_t tail_max_waves, Reduc
 
 struct FoldStep { uint32_t pairs, lane, grid_x; };  // grid (grid_x, pairs); lane: one lane per add, else four
 
+// buckets += parts, pairwise, over nwin bucket sets of nb buckets: split_log steps; a step with many adds runs one lane per add, a
+// small one four (latency): msm.hpp.  Tuning aid: ZKP_FOLD_LANE_MIN, the adds in one launch from which the lane form is used.
+inline void plan_fold(uint32_t nwin, uint32_t nb, uint32_t split_log, FoldStep* fold) {
+    const uint64_t cap = (uint64_t)nwin * nb, lane_from = (uint64_t)knob_int(KNOB_FOLD_LANE_MIN);
+    for (uint32_t t = 0; t < split_log; t++) {
+        const uint32_t pairs = 1u << (split_log - 1 - t), lane = cap * pairs >= lane_from ? 1u : 0u;
+        const uint32_t per = lane ? MSM_THREADS : MSM_THREADS / 4;  // adds per workgroup
+        fold[t] = {pairs, lane, (uint32_t)((cap + per - 1) / per)};
+    }
+}
+
 struct MsmPlan {
     MsmGeom g;                  // geometry of the longest range (range_geom narrows it for shorter ones)
     SortGeom sg;
@@ -429,13 +440,7 @@ inline int plan_msm(const MsmBases& bases_in, size_t count, size_t n, const MsmF
         while (g.split_log < MSM_MAX_SPLIT_LOG && (units << g.split_log) < want_units) g.split_log++;
         g.split_log = (uint32_t)knob_int(KNOB_MSM_SPLIT_LOG, g.split_log);  // tuning aid
     }
-    // buckets += parts, pairwise: split_log steps; a step with many adds runs one lane per add, a small one four (latency): msm.hpp
-    const uint64_t cap = (uint64_t)g.nwin * g.nb, lane_from = (uint64_t)knob_int(KNOB_FOLD_LANE_MIN);
-    for (uint32_t t = 0; t < g.split_log; t++) {
-        const uint32_t pairs = 1u << (g.split_log - 1 - t), lane = cap * pairs >= lane_from ? 1u : 0u;
-        const uint32_t per = lane ? MSM_THREADS : MSM_THREADS / 4;  // adds per workgroup
-        p->fold[t] = {pairs, lane, (uint32_t)((cap + per - 1) / per)};
-    }
+    plan_fold(g.nwin, g.nb, g.split_log, p->fold);
     p->poll_result = range_geom(*p, lens.size() - 1).g.n <= (1ull << 24);
     p->ps_tile = partscatter_tile(sg.nhi);
     p->ps_lds = partscatter_lds_bytes(sg.nhi, p->ps_tile);

@@ -147,6 +147,7 @@ _SIGS = {
     "zkp_selftest_poly_trim_len_dev": ([_VP, _SZ, C.POINTER(_SZ), _VP], C.c_int),
     "zkp_selftest_msm_sort_dev": ([_VP, _VP, _SZ, _SZ, _SZ, _VP, _VP, _VP], C.c_int),
     "zkp_selftest_msm_sort_bits_dev": ([_VP, _VP, _SZ, _SZ, _SZ, C.c_uint, _VP, _VP, _VP], C.c_int),
+    "zkp_selftest_msm_reduce_dev": ([C.c_int, _VP, _VP, _VP], C.c_int),
     "zkp_srs_g1": ([_VP, _SZ, _VP], C.c_int),
     "zkp_ntt_fr": ([_VP, C.c_uint, C.c_int, _VP], C.c_int),
     "zkp_ntt_fr_dev": ([_VP, C.c_uint, _SZ, C.c_int, _VP, _VP], C.c_int),
@@ -749,6 +750,70 @@ def selftest_msm_sort_dev(bases, scalar_tensors, n, range_index=0, out_tensors=N
     d["out_words"] = {name: int(g.out_words[i]) for i, name in enumerate(MSM_SORT_OUTPUTS)}
     d["off"] = [int(x) for x in g.off[:d["nslice"] + 1]]
     return d
+
+
+class _MsmReduceLevel(C.Structure):  # zkp_msm_reduce_level in include/zkp_hip.h
+    _fields_ = [(k, C.c_uint32) for k in ("level", "half", "quad", "grid_x")]
+
+
+class _MsmFoldStep(C.Structure):  # zkp_msm_fold_step
+    _fields_ = [(k, C.c_uint32) for k in ("pairs", "lane", "grid_x")]
+
+
+_MSM_REDUCE_WORDS = ("bucket_words", "parts_words", "over_words", "over_b_words", "over_off_words", "pieces_words", "carry_words",
+                     "result_words", "flag_words")
+
+
+class _MsmReduceGeometry(C.Structure):  # zkp_msm_reduce_geometry
+    _fields_ = [(k, C.c_uint32) for k in ("c", "nwin", "nb", "split_log", "tail_max_waves", "nlevel", "tail_blocks", "tail_threads",
+                                          "combine_x", "over_cap", "desc_cap", "reserved")] + \
+               [("cap", C.c_uint64), ("level", _MsmReduceLevel * 24), ("fold", _MsmFoldStep * 2)] + [(k, C.c_uint64) for k in _MSM_REDUCE_WORDS]
+
+
+_MSM_REDUCE_IN = ("buckets", "parts", "over", "over_b", "over_off", "pieces", "carry")
+
+
+class _MsmReduceIo(C.Structure):  # zkp_msm_reduce_io
+    _fields_ = [(k, C.c_uint32) for k in ("c", "nwin", "split_log", "over_cap", "desc_cap", "resume", "more", "reserved")] + \
+               [("d_" + k, C.c_void_p) for k in _MSM_REDUCE_IN] + [(k + "_words", C.c_size_t) for k in _MSM_REDUCE_IN] + \
+               [("d_out_buckets", C.c_void_p), ("d_out_carry", C.c_void_p), ("out_buckets_words", C.c_size_t), ("out_carry_words", C.c_size_t),
+                ("out_results", C.c_void_p), ("out_flags", C.c_void_p), ("out_results_words", C.c_size_t), ("out_flags_words", C.c_size_t)]
+
+
+def selftest_msm_reduce_dev(c, nwin, split_log=0, buckets=None, parts=None, combine=None, out_buckets=None, run=True, stream=None, slot=-1):
+    """zkp_selftest_msm_reduce_dev: the MSM's combine, fold and bucket reduction on bucket contents of the caller's.
+    buckets / parts / out_buckets: int32 CUDA tensors in the plane-major layout; combine: None or a dict with over_cap, desc_cap, the
+    int32 CUDA tensors over, over_b, over_off, pieces, optionally carry (-> resume), more (flag) and out_carry (required with more).
+    run=False: nothing is launched.  -> (geometry dict, results (nwin, c, 64) uint32 or None, flags (nwin,) uint32 or None); under
+    more the results and flags are returned as they were handed in: all 0xFF."""
+    io, g = _MsmReduceIo(), _MsmReduceGeometry()
+    io.c, io.nwin, io.split_log = c, nwin, split_log
+
+    def put(name, t, prefix="d_"):
+        if t is not None:
+            setattr(io, prefix + name, _dev_ptr(t, 0).value if t.numel() else None)
+            setattr(io, name + "_words", t.numel() * t.element_size() // 4)
+
+    put("buckets", buckets)
+    put("parts", parts)
+    put("out_buckets", out_buckets)
+    if combine is not None:
+        io.over_cap, io.desc_cap = combine["over_cap"], combine["desc_cap"]
+        io.resume, io.more = int(combine.get("carry") is not None), int(bool(combine.get("more")))
+        for k in ("over", "over_b", "over_off", "pieces", "carry"):
+            put(k, combine.get(k))
+        put("out_carry", combine.get("out_carry"))
+    res = flags = None
+    if run:
+        res = np.full((max(nwin, 1), max(c, 1), 64), 0xFFFFFFFF, dtype=np.uint32)
+        flags = np.full(max(nwin, 1), 0xFFFFFFFF, dtype=np.uint32)
+        io.out_results, io.out_flags = res.ctypes.data, flags.ctypes.data
+        io.out_results_words, io.out_flags_words = res.size, flags.size
+    _chk(lib().zkp_selftest_msm_reduce_dev(slot, C.byref(io), _stream_ptr(stream), C.byref(g)))
+    d = {k: int(getattr(g, k)) for k, _ in _MsmReduceGeometry._fields_ if k not in ("level", "fold", "reserved")}
+    d["level"] = [{k: int(getattr(g.level[i], k)) for k, _ in _MsmReduceLevel._fields_} for i in range(d["nlevel"])]
+    d["fold"] = [{k: int(getattr(g.fold[i], k)) for k, _ in _MsmFoldStep._fields_} for i in range(d["split_log"])]
+    return d, res, flags
 
 
 def msm_g1_dev(bases, scalars_tensor, n, stream=None, bits=None):
